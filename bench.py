@@ -3,7 +3,12 @@
 
 A "step" is one pass of the hot path over one batch of synthetic read pairs whose ASCII bytes are already resident in
 HBM: pack -> kernels -> results in HBM.  The headline (`value`) is configs[1] of BASELINE.json: BandEd score-only,
-100 k pairs of 10 kb at 5 % error, reference default bandwidth 15 %.  The same JSON line also carries
+100 k pairs of 10 kb at 5 % error, reference default bandwidth 15 %.
+
+A plain run does only what the headline needs: it generates and uploads the pairs, runs the warm-up, times exactly
+`--steps` steps, brings the last timed step's results to the host (they give `score_checksum`, and `--dump-outputs DIR`
+writes them as .npy files) and prints the line, with `ranks_seen` (all-reduce SUM of 1 over the ranks).  With `--full`
+the same JSON line also carries
 
   workloads.quicked  configs[2]: QuickEd bound-and-align + CIGAR on the same pairs, with its own roofline / e2e /
                      cpu_baseline objects (this is the HBM-relevant workload of the path)
@@ -19,9 +24,9 @@ HBM: pack -> kernels -> results in HBM.  The headline (`value`) is configs[1] of
                      ASCII over the link, 2-bit words the caller already holds, and ASCII packed to 2 bits by the
                      library's SIMD host packer inside the clock (`ascii_hostpacked`)
   cpu_baseline       the compiled reference (or the oracle port) on the host cores, N = 1 only
-  ranks_seen         all-reduce SUM of 1 over the ranks
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]      # the headline alone
+    python bench.py --gpus N --steps K --warmup W --full                       # everything above
 
 N > 1: one process per GPU.  Under a launcher (WORLD_SIZE set: the driver's `python -m torch.distributed.run ...
 bench.py --gpus N`) this process is one rank; without one, `--gpus N` starts the N ranks itself as a child
@@ -518,9 +523,11 @@ class Bench:
         return shard.reduce_totals(self.dist, self.torch, self.device, pairs, cells, checksum, elapsed, extra_sum=extra)
 
     # -----------------------------------------------------------------------------------------------------------
-    def timed_resident(self, workload, first, count, steps, warmup, solo_steps=3, kind=None):
+    def timed_resident(self, workload, first, count, steps, warmup, solo_steps=3, kind=None, lean=False, keep_outputs=False):
         """the contract's loop: `warmup` untimed steps, then exactly `steps` steps between two barrier + synchronize.
-        -> dict(batch, scores, counters, elapsed, kernel ms overlapped / solo, cigar bytes, flow, latency)"""
+        -> dict(batch, scores, counters, elapsed, kernel ms overlapped / solo, cigar bytes, flow, latency)
+        lean: the results and counters of the last timed step only (no latency run, no solo runs); keep_outputs: what that
+        step computed, as its caller receives it (outputs: scores, statuses and, for QuickEd, the CIGAR strings)"""
         args, capi = self.args, self.capi
         params = capi.make_params(**self.kw(workload))
         if self._cache is None or self._cache[0] != (first, count):      # the workloads of one line run on the same pairs
@@ -552,6 +559,17 @@ class Bench:
             self.barrier(rb)
             return time.perf_counter() - t0
 
+        def last_step():
+            # the results of the last timed run on the host, as its caller gets them (a queued run's through the fetch)
+            if not args.sync_each_step and rb.fetch() < 0:
+                raise RuntimeError("quicked_batch_fetch failed")
+            scores, status = rb.scores()
+            out = {"scores": scores, "status": status}
+            if quick and keep_outputs:
+                pool, off = rb.cigar_view()
+                out["cigar_pool"], out["cigar_off"] = pool.copy(), off.copy()
+            return out
+
         try:
             # QuickEd: at least two untimed synchronous runs -- the first run of a batch is always a classic one and sets
             # the bound estimate, the second shows whether the fast flow defers pairs to the fetch
@@ -580,6 +598,21 @@ class Bench:
             elapsed = timed_loop()
             kern_ms, kern_n = kernel_time()
             sets = capi.pool_stats()["sets"]
+            outputs = last_step() if (lean or keep_outputs) else None
+            if lean:
+                if quick and os.environ.get("QE_QUICKED_FAST") != "0" and rb.deferred_pairs():
+                    # the fetch aligned pairs the timed runs left undone: time the host-driven flow instead (as below)
+                    os.environ["QE_QUICKED_FAST"] = "0"; capi.reload_env()
+                    flow["timed_flow"] = "classic (host-driven stages): the fast flow deferred pairs to the fetch on this data (re-timed)"
+                    flow["deferred_pairs"] = rb.deferred_pairs()
+                    run_checked(True)
+                    elapsed = timed_loop()
+                    outputs = last_step()
+                scores, status = outputs["scores"], outputs["status"]
+                assert (status >= 0).all(), "some pairs failed"
+                return dict(batch=batch, scores=scores, counters=rb.counters(), elapsed=elapsed, sets=sets, flow=flow, params=params,
+                            cigar_bytes=capi.lib().quicked_batch_cigar_bytes(rb._h) if quick else None,
+                            outputs=outputs if keep_outputs else None)
             # one synchronous run to fetch results + work counters for the report ...
             tl0 = time.perf_counter()
             run_checked(True)
@@ -593,6 +626,8 @@ class Bench:
                 kernel_time()
                 elapsed = timed_loop()
                 kern_ms, kern_n = kernel_time()
+                if keep_outputs:
+                    outputs = last_step()
                 run_checked(True)
             scores, status = rb.scores()
             assert (status >= 0).all(), "some pairs failed"
@@ -615,7 +650,8 @@ class Bench:
             capi.reload_env()
             rb.close()
         return dict(batch=batch, scores=scores, counters=counters, elapsed=elapsed, kern_ms=kern_ms, kern_n=kern_n,
-                    solo_ms=solo_ms, solo_n=solo_n, cigar_bytes=cig, flow=flow, sets=sets, latency_s=latency, params=params)
+                    solo_ms=solo_ms, solo_n=solo_n, cigar_bytes=cig, flow=flow, sets=sets, latency_s=latency, params=params,
+                    outputs=outputs)
 
     # -----------------------------------------------------------------------------------------------------------
     def roofline(self, workload, r, pairs, step_s):
@@ -727,25 +763,37 @@ class Bench:
         return out
 
     # -----------------------------------------------------------------------------------------------------------
-    def workload_object(self, workload, pairs, steps, warmup, with_e2e, with_cpu, scaling="weak", kind=None, solo_steps=3):
-        """one workload at `pairs` pairs per GPU (weak) or in total (strong): resident rate (+ roofline, e2e, cpu baseline)"""
+    def workload_object(self, workload, pairs, steps, warmup, with_e2e, with_cpu, scaling="weak", kind=None, solo_steps=3, lean=False,
+                        keep_outputs=False):
+        """one workload at `pairs` pairs per GPU (weak) or in total (strong): resident rate (+ roofline, e2e, cpu baseline);
+        lean: the rate alone (no roofline / valu / single-batch figures, which take runs of their own); keep_outputs: the
+        last timed step's results under "outputs" (popped by the caller)"""
         args = self.args
         first, count, _ = shard.plan(pairs, self.rank, self.world, scaling)
-        r = self.timed_resident(workload, first, count, steps, warmup, solo_steps=solo_steps, kind=kind)
+        r = self.timed_resident(workload, first, count, steps, warmup, solo_steps=solo_steps, kind=kind, lean=lean,
+                                keep_outputs=keep_outputs)
         r["kind"], r["solo_steps"] = kind, solo_steps
         cells = r["batch"].cells()
         checksum = int(r["scores"].astype(np.int64).sum())
         tot_pairs, tot_cells, tot_checksum, max_elapsed, _ = self.reduce(count, cells, checksum, r["elapsed"])
         step_s = max_elapsed / steps
-        roof, valu, work_blocks = self.roofline(workload, r, pairs, step_s)
+        if lean:
+            work_blocks = int(r["counters"][0 if workload == "banded_score" or kind == 2 else 1])      # as roofline() counts them
+        else:
+            roof, valu, work_blocks = self.roofline(workload, r, pairs, step_s)
         obj = {"value": tot_pairs * steps / max_elapsed, "unit": "alignments/s", "ms_per_step": step_s * 1e3,
                "gcups": tot_cells * steps / max_elapsed / 1e9,
                # cells actually computed (SURVEY 8d "band GCUPS"): 64 rows x block-advances of the dominant kernel, this rank x world
                "band_gcups": 64.0 * work_blocks * self.world * steps / max_elapsed / 1e9,
                "pairs_per_gpu": count, "total_pairs": tot_pairs, "scaling": scaling, "steps": steps,
-               "runs_in_flight": r["sets"], "single_batch_latency_ms": r["latency_s"] * 1e3,
-               "single_batch_value": count / r["latency_s"],
-               "score_checksum": tot_checksum, "roofline": roof, "valu": valu}
+               "runs_in_flight": r["sets"]}
+        if not lean:
+            obj.update({"single_batch_latency_ms": r["latency_s"] * 1e3, "single_batch_value": count / r["latency_s"]})
+        obj["score_checksum"] = tot_checksum
+        if not lean:
+            obj.update({"roofline": roof, "valu": valu})
+        if keep_outputs:
+            obj["outputs"] = r["outputs"]
         if r["flow"]:
             obj["quicked_flow"] = r["flow"]
         if r["cigar_bytes"] is not None:
@@ -800,6 +848,51 @@ def quicked_score_leg(B, args, expect_checksum):
         rb.close()
 
 
+DUMP_MAX_PAIRS = 1 << 20          # scores / statuses of at most this many pairs (float64: 16 MB), a seeded sample beyond
+DUMP_CIGAR_BYTES = 8 << 20        # CIGAR bytes of the seeded pair sample (float32: 32 MB) ...
+DUMP_CIGAR_PAIRS = 1 << 18        # ... of at most this many pairs (indices + offsets, float64: 4 MB)
+
+
+def dump_outputs(out_dir, outputs, batch, seed, prefix=""):
+    """--dump-outputs: the last timed step's results as <out_dir>/<prefix><name>.npy, float64 / float32, at most 64 MB.
+    scores, status: one value per pair (a fixed, seeded sample of DUMP_MAX_PAIRS pairs beyond that, their indices in
+    pairs.npy).  QuickEd: the CIGAR strings of a fixed, seeded sample of at most DUMP_CIGAR_PAIRS pairs (cigar_pairs)
+    whose worst-case string lengths (2 bytes per pattern + text base) fit DUMP_CIGAR_BYTES, as ASCII codes back to back (cigar_bytes, each
+    string NUL-terminated) and their offsets (cigar_offsets, -1: no alignment)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    n = len(outputs["scores"])
+    arrays = {}
+    if n > DUMP_MAX_PAIRS:
+        idx = np.sort(rng.choice(n, DUMP_MAX_PAIRS, replace=False))
+        arrays["pairs"] = idx.astype(np.float64)
+    else:
+        idx = np.arange(n)
+    arrays["scores"] = outputs["scores"][idx].astype(np.float64)
+    arrays["status"] = outputs["status"][idx].astype(np.float64)
+    if "cigar_pool" in outputs:
+        worst = 2 * (int(batch.pattern_len.max(initial=0)) + int(batch.text_len.max(initial=0))) + 1
+        k = min(n, DUMP_CIGAR_PAIRS, max(1, DUMP_CIGAR_BYTES // worst))
+        cidx = np.sort(rng.choice(n, k, replace=False))
+        pool, off = outputs["cigar_pool"], outputs["cigar_off"]
+        parts, offs, o = [], [], 0
+        for i in cidx:
+            if off[i] < 0:
+                offs.append(-1)
+                continue
+            b = int(off[i])
+            z = np.flatnonzero(pool[b:b + worst] == 0)
+            e = b + int(z[0]) if len(z) else b + int(np.flatnonzero(pool[b:] == 0)[0])
+            parts.append(pool[b:e + 1])
+            offs.append(o)
+            o += e + 1 - b
+        arrays["cigar_pairs"] = cidx.astype(np.float64)
+        arrays["cigar_offsets"] = np.asarray(offs, dtype=np.float64)
+        arrays["cigar_bytes"] = (np.concatenate(parts) if parts else np.zeros(0, np.uint8)).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -838,6 +931,12 @@ def main():
     ap.add_argument("--sync-each-step", action="store_true",
                     help="profiling aid: no overlap between consecutive runs, so per-kernel durations are those of a kernel alone")
     ap.add_argument("--seed", type=int, default=0x51CED)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline / VALU / single-batch figures, e2e, CPU baselines, the other "
+                         "workloads and the strong-scaling legs (the options above that shape them apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (scores, status; QuickEd: a seeded sample of "
+                         "CIGAR strings); at N > 1 every rank writes its shard's as DIR/rank<r>_<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -881,9 +980,13 @@ def main():
     ranks_seen = shard.count_ranks(dist, torch, device)
 
     # ---- the headline: weak scaling, `pairs` pairs per GPU, inputs resident in HBM
-    head = B.workload_object(args.workload, args.pairs, args.steps, args.warmup, with_e2e=not args.no_e2e,
-                             with_cpu=not args.no_cpu_baseline)
-    default_shape = args.workload == "banded_score" and not args.no_workloads
+    full = args.full
+    head = B.workload_object(args.workload, args.pairs, args.steps, args.warmup, with_e2e=full and not args.no_e2e,
+                             with_cpu=full and not args.no_cpu_baseline, lean=not full, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, head.pop("outputs"), B._cache[1], args.seed, "" if world == 1 else f"rank{rank}_")
+    # ---- --full: the other workloads and legs of the line
+    default_shape = full and args.workload == "banded_score" and not args.no_workloads
     others = {}
     if default_shape:
         # configs[2] on the same pairs: QuickEd bound-and-align + CIGAR (the HBM-relevant workload of the path)
@@ -954,7 +1057,7 @@ def main():
         B.capi.pool_trim()
     # ---- strong scaling: `pairs` pairs in total (BASELINE.json's "100 k pairs at 8 GPUs"); at N = 1 the per-GPU share of it
     strong, strong_share = None, None
-    if not args.no_strong:
+    if full and not args.no_strong:
         wls = [args.workload] + [w for w in others if w == "quicked"]
         if world > 1:
             strong = {}
@@ -1041,11 +1144,13 @@ def main():
                                    "starts, results left in HBM (end-to-end rates: e2e)",
                        "pairs_per_gpu": args.pairs, "length": args.length, "error": args.error,
                        "bandwidth": args.bandwidth, "parallelism": B.parallelism},
-            "runs_in_flight": head["runs_in_flight"], "single_batch_latency_ms": head["single_batch_latency_ms"],
-            "roofline": dict(head["roofline"], hbm_copy_measured_GBs=measured_copy_bandwidth()),
-            "valu": head["valu"],
-            "score_checksum": head["score_checksum"],
+            "runs_in_flight": head["runs_in_flight"],
         }
+        if full:
+            line["single_batch_latency_ms"] = head["single_batch_latency_ms"]
+            line["roofline"] = dict(head["roofline"], hbm_copy_measured_GBs=measured_copy_bandwidth())
+            line["valu"] = head["valu"]
+        line["score_checksum"] = head["score_checksum"]
         for k in ("quicked_flow", "cigar_bytes_per_step", "e2e", "cpu_baseline"):
             if k in head:
                 line[k] = head[k]
@@ -1063,7 +1168,7 @@ def main():
             line["e2e_ascii_link_value"] = e2e["ascii_pinned"]["value"]   # the same with raw ASCII over PCIe: the link's floor
         if isinstance(e2e.get("2bit_pinned"), dict) and "value" in e2e["2bit_pinned"]:
             line["e2e_2bit_value"] = e2e["2bit_pinned"]["value"]
-        mc = line["roofline"].get("hbm_copy_measured_GBs")
+        mc = line["roofline"].get("hbm_copy_measured_GBs") if full else None
         if mc:
             line["roofline"]["frac_of_measured_copy"] = line["roofline"]["achieved"] / mc
         if others:

@@ -79,32 +79,18 @@ def build_harness(force=False):
 
 
 REF = "/root/reference"
-REF_CALLERS = os.path.join(ROOT, "tools", "bin", "ref_callers")
+REF_CALLERS = os.path.join(ROOT, "oracle", "_ref", "ref_callers")
 
 
 def build_ref_callers(force=False):
     """Drop-in proof: the reference's OWN callers -- tests/quicked_harness.c, examples/*.c and the C++
-    binding with its examples -- compiled unmodified, from where they lie under /root/reference, against
-    the REFERENCE's headers, and linked against libquicked_hip.so instead of libquicked.a.  Only where the
-    reference tree exists; the binaries travel with the snapshot like the in-tree .so files."""
+    binding with its examples -- compiled unmodified, from where they lie in the reference tree, against
+    the REFERENCE's headers, and linked against libquicked_hip.so instead of libquicked.a
+    (oracle/Makefile: ref-callers).  Only where the reference tree exists; the binaries go to
+    oracle/_ref/ref_callers with the other reference builds."""
     if not os.path.isdir(os.path.join(REF, "quicked")):
         return None
-    os.makedirs(REF_CALLERS, exist_ok=True)
-    inc = ["-I", REF, "-I", os.path.join(REF, "quicked"), "-I", os.path.join(REF, "quicked", "include")]
-    link = ["-L", HERE, "-lquicked_hip", "-Wl,-rpath," + HERE]
-    jobs = [(os.path.join(REF, "tests", "quicked_harness.c"), "quicked_harness", "gcc", [])]
-    for name in sorted(os.listdir(os.path.join(REF, "examples"))):
-        if name.endswith(".c"):
-            jobs.append((os.path.join(REF, "examples", name), "example_" + name[:-2], "gcc", []))
-    cpp_binding = os.path.join(REF, "bindings", "cpp", "quicked.cpp")
-    for name in sorted(os.listdir(os.path.join(REF, "examples", "bindings"))):
-        if name.endswith(".cpp"):
-            jobs.append((os.path.join(REF, "examples", "bindings", name), "binding_" + name[:-4] + "_cpp", "g++",
-                         [cpp_binding, "-I", os.path.join(REF, "bindings", "cpp")]))
-    for src, out, cc, extra in jobs:
-        exe = os.path.join(REF_CALLERS, out)
-        if force or _newer(exe, [src, HIP_LIB]):
-            _run([cc, "-O2", "-w", src] + extra + inc + link + ["-o", exe])
+    _run(["make", "-C", os.path.join(ROOT, "oracle")] + (["-B"] if force else []) + ["ref-callers", "REF=" + REF])
     return REF_CALLERS
 
 

@@ -252,3 +252,67 @@ def edlib_distance(pattern, text):
     assert r.status == 0
     _edlib.edlibFreeAlignResult(r)
     return d
+
+
+# --------------------------------------------------------------------------- #
+# the compiled reference's results as recorded (tests/golden/ref_cases.json, written by tests/golden/make_ref_cases.py
+# from the same seeded inputs): what tests/test_oracle_vs_ref.py compares with where oracle/_ref was not built.  Where it
+# was, the live result is used and must still equal its record.
+# --------------------------------------------------------------------------- #
+REF_CASES = os.path.join(ROOT, "tests", "golden", "ref_cases.json")
+RECORD = None          # make_ref_cases.py sets a dict here: the live results are collected into it instead of checked
+_cases = None
+
+
+def case_key(kind, *parts):
+    """content key of one case: the call's kind, its input bytes and its parameters"""
+    import hashlib
+    import json
+    h = hashlib.sha256(kind.encode())
+    for x in parts:
+        h.update(b"\0")
+        h.update(x if isinstance(x, bytes) else json.dumps(x, sort_keys=True).encode())
+    return h.hexdigest()[:24]
+
+
+def digest(res):
+    """(status, score, cigar) -> [status, score, SHA-256 of the cigar or None]: the form results are recorded in"""
+    import hashlib
+    st, sc, cg = res[:3]
+    return [st, sc, hashlib.sha256(cg.encode()).hexdigest() if cg is not None else None]
+
+
+def _expected(key, live, have):
+    global _cases
+    if _cases is None:
+        import json
+        if os.path.exists(REF_CASES):
+            with open(REF_CASES) as f:
+                _cases = json.load(f)["cases"]
+        else:
+            _cases = {}
+    rec = _cases.get(key)
+    if have:
+        got = live()
+        if RECORD is not None:
+            RECORD[key] = got
+        else:
+            assert rec is None or rec == got, f"tests/golden/ref_cases.json[{key}] = {rec}, the compiled reference now gives {got}"
+        return got
+    assert rec is not None, f"no recorded reference result for case {key}: regenerate tests/golden/ref_cases.json (make_ref_cases.py)"
+    return rec
+
+
+def ref_expected(pattern, text, **kw):
+    """the reference's (status, score, cigar) for quicked_align, in digest() form"""
+    return _expected(case_key("align", pattern, text, kw), lambda: digest(ref_align(pattern, text, **kw)), have_ref())
+
+
+def ref_sam_expected(ops, show_mismatches):
+    """the reference's cigar_sprint_SAM_CIGAR over an operations string"""
+    return _expected(case_key("sam", ops, bool(show_mismatches)), lambda: ref_sam_cigar(ops, show_mismatches), have_ref())
+
+
+def edlib_expected(pattern, text):
+    """edlib's global edit distance"""
+    return _expected(case_key("edlib", pattern, text), lambda: edlib_distance(pattern, text), have_edlib())

@@ -1665,13 +1665,15 @@ def test_quicked_device_side_stage1_equals_the_classic_flow(monkeypatch):
 
 def test_bench_times_the_classic_flow_when_pairs_leave_stage_1():
     """bench.py's timed loop never fetches, and an un-fetched fast QuickEd run leaves the pairs past stage 1 undone: on
-    data with such pairs the bench must time the host-driven flow (and say so), on the benchmark's kind of data the fast one"""
+    data with such pairs the bench must time the host-driven flow (and say so), on the benchmark's kind of data the fast one.
+    Both in a plain run and with --full."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for extra, want in ((["--error", "0.02", "--indels-num", "2", "--indels-len", "300"], "classic"),
-                        (["--error", "0.05"], "stage-1 rule on the device"), (["--error", "0.35"], "stage-1 rule on the device")):
+    for (extra, want), mode in [(c, m) for c in ((["--error", "0.02", "--indels-num", "2", "--indels-len", "300"], "classic"),
+                                                 (["--error", "0.05"], "stage-1 rule on the device"),
+                                                 (["--error", "0.35"], "stage-1 rule on the device")) for m in ([], ["--full"])]:
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "quicked", "--pairs", "1500", "--length", "2000",
-                              "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-e2e"] + extra,
+                              "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-e2e"] + mode + extra,
                              capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1837,7 +1839,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n = 3000
-    common = ["--steps", "2", "--warmup", "1", "--length", "2000", "--no-cpu-baseline", "--e2e-batches", "3", "--cfg5-pairs", "5000"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--length", "2000", "--no-cpu-baseline", "--e2e-batches", "3", "--cfg5-pairs", "5000"]
     env = dict(os.environ, QE_BENCH_SHARE_GPU="1", QE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                          "--master-port", "29611", os.path.join(root, "bench.py"), "--gpus", "2", "--pairs", str(n)] + common,
@@ -1857,7 +1859,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(tmp_path):
     # config 5's leg: QuickEd + CIGAR, --cfg5-pairs IN TOTAL split over the ranks; the two shards add up to the whole
     c5 = two["workloads"]["cfg5"]
     assert c5["total_pairs"] == 5000 and c5["pairs_per_gpu"] == 2500 and c5["value"] > 0 and "5000 pairs" in c5["data"]
-    rq = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "quicked", "--pairs", "5000", "--no-e2e",
+    rq = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--workload", "quicked", "--pairs", "5000", "--no-e2e",
                          "--no-strong", "--steps", "2", "--warmup", "1", "--length", "2000", "--no-cpu-baseline"],
                         capture_output=True, text=True, timeout=900)
     assert rq.returncode == 0, rq.stderr[-3000:]
@@ -1875,7 +1877,7 @@ def test_bench_reduces_through_rccl_on_one_gpu():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--gpus", "1", "--pairs", "3000", "--length", "2000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
+    common = ["--full", "--gpus", "1", "--pairs", "3000", "--length", "2000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
               "--indel-pairs", "0", "--cfg4-pairs", "0", "--mixed-share", "0", "--cfg5-pairs", "8000"]
     env = dict(os.environ, QE_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     env.pop("QE_BENCH_BACKEND", None)
@@ -1909,7 +1911,7 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n = 125
-    common = ["--steps", "2", "--warmup", "1", "--length", "2000", "--no-cpu-baseline", "--no-workloads", "--e2e-batches", "2"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--length", "2000", "--no-cpu-baseline", "--no-workloads", "--e2e-batches", "2"]
     env = dict(os.environ, QE_BENCH_SHARE_GPU="1", QE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r8 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                          "--master-port", "29631", os.path.join(root, "bench.py"), "--gpus", "8", "--pairs", str(n)] + common,
@@ -1925,3 +1927,53 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
     assert eight["strong"]["total_pairs"] == n and eight["strong"]["value"] > 0
     assert eight["e2e"]["ascii_hostpacked"]["host_pack_threads_per_uploader"] >= 1
     assert eight["e2e"]["ascii_hostpacked"]["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_timed_steps_results(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the headline alone, and --dump-outputs writes
+    what its last timed step computed: BandEd score-only scores equal to the oracle's for every pair, QuickEd's scores
+    and its CIGAR sample byte-identical to the oracle's; the same arguments give the same files."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, length = 600, 1000
+    base = ["--pairs", str(n), "--length", str(length), "--steps", "3", "--warmup", "1"]
+
+    def run(extra, d):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + base + extra + ["--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    def load(d, name):
+        a = np.load(os.path.join(d, name + ".npy"))
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        return a
+
+    pairs = list(datagen.generate(n, length, 0.05, seed=datagen.DEFAULT_SEED).pairs())
+    line = run([], tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["unit"] == "alignments/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - n / line["ms_per_step"] * 1e3) / line["value"] < 1e-6
+    for k in ("roofline", "valu", "e2e", "cpu_baseline", "workloads", "strong_share", "single_batch_latency_ms"):
+        assert k not in line, k
+    scores, status = load(tmp_path / "a", "scores"), load(tmp_path / "a", "status")
+    assert len(scores) == n and (status >= 0).all() and int(scores.sum()) == line["score_checksum"]
+    assert scores.astype(np.int64).tolist() == [oracle_cached(p, t, algo=O.BANDED, only_score=True, bandwidth=15)[1] for p, t in pairs]
+    run([], tmp_path / "b")
+    for name in ("scores", "status"):
+        assert np.array_equal(load(tmp_path / "a", name), load(tmp_path / "b", name)), name
+
+    line = run(["--workload", "quicked"], tmp_path / "q")
+    assert line["steps"] == 3 and "quicked_flow" in line and "roofline" not in line
+    scores, status = load(tmp_path / "q", "scores"), load(tmp_path / "q", "status")
+    exp = [oracle_cached(p, t, algo=O.QUICKED) for p, t in pairs]
+    assert [(int(a), int(b)) for a, b in zip(status, scores)] == [(e[0], e[1]) for e in exp]
+    idx, off = load(tmp_path / "q", "cigar_pairs").astype(np.int64), load(tmp_path / "q", "cigar_offsets").astype(np.int64)
+    raw = load(tmp_path / "q", "cigar_bytes").astype(np.uint8).tobytes()
+    assert len(idx) == n and len(off) == n
+    for i, o in zip(idx, off):
+        assert raw[o:raw.index(b"\0", o)].decode() == exp[i][2], i

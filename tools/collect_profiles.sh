@@ -8,7 +8,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}      # the repository's root on the GPU box (or wherever the script lies)
 cd /tmp && export TMPDIR=/tmp; cd "$R"
 out=gpurun_out/$tag; mkdir -p $out
-one="--no-workloads --no-strong --indel-pairs 0 --no-cpu-baseline --no-e2e"
+one="--full --no-workloads --no-strong --indel-pairs 0 --no-cpu-baseline --no-e2e"
 for wl in $wls; do
   case $wl in
     banded_score) args="--workload banded_score"; steps=10;;
@@ -63,8 +63,8 @@ done
 python3 tools/summarise_pmc.py $out $tag $wls > /dev/null
 cp $out/pmc_traffic_latest.json profiles/pmc_traffic_latest.json      # (on the box's copy: the line below prints the traffic of THESE kernels)
 # the full line (what the driver runs) and config 4 on its own
-( time python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_line.json 2> $out/bench_line.err ) 2> $out/${tag}_bench_line_time.txt
-python3 bench.py --workload quicked --pairs 10000 --length 100000 --error 0.1 --steps 20 --warmup 3 --no-workloads --no-strong --indel-pairs 0 > $out/${tag}_bench_cfg4.json 2> $out/bench_cfg4.err
+( time python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_line.json 2> $out/bench_line.err ) 2> $out/${tag}_bench_line_time.txt
+python3 bench.py --full --workload quicked --pairs 10000 --length 100000 --error 0.1 --steps 20 --warmup 3 --no-workloads --no-strong --indel-pairs 0 > $out/${tag}_bench_cfg4.json 2> $out/bench_cfg4.err
 python3 tools/single_call_latency.py > $out/${tag}_single_call_latency.txt 2> $out/single_call_latency.err
 # WindowEd on its own (the WINDOWED algorithm's default shape is 9 / 1: k_windowed_cp), history path against checkpoint path
 for cp in 0 1; do echo "== QE_WINDOWED_CP=$cp"; QE_WINDOWED_CP=$cp python3 tools/probe_windowed_n.py 2>&1; done > $out/${tag}_windowed_rates.txt

@@ -40,7 +40,7 @@ def paragraph(tag=None):
                 lat[(int(mm.group(1)), mm.group(2))] = float(mm.group(3))
     cfg = d["config"]
     text = (
-        f"Measured on one MI355X (`profiles/{tag}_bench_line.json` -- the one line `python bench.py` prints -- and "
+        f"Measured on one MI355X (`profiles/{tag}_bench_line.json` -- the one line `python bench.py --full` prints -- and "
         f"`{tag}_bench_cfg4.json`; this paragraph is generated from them by `tools/readme_numbers.py`), "
         f"{cfg['pairs_per_gpu'] // 1000} k pairs of {cfg['length'] // 1000} kb at {cfg['error'] * 100:.0f} % error per batch: "
         f"BandEd score-only **{m(d['value'], 2)} alignments/s** device-resident ({d['gcups'] / 1e3:.0f} k GCUPS); "
