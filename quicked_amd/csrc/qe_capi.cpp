@@ -314,6 +314,8 @@ QE_API quicked_status_t quicked_pool_trim(void) {
     }
 }
 
+// Test hook, not in the public header: parses the QE_* switches again (qe_pool.h: switches_reload).  The in-process test
+// suites change switches between runs and reach it through capi.reload_env().
 QE_API quicked_status_t quicked_debug_reload_env(void) {
     qe::switches_reload();
     return QUICKED_OK;

@@ -214,7 +214,7 @@ static int quicked_estimate(std::vector<int32_t>& bounds) {
 }
 // per task: no bound exceeds max(m, n) (the bandwidth percentage only enters stage 3, quicked.c:246)
 static int quicked_task_estimate(int est_bound, int longest) { return std::max(1, std::min(est_bound, std::max(longest, 65))); }
-static bool quicked_fast_enabled(const Context& C) { return !C.memory_tight && env_int("QE_QUICKED_FAST", 1) != 0; }
+static bool quicked_fast_enabled(const Context& C) { return !C.memory_tight && sw(Sw::QuickedFast) != 0; }
 
 // known_s1: stage 1 is known already (the fast flow's leftovers: bound and "goes on to stage 2" per task) -- not run again
 struct KnownStage1 { std::vector<int32_t> score; std::vector<uint8_t> stage2; };
@@ -452,9 +452,8 @@ static void quicked_classic(quicked_batch& B, Context& C, const quicked_params_t
 static bool quicked_fast_wanted(const quicked_batch& B, const Context& C, const quicked_params_t& p, const TaskList& L,
                                 std::vector<int32_t>& est, bool fetch) {
     if (p.algo != QUICKED || !quicked_fast_enabled(C) || B.est_bound <= 0) return false;   // the first run of a batch is a classic one
-    if (p.only_score && fetch && env_int("QE_QUICKED_SCORE_PASS_FAST", 1) == 0 && quicked_score_pass_wanted()) return false;   // the classic flow ends in the score pass
     if (tl_timers.align) return false;          // quicked_align: the aligner's stage timers bracket host-synchronous stages
-    const int forced = env_int("QE_QUICKED_EST", 0);                   // tests: a small estimate sends pairs through the overflow path
+    const int forced = sw(Sw::QuickedEst);                   // tests: a small estimate sends pairs through the overflow path
     const uint64_t split = split_threshold();
     est.assign(L.pair.size(), 0);
     for (size_t t = 0; t < L.pair.size(); ++t) {
@@ -1148,7 +1147,7 @@ static void finisher_work(const FinishJob& job, std::vector<FinishJob>& taken) {
         std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
     // other queued jobs whose runs are over too: the same flow serves their pairs (merged_finish)
-    const int merge_max = std::max(1, env_int("QE_FINISH_MERGE", 4));
+    const int merge_max = std::max(1, sw(Sw::FinishMerge));
     std::vector<FinishJob> group{job};
     {
         std::lock_guard<std::mutex> lk(g_fin_mu);
@@ -1215,7 +1214,7 @@ static void finisher_work(const FinishJob& job, std::vector<FinishJob>& taken) {
             // number of pairs (12.5 k-pair batches with 1 % hard pairs: 0.54 -> 1.08 M alignments/s) -- a flow of its own
             // for a batch that left thousands (20 k indel-heavy pairs each: merged, three of them ran 5 x slower than apart)
             std::sort(items.begin(), items.end(), [](const MergeItem& a, const MergeItem& b) { return a.W.Ls.pair.size() < b.W.Ls.pair.size(); });
-            const size_t merge_pairs = (size_t)std::max(0, env_int("QE_FINISH_MERGE_PAIRS", 8192));
+            const size_t merge_pairs = (size_t)std::max(0, sw(Sw::FinishMergePairs));
             size_t nm = 0, pairs = 0;
             while (nm < items.size() && pairs + items[nm].W.Ls.pair.size() <= merge_pairs) pairs += items[nm++].W.Ls.pair.size();
             if (nm < 2) nm = 0;
@@ -1343,7 +1342,7 @@ void finisher_retire() {
 
 // called by run_batch with B.fin_mu held
 static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf) {
-    const int max_threads = env_int("QE_FINISHERS", 3);           // read per call: tests switch it
+    const int max_threads = sw(Sw::Finishers);           // read per call: tests switch it
     if (max_threads <= 0) return;
     if (g_fin_stop.load()) return;
     ++B.fin_jobs;

@@ -1503,9 +1503,8 @@ __global__ __launch_bounds__(512) void k_banded_coop_lds(CoopLdsArgs X) {
     const bool hasN = (fl & FLAG_HAS_N) != 0;
     const Geom GE = band_geometry(m, n, cut_in);
     const int nw = (m + 63) >> 6;
-    const bool fgeom = FILL || A.fill_geom != 0;                        // score-only over the fill's cells (BandedArgs::fill_geom)
-    const int nsl = fgeom ? GE.ebb : ((GE.cutoff + 63) >> 6) + 1;       // the score-only passes use their own narrower band (bpm_banded.c:801-803)
-    const int stop_row = fgeom ? nw - 1 : nw;                           // bpm_banded.c:295 / 917
+    const int nsl = FILL ? GE.ebb : ((GE.cutoff + 63) >> 6) + 1;        // the score-only passes use their own narrower band (bpm_banded.c:801-803)
+    const int stop_row = FILL ? nw - 1 : nw;                            // bpm_banded.c:295 / 917
     const int lvl_last = (m - 1) & 63;
     const int prolog = GE.prolog;
     // my slots, and the passes every lane of the wave walks them in
@@ -2531,9 +2530,6 @@ template __global__ void k_banded_sys2<false>(BandedArgs);
 // ---------------------------------------------------------------------------
 // RLE emitter shared by the tracebacks: ops arrive back to front
 // ---------------------------------------------------------------------------
-#ifndef QE_TB_ELIDE
-#define QE_TB_ELIDE 0      // tools/pmc_tb_elide.sh: k_traceback with one kind of memory access left out (results garbage, time is the datum)
-#endif
 struct RunSink {
     u32* runs; int cap; int nruns; int cur_op; int cur_len; int nops; int edits; int stride;
     // stride: elements between consecutive runs of this lane's task: 64 in the [idx][lane] layout (one coalesced row per store
@@ -2564,7 +2560,7 @@ struct RunSink {
     __device__ __forceinline__ void emit(int op, int count, bool pred) {
         const bool brk = pred && op != cur_op;
         const bool st = brk && cur_len > 0;
-        if (!(QE_TB_ELIDE & 1)) if (st && nruns < cap) runs[(int64_t)nruns * stride] = ((u32)cur_len << 2) | (u32)cur_op;
+        if (st && nruns < cap) runs[(int64_t)nruns * stride] = ((u32)cur_len << 2) | (u32)cur_op;
         nruns += st ? 1 : 0;
         cur_len = brk ? count : cur_len + (pred ? count : 0);
         cur_op = brk ? op : cur_op;
@@ -2755,14 +2751,11 @@ __global__ __launch_bounds__(512) void k_traceback(TraceArgs A) {
         if (act) {
             if (k != ck) {
                 ck = k; cs = -1;
-                if (QE_TB_ELIDE & 8) { cf_a = 0; cf_b = 0; cl_b = gns - 1; T0 = 0x9E3779B97F4A7C15ull * (u64)(k + lane + 1); T1 = T0 >> 7; TN = 0; }
-                else {
                 cf_a = cf[(int64_t)(k + 1) * 64]; cf_b = cf[(int64_t)k * 64]; cl_b = cl[(int64_t)k * 64];
                 load_planes(tp, t0 + 64 * k, T0, T1, TN);
-                }
             }
             const int s = Rb - (k - G.prolog);
-            if (Rb != cR) { cR = Rb; if (QE_TB_ELIDE & 8) { pa = 0xD1B54A32D192ED03ull * (u64)(Rb + lane + 1); pb = pa >> 5; pn = 0; } else load_planes(pp, p0 + 64 * Rb, pa, pb, pn); }
+            if (Rb != cR) { cR = Rb; load_planes(pp, p0 + 64 * Rb, pa, pb, pn); }
             // a step at column h reads Pv of stored column h + 1: inside the band of THAT column's chunk or 0
             // (oracle header).  All but the last column of the tile share this chunk; the last may be the chunk's last.
             inb_same = (u32)((s >= 0) & (s >= cf_b) & (s <= cl_b));
@@ -2775,11 +2768,10 @@ __global__ __launch_bounds__(512) void k_traceback(TraceArgs A) {
             const int pos_v = k - G.prolog, s = Rb - pos_v;
             computed = s >= cf_b && s <= min(cl_b, nw - 1 - pos_v);
             if (computed) {
-                const int se = (QE_TB_ELIDE & 14) ? min(max(s, 0), gns - 1) : s;        // (with made-up band edges any slot may come up)
-                const uint4 c0 = (QE_TB_ELIDE & 2) ? make_uint4((u32)q * 2654435761u, (u32)lane, 0u, 0u) : cp[(int64_t)(q * (TW / QE_CP_COLS)) * cps + (int64_t)se * 64];
+                const uint4 c0 = cp[(int64_t)(q * (TW / QE_CP_COLS)) * cps + (int64_t)s * 64];
                 if (s != cs) {
                     cs = s;
-                    const uint4 w0 = (QE_TB_ELIDE & 4) ? make_uint4(~0u, ~0u, 0u, 0u) : hw[((int64_t)k * gns + se) * 64];
+                    const uint4 w0 = hw[((int64_t)k * gns + s) * 64];
                     hinP = mk64(w0.x, w0.y); hinM = mk64(w0.z, w0.w);
                 }
                 P = mk64(c0.x, c0.y); M = mk64(c0.z, c0.w);
@@ -3091,12 +3083,6 @@ __global__ __launch_bounds__(256) void k_traceback_sys(TraceArgs A) {
     u32 steps = 0;
     int nmatch = 0;
     constexpr int TW = QE_CP_COLS;
-#ifdef QE_TBS_PROF      // tools/tbs_prof.sh: where a round's cycles go (s_memtime at the phase boundaries, printed by the first lane)
-    long long pf_t = __builtin_readcyclecounter(), pf_load = 0, pf_comp = 0, pf_walk = 0, pf_bcast = 0; int pf_rounds = 0, pf_iters = 0;
-#define PF_MARK(acc) do { const long long n__ = __builtin_readcyclecounter(); acc += n__ - pf_t; pf_t = n__; } while (0)
-#else
-#define PF_MARK(acc) do { } while (0)
-#endif
     // every load of a tile in one go: the checkpoint and the carry words are fetched for the slot clamped into the group's
     // range before the band-edge records say whether the slot was computed (one memory latency, not two); planes as raw words
     auto tbs_fetch = [&](int q, int Rb) {
@@ -3150,10 +3136,6 @@ __global__ __launch_bounds__(256) void k_traceback_sys(TraceArgs A) {
                 P = mk64(c0.x, c0.y); M = mk64(c0.z, c0.w);
             }
         }
-#ifdef QE_TBS_PROF
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PF_MARK(pf_load); ++pf_rounds;
-#endif
         {   // TW block steps from the checkpoint: the fill's arithmetic, so its bits
             const int c_first = (TW * max(q, 0)) & 63;
             const u32 alo = lo32(pa), ahi = hi32(pa), blo = lo32(pb), bhi = hi32(pb);
@@ -3192,25 +3174,18 @@ __global__ __launch_bounds__(256) void k_traceback_sys(TraceArgs A) {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) X8[c] = ~0u;
             }
-            PF_MARK(pf_comp);
             walk_round_diag<TW, LG>(tP, tM, X8, P8, M8, live, act, x, Rb, d0 + TW * q - 64 * Rb, d0, TW * (h / TW) + TW - 1, inb_same, inb_7, j == 0,
                                 v, h, steps, nmatch, R);
-            PF_MARK(pf_walk);
             continue;
         }
         // the walk, tile by tile in path order
         bool first_phase = true;
-        PF_MARK(pf_comp);
         while (true) {
             const bool mine = act && live && v >= 0 && h >= 0 && (h / TW) == q && (v >> 6) == Rb;
             const u64 bal = __ballot(mine);
             const u32 grp = (u32)(bal >> gl) & ((1u << GL) - 1u);
             if (!__any(grp != 0)) break;
-            PF_MARK(pf_bcast);
             walk_tile_lean<TW>(tP, tM, tE, mine, inb_same, inb_7, Rb, v, h, steps, nmatch, R);
-#ifdef QE_TBS_PROF
-            PF_MARK(pf_walk); ++pf_iters;
-#endif
             if (grp != 0) {                                         // (uniform over the lanes of a group)
                 const int own = gl | (__ffs((int)grp) - 1);
                 v = __shfl(v, own); h = __shfl(h, own); steps = (u32)__shfl((int)steps, own); nmatch = __shfl(nmatch, own);
@@ -3219,11 +3194,7 @@ __global__ __launch_bounds__(256) void k_traceback_sys(TraceArgs A) {
             first_phase = false;
         }
         (void)first_phase;
-        PF_MARK(pf_bcast);
     }
-#ifdef QE_TBS_PROF
-    if (wv == 0 && lane == 0) printf("k_traceback_sys<%d>: %d rounds, %d tile walks; cycles: loads %lld, recompute %lld, walks %lld, hand-over %lld\n", LG, pf_rounds, pf_iters, pf_load, pf_comp, pf_walk, pf_bcast);
-#endif
     if (!ok || j != 0) return;
     R.nops = (int)steps; R.edits = (int)steps - nmatch;
     R.push_n(OP_I, h + 1);

@@ -80,26 +80,48 @@ inline const Chip& chip(int device) {
 
 // ---------------------------------------------------------------------------
 // The library's switches.  Every QE_* environment variable it knows is read ONCE, the first time any of them is asked
-// for, into one immutable table; the launch path only ever looks names up in that table (no getenv per stage call,
+// for, into one immutable table; the launch path only ever indexes that table by its Sw (no getenv per stage call,
 // nothing that races an embedding application's setenv).  Production needs none of them: they force kernel forms for the
-// parity tests, lower thresholds so that small inputs reach deep paths, and switch traces on.  A name that is not in
-// the list is a programming error.  quicked_debug_reload_env() (tests: the in-process suites change switches between
-// runs) parses the environment again; it must not run concurrently with other calls into the library.
+// parity tests, lower thresholds so that small inputs reach deep paths, and switch traces on.  Every switch has one row
+// below, in the order of Sw: its variable and the value it has when unset.  quicked_debug_reload_env() (qe_capi.cpp; the
+// in-process test suites change switches between runs) parses the environment again.
 // ---------------------------------------------------------------------------
+enum class Sw : int {
+    QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
+    CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
+    TraceSys, Trace, TracePool, OomWaitMs, Count
+};
+struct SwitchDef { Sw sw; const char* name; long long dflt; };
+inline constexpr SwitchDef switch_defs[] = {
+    {Sw::QuickedFast, "QE_QUICKED_FAST", 1},           {Sw::QuickedEst, "QE_QUICKED_EST", 0},
+    {Sw::QuickedScorePass, "QE_QUICKED_SCORE_PASS", -1},     // -1: where it pays (quicked_score_pass_fits), 0: never, 1: wherever allowed
+    {Sw::FinishMerge, "QE_FINISH_MERGE", 4},           {Sw::FinishMergePairs, "QE_FINISH_MERGE_PAIRS", 8192},
+    {Sw::Finishers, "QE_FINISHERS", 3},                {Sw::LaneRel, "QE_LANE_REL", 1},
+    {Sw::CoopG, "QE_COOP_G", 1},                       {Sw::CoopFillG, "QE_COOP_FILL_G", 1},     // present = forced (0 / 1: G = 1)
+    {Sw::CoopLds, "QE_COOP_LDS", 1},                   {Sw::CoopTallFill, "QE_COOP_TALL_FILL", 1},
+    {Sw::Wave, "QE_WAVE", -1},                         {Sw::ScoreSys, "QE_SCORE_SYS", -1},
+    {Sw::Stage3Device, "QE_STAGE3_DEVICE", -1},        {Sw::FormatWave, "QE_FORMAT_WAVE", -1},
+    {Sw::WindowedCp, "QE_WINDOWED_CP", 1},             {Sw::WindowedQuad, "QE_WINDOWED_QUAD", -1},
+    {Sw::WindowedSys, "QE_WINDOWED_SYS", -1},          {Sw::SplitBytes, "QE_SPLIT_BYTES", 1LL << 24},
+    {Sw::FillSys, "QE_FILL_SYS", -1},                  {Sw::FillMulti, "QE_FILL_MULTI", 1},
+    {Sw::TraceSys, "QE_TRACE_SYS", -1},                {Sw::Trace, "QE_TRACE", 0},
+    {Sw::TracePool, "QE_TRACE_POOL", 0},               {Sw::OomWaitMs, "QE_OOM_WAIT_MS", 10000},
+};
+inline constexpr int switch_count = (int)Sw::Count;
+constexpr bool switch_rows_in_order() {
+    for (int i = 0; i < switch_count; ++i) if ((int)switch_defs[i].sw != i) return false;
+    return true;
+}
+static_assert(sizeof(switch_defs) / sizeof(switch_defs[0]) == (size_t)switch_count && switch_rows_in_order(), "one row per switch, in the order of Sw");
+
 struct SwitchTable {
-    static constexpr int N = 29;
-    static constexpr const char* names[N] = {
-        "QE_QUICKED_FAST", "QE_QUICKED_EST", "QE_FINISH_MERGE", "QE_FINISH_MERGE_PAIRS", "QE_FINISHERS", "QE_WAVE_PRIO", "QE_LANE_REL",
-        "QE_COOP_G", "QE_COOP_FILL_G", "QE_COOP_LDS", "QE_WAVE", "QE_SCORE_SYS", "QE_STAGE3_DEVICE", "QE_FORMAT_WAVE", "QE_WINDOWED_CP",
-        "QE_WINDOWED_QUAD", "QE_WINDOWED_SYS", "QE_SPLIT_BYTES", "QE_FILL_SYS", "QE_COOP_TALL_FILL", "QE_FILL_MULTI", "QE_TRACE_SYS",
-        "QE_TRACE", "QE_TRACE_POOL", "QE_OOM_WAIT_MS", "QE_SCORE_WAVES", "QE_QUICKED_SCORE_PASS", "QE_QUICKED_SCORE_PASS_FAST", "QE_SCORE_PASS_COOP_G"};
-    bool set[N];
-    long long value[N];
+    bool set[switch_count];
+    long long value[switch_count];           // the variable's value, or the row's default where it is not set
     SwitchTable() {
-        for (int i = 0; i < N; ++i) {
-            const char* e = getenv(names[i]);
+        for (int i = 0; i < switch_count; ++i) {
+            const char* e = getenv(switch_defs[i].name);
             set[i] = e != nullptr;
-            value[i] = e ? strtoll(e, nullptr, 10) : 0;
+            value[i] = e ? strtoll(e, nullptr, 10) : switch_defs[i].dflt;
         }
     }
 };
@@ -113,16 +135,13 @@ inline const SwitchTable& switches() {
     }
     return *t;
 }
-inline void switches_reload() { g_switches.store(new SwitchTable(), std::memory_order_release); }     // the old table stays (a reader may hold it): a few hundred bytes per reload, tests only
-inline int switch_index(const char* name) {
-    for (int i = 0; i < SwitchTable::N; ++i) if (strcmp(SwitchTable::names[i], name) == 0) return i;
-    fprintf(stderr, "[quicked_hip] internal error: unknown switch %s\n", name);
-    abort();
-}
-inline bool env_set(const char* name) { return switches().set[switch_index(name)]; }
-inline long long env_ll(const char* name, long long dflt) { const SwitchTable& t = switches(); const int i = switch_index(name); return t.set[i] ? t.value[i] : dflt; }
-inline int env_int(const char* name, int dflt) { return (int)env_ll(name, dflt); }
-inline bool pool_trace() { return env_set("QE_TRACE_POOL"); }
+// The table it replaces is leaked on purpose: any thread in the library -- the early-finish threads included -- may still
+// hold a reference to it.  A few hundred bytes per reload, and only the test suites reload.
+inline void switches_reload() { g_switches.store(new SwitchTable(), std::memory_order_release); }
+inline bool sw_set(Sw s) { return switches().set[(int)s]; }
+inline long long sw_ll(Sw s) { return switches().value[(int)s]; }
+inline int sw(Sw s) { return (int)sw_ll(s); }
+inline bool pool_trace() { return sw_set(Sw::TracePool); }
 inline double mono_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
 // ---------------------------------------------------------------------------
@@ -156,7 +175,7 @@ inline void device_malloc(void** p, size_t bytes, int device, DevicePool* keep, 
         // other threads are in the middle of runs: ask them to shrink, and take what comes free
         (void)hipGetLastError();
         ++bk.pressure;
-        const int wait_ms = env_int("QE_OOM_WAIT_MS", 10000);
+        const int wait_ms = sw(Sw::OomWaitMs);
         const double t_end = mono_ms() + wait_ms;
         if (pool_trace()) fprintf(stderr, "[qe-pool] out of memory for %.2f GB: waiting up to %d ms for other threads\n", bytes / 1e9, wait_ms);
         while (e == hipErrorOutOfMemory && mono_ms() < t_end) {

@@ -18,9 +18,8 @@ namespace qe {
 // slots the first one left empty, at no cost to either.
 // ---------------------------------------------------------------------------
 // The cooperative forms are launches of few waves, each a serial chain; next to a chip-filling launch of another run a lone
-// wave gets a third of its SIMD's issue slots.  s_setprio 3 in those kernels (QE_WAVE_PRIO=0: off) puts them first in line.
-static int wave_prio() { return env_int("QE_WAVE_PRIO", 1); }
-template <class Args> static Args with_prio(Args a) { a.prio = wave_prio(); return a; }
+// wave gets a third of its SIMD's issue slots.  s_setprio 3 in those kernels puts them first in line.
+template <class Args> static Args with_prio(Args a) { a.prio = 1; return a; }
 
 template <typename Kernel, typename Args>
 static void launch_groups(Context& C, Kernel kernel, const Args& args, size_t ngroups, int max_waves, size_t lds_per_wave, bool chain = false,
@@ -166,8 +165,9 @@ static BandLayout band_layout(const TaskList& L, bool fill, bool want_runs, bool
     return B;
 }
 
-struct DevLayout {
-    uint8_t* ws; int64_t *ws_off, *mat_off, *runs_off; int32_t *nslots, *nrows, *nch, *runs_cap; uint4* mat; u32* runs;
+struct DevLayout {                  // all null: a launch without a group workspace
+    uint8_t* ws = nullptr; int64_t *ws_off = nullptr, *mat_off = nullptr, *runs_off = nullptr;
+    int32_t *nslots = nullptr, *nrows = nullptr, *nch = nullptr, *runs_cap = nullptr; uint4* mat = nullptr; u32* runs = nullptr;
 };
 static DevLayout upload_layout(const BandLayout& B, Context& C) {
     DevLayout d;
@@ -209,6 +209,14 @@ static TaskOut take_out(Context& C, size_t nt) {
     return o;
 }
 
+// The cutoffs are still being computed on the device (QuickEd's fast flow): the list's are the estimates the buffers are
+// sized for; k_apply_cutoffs puts the real ones in and takes the tasks out that the host finishes afterwards.  `cleared`, an
+// output per task, reads -1 for those.
+static void apply_device_cutoffs(Context& C, const DevTasks& T, size_t nt, int32_t* cleared, const int32_t* d_cut, const int32_t* d_skip) {
+    HIP_CHECK(hipMemsetAsync(cleared, 0xFF, nt * sizeof(int32_t), C.stream));
+    hipLaunchKernelGGL(k_apply_cutoffs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, C.stream, (int)nt, T.cutoff, T.pair, d_cut, d_skip);
+}
+
 // ---------------------------------------------------------------------------
 // Stage runners.  Each returns with its kernels enqueued on C.stream.
 // ---------------------------------------------------------------------------
@@ -241,8 +249,18 @@ static BandState band_state(const ScoreLaunch& S) {
     return b;
 }
 
-// d_cut / d_skip: the cutoffs are still being computed on the device (QuickEd's fast flow): the list's are the estimates the
-// buffers are sized for; k_apply_cutoffs puts the real ones in and takes the tasks out that the host finishes afterwards
+// What every BandEd score-only launch passes alike: the pairs, the list, its group workspace (null where it has none) and the
+// outputs (O.len doubles as maxrow).  Every other field keeps BandedArgs' default (fill_multi = lane_rel = 1) or is 0 / null.
+static BandedArgs score_args(const quicked_batch& B, const ScoreLaunch& S, bool reversed) {
+    BandedArgs a{};
+    a.P = pair_view(B, reversed); a.T = S.T.v;
+    a.ws = S.D.ws; a.g_ws_off = S.D.ws_off; a.g_nslots = S.D.nslots; a.g_nrows = S.D.nrows; a.g_nch = S.D.nch;
+    a.g_mat_off = S.D.mat_off;
+    a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv; a.o_maxrow = S.O.len;
+    return a;
+}
+
+// d_cut / d_skip: the cutoffs are still on the device (apply_device_cutoffs)
 static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, bool fill_geom = false,
                                        const int32_t* d_cut = nullptr, const int32_t* d_skip = nullptr) {
     ScoreLaunch S;
@@ -252,23 +270,13 @@ static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskL
     S.T = upload_tasks(L, C);
     S.D = upload_layout(lay, C);
     S.O = take_out(C, S.nt);
-    if (d_cut) {
-        HIP_CHECK(hipMemsetAsync(S.O.score, 0xFF, S.nt * sizeof(int32_t), C.stream));      // a task taken out of the list has no score (-1)
-        hipLaunchKernelGGL(k_apply_cutoffs, dim3((unsigned)((S.nt + 255) / 256)), dim3(256), 0, C.stream, (int)S.nt, S.T.cutoff, S.T.pair, d_cut, d_skip);
-    }
-    BandedArgs a;
-    a.P = pair_view(B, reversed); a.T = S.T.v;
-    a.ws = S.D.ws; a.g_ws_off = S.D.ws_off; a.g_nslots = S.D.nslots; a.g_nrows = S.D.nrows; a.g_nch = S.D.nch;
-    a.mat = nullptr; a.g_mat_off = S.D.mat_off;
-    a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv;
-    a.o_maxrow = S.O.len;
-    a.only_if = nullptr;
-    a.lane_rel = env_int("QE_LANE_REL", 1);
+    if (d_cut) apply_device_cutoffs(C, S.T, S.nt, S.O.score, d_cut, d_skip);      // a task taken out of the list has no score (-1)
+    BandedArgs a = score_args(B, S, reversed);
+    a.lane_rel = sw(Sw::LaneRel);
     a.fill_geom = fill_geom ? 1 : 0;
     auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
-    // QE_SCORE_WAVES = 3: a 52 KB pin, three workgroups per CU = three waves per SIMD (the kernel's 158 VGPRs allow it)
-    launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0, false, env_int("QE_SCORE_WAVES", 2) == 3 ? (size_t)52 * 1024 : 0);
+    launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     return S;
 }
@@ -276,8 +284,8 @@ static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskL
 // lanes per alignment for the cooperative score-only kernel: enough waves to fill the chip
 // (>= ~4 per SIMD) while every lane keeps >= 2 band slots; QE_COOP_G overrides (0 / 1 = off)
 static int coop_lanes(const TaskList& L, int in_flight = 1, bool fill = false) {
-    const char* const e_name = fill ? "QE_COOP_FILL_G" : "QE_COOP_G";
-    const bool e = env_set(e_name);
+    const Sw force = fill ? Sw::CoopFillG : Sw::CoopG;
+    const bool e = sw_set(force);
     int min_nsl = 1 << 30, n_max = 1;
     size_t live = 0;
     for (size_t t = 0; t < L.pair.size(); ++t) {
@@ -294,10 +302,9 @@ static int coop_lanes(const TaskList& L, int in_flight = 1, bool fill = false) {
     // latency grows with their length (100 kb half passes: 526 -> 430 ms from G = 8 to 32)
     const Chip& chp = chip(tl_device);
     const size_t target = std::min<size_t>(2 * chp.slots2(), chp.frac2(0.34) * (size_t)std::max(1, n_max / 10000));      // ~700 waves of 2 048 slots per 10 kb of read
-    if (e) G = env_int(e_name, 1);
+    if (e) G = sw(force);
     else
         while (G < 64 && ((live * G) / 64) * (size_t)std::max(1, in_flight) < target) G *= 2;      // runs in flight fill the chip together
-    // the band-height test first + 2 < last must stay decidable G-2 chunks early: keep the band >= 3 G + 4 slots
     // the band-height test first + 2 < last must stay decidable G - 2 chunks early: a band of >= 3 G + 4 slots always is;
     // with 2 G + 4 a task whose band comes within G slots of its minimum height is flagged and recomputed by the one-lane
     // kernel -- rare, and worth it where the launch is short of waves anyway (4 000 pairs of 10 kb: 4.2 -> 2.8 ms with G = 8)
@@ -307,16 +314,14 @@ static int coop_lanes(const TaskList& L, int in_flight = 1, bool fill = false) {
     return G < 2 ? 1 : G;
 }
 
-// k_banded_coop over the list, then k_banded<false> over the tasks it flagged
 // the band state of a wave's 64 / G tasks in LDS (k_banded_coop_lds): bytes per wave for bands of ns slots
 static size_t coop_lds_bytes(int ns, int G) {
     const int NA = 64 / G, rr = ns + G + 4, cr = std::max(16, 4 * G);
     const size_t bytes = (size_t)2 * (ns + 1) * NA * 8 + (size_t)2 * rr * NA * 4 + (size_t)2 * cr * NA * 2 + (size_t)2 * NA * 4;
     return (bytes + 63) & ~(size_t)63;
 }
-// fill_geom: score-only over the FILL's cells (BandedArgs::fill_geom) -- the LDS form only; d_cut / d_skip as launch_banded_score
-static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int G, int timed, bool fill_geom = false,
-                                      const int32_t* d_cut = nullptr, const int32_t* d_skip = nullptr) {
+// k_banded_coop(_lds) over the list, then k_banded<false> over the tasks it flagged
+static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int G, int timed) {
     ScoreLaunch S;
     S.nt = L.pair.size();
     const int NA = 64 / G;
@@ -331,7 +336,7 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
             const size_t t = w * NA + q;
             if (L.pair[t] < 0) continue;
             const HGeom Gm = host_geometry(L.m[t], L.n[t], L.cutoff[t]);
-            const int nsl = fill_geom ? Gm.ebb : Gm.ebb_local;
+            const int nsl = Gm.ebb_local;
             ns = std::max(ns, nsl);
             nr = std::max(nr, (L.m[t] + 63) / 64 + nsl + 4);
             nch = std::max(nch, L.n[t] / 64 + 3);
@@ -342,14 +347,8 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
         const size_t bytes = (size_t)2 * (ns + 1) * NA * 8 + (size_t)2 * nr * NA * 4 + (size_t)2 * nch * NA * 2 + (size_t)2 * NA * 4;
         ws_bytes += (bytes + 255) & ~(size_t)255;
     }
-    if (fill_geom && (env_int("QE_COOP_LDS", 1) == 0 || coop_lds_bytes(ns_max, G) > (size_t)38 * 1024))
-        return launch_banded_score(B, C, L, reversed, timed, true, d_cut, d_skip);      // no room on chip: one lane per task
     S.T = upload_tasks(L, C);
     S.O = take_out(C, S.nt);
-    if (d_cut) {
-        HIP_CHECK(hipMemsetAsync(S.O.score, 0xFF, S.nt * sizeof(int32_t), C.stream));
-        hipLaunchKernelGGL(k_apply_cutoffs, dim3((unsigned)((S.nt + 255) / 256)), dim3(256), 0, C.stream, (int)S.nt, S.T.cutoff, S.T.pair, d_cut, d_skip);
-    }
     uint8_t* ws = C.scratch_p->take<uint8_t>(ws_bytes + 256);
     int64_t* d_off = C.scratch_p->take<int64_t>(nwaves); int32_t* d_ns = C.scratch_p->take<int32_t>(nwaves);
     int32_t* d_nr = C.scratch_p->take<int32_t>(nwaves); int32_t* d_nch = C.scratch_p->take<int32_t>(nwaves);
@@ -360,7 +359,6 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
     a.ws = ws; a.w_ws_off = d_off; a.w_nslots = d_ns; a.w_nrows = d_nr; a.w_nch = d_nch;
     a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv;
     a.o_maxrow = S.O.len; a.o_abort = S.O.hew;
-    a.fill_geom = fill_geom ? 1 : 0;
     HIP_CHECK(hipMemsetAsync(S.O.hew, 0, S.nt * sizeof(int32_t), C.stream));
     auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
@@ -369,30 +367,21 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
     memset(&x, 0, sizeof(x));
     x.A = a;
     x.lgG = 0; while ((1 << x.lgG) < G) ++x.lgG;
-    x.ns = 3; for (int32_t v : w_ns) x.ns = std::max(x.ns, v);
+    x.ns = ns_max;
     x.rr = x.ns + G + 4;
     x.cr = std::max(16, 4 * G);
-    {
-        const size_t bytes = (size_t)2 * (x.ns + 1) * NA * 8 + (size_t)2 * x.rr * NA * 4 + (size_t)2 * x.cr * NA * 2 + (size_t)2 * NA * 4;
-        x.lds_per_wave = (int32_t)((bytes + 63) & ~(size_t)63);
-    }
-    const int lds_env = env_int("QE_COOP_LDS", 1);
-    if (lds_env != 0 && (size_t)x.lds_per_wave <= (size_t)38 * 1024)
+    x.lds_per_wave = (int32_t)coop_lds_bytes(x.ns, G);
+    if (sw(Sw::CoopLds) != 0 && (size_t)x.lds_per_wave <= (size_t)38 * 1024)
         launch_groups(C, k_banded_coop_lds<false>, x, (size_t)nwaves, 8, (size_t)x.lds_per_wave);
     else
         launch_groups(C, k_banded_coop, a, (size_t)nwaves, 8, 0);
     // fallback pass: one lane per task, only where a band-edge decision could not be resolved in time
-    BandLayout lay = band_layout(L, fill_geom, false);
+    BandLayout lay = band_layout(L, false, false);
     lay.mat_u4 = 0;
     S.D = upload_layout(lay, C);
-    BandedArgs b;
-    b.fill_geom = fill_geom ? 1 : 0;
-    b.P = a.P; b.T = S.T.v;
-    b.ws = S.D.ws; b.g_ws_off = S.D.ws_off; b.g_nslots = S.D.nslots; b.g_nrows = S.D.nrows; b.g_nch = S.D.nch;
-    b.mat = nullptr; b.g_mat_off = S.D.mat_off;
-    b.o_score = S.O.score; b.o_first = S.O.first; b.o_last = S.O.last; b.o_posv = S.O.posv; b.o_adv = S.O.adv;
-    b.o_maxrow = S.O.len; b.only_if = S.O.hew;
-    b.lane_rel = env_int("QE_LANE_REL", 1);
+    BandedArgs b = score_args(B, S, reversed);
+    b.only_if = S.O.hew;
+    b.lane_rel = sw(Sw::LaneRel);
     launch_groups(C, k_banded<false>, b, L.ngroups(), 8, 0);
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     return S;
@@ -453,7 +442,7 @@ struct PendingFetch {
 // passes (tfin == n: no stopped band to export) and a band that fits the wave.  QE_WAVE = 0 / 1 switches the form off /
 // forces it wherever it is eligible (tests).
 static bool wave_form_wanted(const TaskList& L) {
-    const int force = env_int("QE_WAVE", -1);
+    const int force = sw(Sw::Wave);
     if (force == 0) return false;
     size_t live = 0;
     int n_max = 0;
@@ -471,11 +460,8 @@ static ScoreLaunch launch_banded_wave(quicked_batch& B, Context& C, const TaskLi
     S.nt = L.pair.size();
     S.T = upload_tasks(L, C);
     S.O = take_out(C, S.nt);
-    BandedArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = pair_view(B, reversed); a.T = S.T.v;
-    a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv;
-    a.o_maxrow = S.O.len;
+    BandedArgs a = score_args(B, S, reversed);       // no group workspace
+    a.fill_multi = 0; a.lane_rel = 0;
     auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
     launch_groups(C, k_banded_wave, a, S.nt, 4, 0);                     // one wave per task
@@ -496,19 +482,11 @@ static ScoreLaunch launch_banded_sys(quicked_batch& B, Context& C, const TaskLis
     S.T = upload_tasks(L, C);
     S.D = upload_layout(lay, C);
     S.O = take_out(C, S.nt);
-    if (d_cut) {       // as launch_banded_score
-        HIP_CHECK(hipMemsetAsync(S.O.score, 0xFF, S.nt * sizeof(int32_t), C.stream));
-        hipLaunchKernelGGL(k_apply_cutoffs, dim3((unsigned)((S.nt + 255) / 256)), dim3(256), 0, C.stream, (int)S.nt, S.T.cutoff, S.T.pair, d_cut, d_skip);
-    }
-    BandedArgs a;
+    if (d_cut) apply_device_cutoffs(C, S.T, S.nt, S.O.score, d_cut, d_skip);
+    BandedArgs a = score_args(B, S, reversed);
     a.fill_geom = fill_geom ? 1 : 0;
-    a.P = pair_view(B, reversed); a.T = S.T.v;
-    a.ws = S.D.ws; a.g_ws_off = S.D.ws_off; a.g_nslots = S.D.nslots; a.g_nrows = S.D.nrows; a.g_nch = S.D.nch;
-    a.mat = nullptr; a.g_mat_off = S.D.mat_off;
-    a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv;
-    a.o_maxrow = S.O.len;
-    a.only_if = nullptr; a.o_abort = S.O.hew;
-    a.lane_rel = env_int("QE_LANE_REL", 1);
+    a.o_abort = S.O.hew;
+    a.lane_rel = sw(Sw::LaneRel);
     auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
     if (lg == 4) launch_groups(C, k_banded_sys<4, false>, with_prio(a), S.nt / 4, 4, 0, false, (size_t)40 * 1024);
@@ -522,7 +500,7 @@ static ScoreLaunch launch_banded_sys(quicked_batch& B, Context& C, const TaskLis
 // whole-text passes on few tasks (QuickEd's stage-3 doubling rounds on the pairs a run left, a BandEd score-only call on one
 // pair or a few hundred): 0 = no, else log2 of the lanes per task.  QE_SCORE_SYS = 0 / 1: never / wherever eligible (tests)
 static int sys_score_lanes(const TaskList& L, int in_flight, bool fill_geom = false) {
-    const int env = env_int("QE_SCORE_SYS", -1);
+    const int env = sw(Sw::ScoreSys);
     if (env == 0) return 0;
     size_t live = 0;
     int max_nsl = 0;
@@ -547,24 +525,22 @@ static int sys_score_lanes(const TaskList& L, int in_flight, bool fill_geom = fa
 // (too many tasks for a wave each).  QE_STAGE3_DEVICE = 0 / 1: never / whenever the list is not empty (tests)
 static bool stage3_on_device(quicked_batch& B, Context& C, const TaskList& L, std::vector<int32_t>& score, std::vector<u32>& adv,
                              std::vector<int32_t>& flagged, std::vector<int32_t>& cutoff) {
-    const int env = env_int("QE_STAGE3_DEVICE", -1);
+    const int env = sw(Sw::Stage3Device);
     if (env == 0) return false;
     size_t live = 0;
     for (int32_t pr : L.pair) live += pr >= 0;
     if (live == 0 || (env != 1 && L.pair.size() > chip(C.device).frac2(0.54))) return false;
     const size_t nt = L.pair.size();
-    const DevTasks T = upload_tasks(L, C);
-    const TaskOut O = take_out(C, nt);
+    ScoreLaunch S;                                   // no group workspace
+    S.nt = nt;
+    S.T = upload_tasks(L, C);
+    S.O = take_out(C, nt);
     int32_t* d_cut = C.scratch_p->take<int32_t>(nt);
-    HIP_CHECK(hipMemsetAsync(O.hew, 0, nt * sizeof(int32_t), C.stream));
-    BandedArgs a;
-    a.P = pair_view(B, false); a.T = T.v;
-    a.ws = nullptr; a.g_ws_off = nullptr; a.g_nslots = nullptr; a.g_nrows = nullptr; a.g_nch = nullptr;
-    a.mat = nullptr; a.g_mat_off = nullptr;
-    a.o_score = O.score; a.o_first = O.first; a.o_last = O.last; a.o_posv = O.posv; a.o_adv = O.adv; a.o_maxrow = O.len;
-    a.only_if = nullptr; a.o_abort = O.hew; a.doubling = 1; a.o_cutoff = d_cut;
+    HIP_CHECK(hipMemsetAsync(S.O.hew, 0, nt * sizeof(int32_t), C.stream));
+    BandedArgs a = score_args(B, S, false);
+    a.o_abort = S.O.hew; a.doubling = 1; a.o_cutoff = d_cut;
     launch_groups(C, k_banded_sys<6, false>, with_prio(a), nt, 4, 0, false, (size_t)40 * 1024);
-    d2h(score, O.score, nt, C.stream); d2h(adv, O.adv, nt, C.stream); d2h(flagged, O.hew, nt, C.stream); d2h(cutoff, d_cut, nt, C.stream);
+    d2h(score, S.O.score, nt, C.stream); d2h(adv, S.O.adv, nt, C.stream); d2h(flagged, S.O.hew, nt, C.stream); d2h(cutoff, d_cut, nt, C.stream);
     HIP_CHECK(hipStreamSynchronize(C.stream));
     return true;
 }
@@ -573,10 +549,10 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
                              bool fetch, int32_t** d_score_out, PendingFetch* pf = nullptr) {
     // one wavefront per alignment only where the cooperative on-chip form has no room (a band of fewer than 8 slots): with
     // G = 8 lanes per alignment and 4-slot passes that form does a 10 kb pair in 2.7 ms, the wave form in 4.3
-    const bool forced = env_set("QE_COOP_G") || env_int("QE_WAVE", -1) == 1;      // tests of the other forms
+    const bool forced = sw_set(Sw::CoopG) || sw(Sw::Wave) == 1;      // tests of the other forms
     const int lg = forced ? 0 : sys_score_lanes(L, fetch ? 1 : C.in_flight);
     const int G0 = lg ? 1 : coop_lanes(L, fetch ? 1 : C.in_flight);
-    const bool wave = !lg && wave_form_wanted(L) && (G0 < 2 || env_int("QE_WAVE", -1) == 1);
+    const bool wave = !lg && wave_form_wanted(L) && (G0 < 2 || sw(Sw::Wave) == 1);
     const int G = wave ? 1 : G0;
     const ScoreLaunch S = lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
                           wave ? launch_banded_wave(B, C, L, reversed, 1)
@@ -606,15 +582,14 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
 // 1 k pairs 0.44 / 1.5 M alignments/s, 4 k 2.9 / 4.8, 12.5 k 5.6 / 9.1, 25 k 6.3 / 10.4, 100 k 7.05 / 11.5 -- every size of such reads (taller bands: quicked_score_pass_fits).
 // In the fast flow the pass reads its cutoffs from the device like the align step does (k_apply_cutoffs); pairs with lower-case /
 // IUPAC symbols leave the flow there (Stage1Args::flags) and in the host-driven flow keep the whole batch on the align step.
-// QE_QUICKED_SCORE_PASS = 0: never (the align step: tests), 1: wherever the results allow it and no read splits; QE_QUICKED_SCORE_PASS_FAST = 0: synchronous runs take the pass at the
-// end of the host-driven flow only.
-static bool quicked_score_pass_wanted() { return env_int("QE_QUICKED_SCORE_PASS", 1) != 0; }
+// QE_QUICKED_SCORE_PASS = 0: never (the align step: tests), 1: wherever the results allow it and no read splits.
+static bool quicked_score_pass_wanted() { return sw(Sw::QuickedScorePass) != 0; }
 // ... and for THIS list (cutoffs: the bounds, or the fast flow's estimates): a run the caller waits for, of a few thousand
 // tasks whose bands are too tall for the systolic forms, is a handful of one-lane waves with one wave's chain each, and the
 // align step's cooperative fill is ahead there (2 000 pairs of 20 kb at 5 %: 11 ms against 15; of 10 kb at 10 %: 7.8 / 7.8;
 // from 8 000 pairs on the pass wins: 20 / 16 and 12.6 / 7.9 ms).  Queued runs fill the chip together: always.
 static bool quicked_score_pass_fits(const TaskList& L, bool fetch) {
-    if (env_int("QE_QUICKED_SCORE_PASS", -1) == 1 || !fetch) return true;
+    if (sw(Sw::QuickedScorePass) == 1 || !fetch) return true;
     if (sys_score_lanes(L, 1, true) != 0) return true;
     size_t live = 0;
     for (int32_t pr : L.pair) live += pr >= 0;
@@ -624,14 +599,12 @@ static bool quicked_score_pass_fits(const TaskList& L, bool fetch) {
 static void run_fill_score(quicked_batch& B, Context& C, const TaskList& L, StageResult* R, bool fetch, int32_t** d_score_out,
                            PendingFetch* pf = nullptr, const int32_t* d_cut = nullptr, const int32_t* d_skip = nullptr) {
     // launches of few waves: the systolic forms (16 lanes or a wave per task), as the score-only passes and the fills take them
-    // (the cooperative LDS form can run the pass too -- launch_banded_coop(.., fill_geom) -- but loses to the one-lane kernel
-    // wherever it was tried: 2 000 / 8 000 / 30 000 pairs of 20 kb alone 21 / 21 / 30 ms against 15 / 16 / 21, its bands of ~20
-    // slots leave G = 8 lanes 2 G + 4 slots and most tasks to the fallback pass: profiles/r06_y_probe_coop_form.txt)
+    // (a cooperative LDS form of the pass was tried in round 6 and lost to the one-lane kernel everywhere: 2 000 / 8 000 / 30 000
+    // pairs of 20 kb alone 21 / 21 / 30 ms against 15 / 16 / 21, its bands of ~20 slots leave G = 8 lanes 2 G + 4 slots and
+    // most tasks to the fallback pass: profiles/r06_y_probe_coop_form.txt)
     const int lg = sys_score_lanes(L, fetch ? 1 : C.in_flight, true);
-    const int Gc = lg ? 0 : env_int("QE_SCORE_PASS_COOP_G", 0);       // tests / probes: that many lanes per task in the cooperative LDS form
-    const ScoreLaunch S = lg ? launch_banded_sys(B, C, L, false, lg, 2 /* timed as a fill */, true, d_cut, d_skip) :
-                          Gc >= 2 ? launch_banded_coop(B, C, L, false, Gc, 2, true, d_cut, d_skip)
-                                  : launch_banded_score(B, C, L, false, 2, true, d_cut, d_skip);
+    const ScoreLaunch S = lg ? launch_banded_sys(B, C, L, false, lg, 2 /* timed as a fill */, true, d_cut, d_skip)
+                             : launch_banded_score(B, C, L, false, 2, true, d_cut, d_skip);
     if (d_score_out) *d_score_out = S.O.score;
     if (pf && !fetch) {
         pf->kind = 1; pf->task_pair = L.pair; pf->d_score = S.O.score; pf->d_adv = S.O.adv; pf->counter_slot = 1;
@@ -653,7 +626,7 @@ static bool wave_formatter_wanted(const quicked_batch& B, const SegList& SL, boo
     const size_t nr = SL.root_pair.size(), nseg = SL.kind.size();
     size_t pool_bytes = 0;
     if (want_strings) for (size_t b : SL.bound) pool_bytes += b;
-    const int wave_env = env_int("QE_FORMAT_WAVE", -1);      // tests force either form
+    const int wave_env = sw(Sw::FormatWave);      // tests force either form
     return B.cigar_style != 2 && nr > 0 && (wave_env >= 0 ? wave_env != 0 : (nseg > 0 && pool_bytes / nr >= 512));
 }
 
@@ -795,12 +768,12 @@ static void run_windowed(quicked_batch& B, Context& C, const TaskList& L, bool r
     a.ws = D.ws; a.g_ws_off = D.ws_off; a.runs = D.runs; a.g_runs_off = D.runs_off; a.g_runs_cap = D.runs_cap;
     a.o_score = O.score; a.o_hew = O.hew; a.o_nruns = O.nruns; a.o_nops = O.nops; a.o_edits = O.edits; a.o_steps = O.steps;
     // (2, 1) windows stay on chip (k_windowed); every other shape runs the checkpointed general path
-    a.cp_path = env_int("QE_WINDOWED_CP", 1);
+    a.cp_path = sw(Sw::WindowedCp);
     if (W == 2 && O_ == 1) {
         // few waves: four lanes per alignment run the chain of full windows first (k_windowed_quad, a third of the one-lane
         // chain's latency for 1.9 x its instructions), the one-lane kernel then only has every task's clamped last windows
         // left.  Worth it while the launches in flight leave SIMDs idle; QE_WINDOWED_QUAD = 0 / 1: never / always (tests)
-        const int quad = env_int("QE_WINDOWED_QUAD", -1);
+        const int quad = sw(Sw::WindowedQuad);
         const size_t waves = (size_t)ng * 4 * (size_t)std::max(1, fetch ? 1 : C.in_flight);
         if (score_only && (quad == 1 || (quad != 0 && waves <= chip(C.device).slots2()))) {
             a.state = C.scratch_p->take<int32_t>(5 * nt);
@@ -811,7 +784,7 @@ static void run_windowed(quicked_batch& B, Context& C, const TaskList& L, bool r
         // few waves: sixteen lanes per alignment (k_windowed_sys: the window's block rows as a systolic array, sixteen traceback
         // tiles rebuilt at a time); what it flags (N, non-canonical symbols) stays with the one-lane kernel.
         // QE_WINDOWED_SYS = 0 / 1: never / wherever eligible (tests)
-        const int wsys = env_int("QE_WINDOWED_SYS", -1);
+        const int wsys = sw(Sw::WindowedSys);
         const size_t waves = (size_t)ng * 16 * (size_t)std::max(1, fetch ? 1 : C.in_flight);
         // not for W == 2 with the x86 SSE semantics (bpm_windowed.c:577: the SSE window kernel runs whenever window_size == 2
         // and force_scalar is off, whatever the overlap): k_windowed_sys computes the scalar kernel's windows, the one-lane
@@ -859,7 +832,7 @@ static void run_windowed(quicked_batch& B, Context& C, const TaskList& L, bool r
 // ---------------------------------------------------------------------------
 // BUFFER_SIZE_16M of bpm_hirschberg.c:65; QE_SPLIT_BYTES lowers it so tests can force many split levels on small inputs
 static uint64_t split_threshold() {
-    return (uint64_t)env_ll("QE_SPLIT_BYTES", (long long)1 << 24);
+    return (uint64_t)sw_ll(Sw::SplitBytes);
 }
 static void reset_host_results(quicked_batch& B) {
     B.wr->score.assign((size_t)B.n, -1);
@@ -1046,8 +1019,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
         // estimates in roots.cutoff; no root may have split or vanished, so leaf k is root k
         if (n_leaves != root_node.size() || nodes.size() != root_node.size())
             throw HipError{hipErrorInvalidValue, "device-side cutoffs need one leaf per root", __LINE__};
-        HIP_CHECK(hipMemsetAsync(O.nruns, 0xFF, nt * sizeof(int32_t), C.stream));      // a task taken out of the list has no runs (-1)
-        hipLaunchKernelGGL(k_apply_cutoffs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, C.stream, (int)nt, T.cutoff, T.pair, d_cut, d_skip);
+        apply_device_cutoffs(C, T, nt, O.nruns, d_cut, d_skip);      // a task taken out of the list has no runs (-1)
     }
     int64_t* d_ws_off = C.scratch_p->take<int64_t>(ng + 1); int64_t* d_mat_off = C.scratch_p->take<int64_t>(ng + 1);
     int64_t* d_runs_off = C.scratch_p->take<int64_t>(ng + 1);
@@ -1066,8 +1038,8 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
     // (first + 2 < last) cannot be decided chunks ahead, and the cooperative protocol hands most leaves back to the
     // one-lane kernel (config 4's leaves: both kernels ran, 45 + 36 ms instead of 38).  A user bandwidth leaves the band
     // tall: few long BandEd alignments with CIGAR fill with G lanes each.  QE_COOP_FILL_G forces a width (tests).
-    const bool fill_forced = env_set("QE_COOP_FILL_G");
-    int Gfill = (env_int("QE_COOP_LDS", 1) == 0 || (tight_runs && !fill_forced)) ? 1 : coop_lanes(LL, fetch ? 1 : C.in_flight, true);
+    const bool fill_forced = sw_set(Sw::CoopFillG);
+    int Gfill = (sw(Sw::CoopLds) == 0 || (tight_runs && !fill_forced)) ? 1 : coop_lanes(LL, fetch ? 1 : C.in_flight, true);
     // Round 4: ... except where the bound is LARGE.  A pair with large indels has a bound of thousands, its band is 40-60
     // slots tall for most of its length (the edge pruning only bites as the score nears the cutoff), and a launch of such
     // leaves is a few waves of one lane's chain each (the pairs a QuickEd run left for the host-driven flow: 25-35 ms for
@@ -1079,12 +1051,12 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
     // tight bounds in a launch of few waves: the systolic fill (k_banded_sys, below) -- 16 lanes per leaf for bands of <= 15
     // slots, a wave per leaf for bands of <= 63 (the bounds of pairs with large indels), the one-lane kernel for what is left.
     // QE_FILL_SYS = 0 / 1: never / wherever the bound is tight (tests)
-    const int sys_env = env_int("QE_FILL_SYS", -1);
+    const int sys_env = sw(Sw::FillSys);
     const size_t in_fl = (size_t)std::max(1, fetch ? 1 : C.in_flight);
     const Chip& chp = chip(C.device);
     const bool sys_fill = Gfill < 2 && tight_runs && (sys_env == 1 || (sys_env != 0 && (size_t)ng * 16 * in_fl <= 2 * chp.slots2()));
     std::vector<int32_t> hew_init;
-    if (!sys_fill && Gfill < 2 && tight_runs && !fill_forced && !d_cut && env_int("QE_COOP_LDS", 1) != 0 && env_int("QE_COOP_TALL_FILL", 1) != 0 &&
+    if (!sys_fill && Gfill < 2 && tight_runs && !fill_forced && !d_cut && sw(Sw::CoopLds) != 0 && sw(Sw::CoopTallFill) != 0 &&
         (size_t)ng * (size_t)std::max(1, fetch ? 1 : C.in_flight) <= 64) {
         size_t live = 0;
         std::vector<int> ebb(nt, 0);
@@ -1140,8 +1112,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
             x.ns = 3; for (int g = g0; g < g1; ++g) x.ns = std::max(x.ns, lay.nslots[g]);
             x.rr = x.ns + Gfill + 4;
             x.cr = std::max(16, 4 * Gfill);
-            const size_t bytes = (size_t)2 * (x.ns + 1) * NAf * 8 + (size_t)2 * x.rr * NAf * 4 + (size_t)2 * x.cr * NAf * 2 + (size_t)2 * NAf * 4;
-            x.lds_per_wave = (int32_t)((bytes + 63) & ~(size_t)63);
+            x.lds_per_wave = (int32_t)coop_lds_bytes(x.ns, Gfill);
             x.mat = mat; x.g_mat_off = a.g_mat_off; x.gws = ws; x.g_ws_off = a.g_ws_off;
             x.g_nslots = a.g_nslots; x.g_nrows = a.g_nrows; x.g_nch = a.g_nch;
             if ((size_t)x.lds_per_wave <= (size_t)38 * 1024) {
@@ -1167,8 +1138,8 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
                 if (maxns > 63) launch_groups(C, k_banded_sys2<true>, with_prio(a), (size_t)(g1 - g0) * 64, 4, 0, false, sys_pin);
             }
         }
-        a.fill_multi = env_int("QE_FILL_MULTI", 1);
-        a.lane_rel = env_int("QE_LANE_REL", 1);
+        a.fill_multi = sw(Sw::FillMulti);
+        a.lane_rel = sw(Sw::LaneRel);
         launch_groups(C, k_banded<true>, a, (size_t)(g1 - g0), 8, 0);     // everything, or what the cooperative fill flagged
         if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
         TraceArgs tr;
@@ -1184,7 +1155,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
         // lanes per leaf: 16 while the launch is one round of waves (two per SIMD at 246 VGPRs: ~8 k leaves), 8 up to ~3 300
         // waves (the walk runs in all lanes of a group at once in both: one batch of 12.5 k leaves alone 8.1 ms with 8 lanes,
         // 8.6 with 16, 10.3 with the tile-by-tile walk of the round's first half), 4 up to ~1 700 waves
-        const int tsys = env_int("QE_TRACE_SYS", -1);
+        const int tsys = sw(Sw::TraceSys);
         const size_t gw = (size_t)(g1 - g0) * (size_t)std::max(1, fetch ? 1 : C.in_flight);      // one-lane waves in flight
         int tlg = 0;
         if (tsys > 1) tlg = tsys == 4 ? 2 : (tsys == 8 ? 3 : 4);
