@@ -105,6 +105,21 @@ quicked_status_t quicked_batch_reload_packed(quicked_batch_t* batch, int64_t n, 
  * pool and bit-planes -- three for batches that fill the chip, up to twelve for small ones (quicked_pool_stats()[2]) --
  * so the kernels of the next runs overlap those of run k. */
 quicked_status_t quicked_batch_run(quicked_batch_t* batch, const quicked_params_t* params, int sync);
+/* Bounded distances: "is pair i within k edits, and if so, how many?".  Pair i's bound is max_dist[i] (n values, read during
+ * the call) or, where max_dist is NULL, max_dist_all.  Result of pair i: its edit distance d if d <= bound, else "beyond":
+ * score -1 with the status QUICKED_OK -- an answer, not an error -- and no CIGAR.  The distance is the library's own (what
+ * algo = QUICKED computes: case folded, every non-ACGT byte one symbol, dna_text.c:41-46).  only_score == 0: a CIGAR with
+ * exactly d edits for every pair within its bound (cigar_off -1 for the others), in the style and with the validator of
+ * quicked_batch_configure; such a run needs sync != 0 (sync == 0: QUICKED_UNIMPLEMENTED, nothing is queued).  only_score != 0
+ * with sync == 0 queues the run like quicked_batch_run does; quicked_batch_fetch brings its results.  Results through the
+ * getters below.  Empty sequences keep QUICKED_EMPTY_SEQUENCE; a NULL batch or a negative bound: QUICKED_ERROR, nothing is
+ * launched.  ASCII and packed batches alike.  A pair whose bound (at most max(pattern, text) counts) is <= 63 can be
+ * decided by a kernel that keeps the pair's whole band in one 64-bit word: the library picks it for pairs of 2000 bases and more,
+ * QE_BOUNDED_DIAG=1 wherever it applies, QE_BOUNDED_DIAG=0 never; the others, and the CIGARs, go through the BandEd
+ * kernels with the bound as the cutoff.  Pairs with lower-case / IUPAC bytes get their distance from the QUICKED flow
+ * itself (its alignment's edit count), on the host's schedule: when a sync != 0 run ends, or in the fetch. */
+quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const int32_t* max_dist, int32_t max_dist_all,
+                                           int only_score, int sync);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read
@@ -184,7 +199,8 @@ quicked_status_t quicked_pool_trim(void);
  * launches that was; synchronises the batch's stream. */
 quicked_status_t quicked_batch_kernel_time(quicked_batch_t* batch, double* ms_sum, int64_t* launches);
 /* The same by kind of launch: [0] score-only BandEd passes (a BANDED run, QuickEd's stage 3), [1] fills, [2] the half passes of
- * Hirschberg's split levels (bpm_hirschberg.c:85-100; the dominant launches of long reads), [3] unused. */
+ * Hirschberg's split levels (bpm_hirschberg.c:85-100; the dominant launches of long reads), [3] diagonal-word launches of bounded
+ * runs (quicked_batch_run_bounded; 0 in every other run). */
 quicked_status_t quicked_batch_kernel_times(quicked_batch_t* batch, double ms_sum[4], int64_t launches[4]);
 
 #ifdef __cplusplus

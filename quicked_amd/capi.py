@@ -58,7 +58,8 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_configure", "quicked_batch_check_results", "quicked_batch_validate",
            "quicked_wire_words", "quicked_wire_pack", "quicked_batch_create_packed",
            "quicked_batch_reload", "quicked_batch_reload_packed", "quicked_batch_fetch", "quicked_pool_stats", "quicked_batch_cigar_view",
-           "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats"]
+           "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats",
+           "quicked_batch_run_bounded"]
 
 _LIB = None
 
@@ -98,6 +99,8 @@ def lib():
     L.quicked_batch_destroy.argtypes = [C.c_void_p]
     L.quicked_batch_destroy.restype = None
     L.quicked_batch_run.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int]
+    L.quicked_batch_run_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int]
+    L.quicked_batch_run_bounded.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -312,6 +315,16 @@ class ResidentBatch:
     def run(self, params, sync=True):
         return self._lib.quicked_batch_run(self._h, C.byref(params), 1 if sync else 0)
 
+    def run_bounded(self, max_dist, only_score=True, sync=True):
+        """quicked_batch_run_bounded: per pair "the distance if it is <= its bound, else -1".  max_dist: one int for every
+        pair, or an array of n bounds.  only_score=False (sync only): a CIGAR for every pair within its bound."""
+        if np.ndim(max_dist) == 0:
+            return self._lib.quicked_batch_run_bounded(self._h, None, int(max_dist), 1 if only_score else 0, 1 if sync else 0)
+        md = np.ascontiguousarray(max_dist, dtype=np.int32)
+        if md.shape != (self.n,):
+            raise ValueError("max_dist: one bound per pair")
+        return self._lib.quicked_batch_run_bounded(self._h, md.ctypes.data, 0, 1 if only_score else 0, 1 if sync else 0)
+
     def sync(self):
         return self._lib.quicked_batch_sync(self._h)
 
@@ -406,7 +419,8 @@ class ResidentBatch:
         return ms.value, n.value
 
     def kernel_times(self):
-        """-> (ms[4], launches[4]) by kind since the last call: 0 score-only passes, 1 fills, 2 Hirschberg half passes"""
+        """-> (ms[4], launches[4]) by kind since the last call: 0 score-only passes, 1 fills, 2 Hirschberg half passes, 3 diagonal-word
+        launches of bounded runs"""
         ms, n = np.zeros(4, dtype=np.float64), np.zeros(4, dtype=np.int64)
         self._lib.quicked_batch_kernel_times(self._h, ms.ctypes.data, n.ctypes.data)
         return ms, n

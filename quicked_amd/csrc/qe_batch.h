@@ -174,7 +174,10 @@ inline bool trace_on() { return sw_set(Sw::Trace); }
 
 // ---- the device side (qe_driver.hip)
 // dispatch on params->algo (quicked_align, quicked.c:405-437) for every pair of the batch; fetch: synchronous, results to the host
-quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch);
+// bd != nullptr: a bounded run (quicked_batch_run_bounded): pair i's bound is bd->max_dist[i], or bd->max_dist_all where that is
+// null; p is the default BANDED parameter block with the caller's only_score
+struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
+quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);
 // (re)loads a batch object with n pairs: host-side layout, arena (kept when it is large enough), H2D

@@ -196,6 +196,22 @@ QE_API quicked_status_t quicked_batch_run(quicked_batch_t* batch, const quicked_
     }, &arg);
 }
 
+// Bounded distances: the arguments are checked before anything touches the device
+QE_API quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const int32_t* max_dist, int32_t max_dist_all,
+                                                  int only_score, int sync) {
+    if (!batch || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    struct Arg { BoundedRun bd; int only_score, sync; } arg{{max_dist, max_dist_all}, only_score, sync};
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        if (x->bd.max_dist) for (int64_t i = 0; i < B->n; ++i) if (x->bd.max_dist[i] < 0) return QUICKED_ERROR;
+        if (!x->only_score && !x->sync) return QUICKED_UNIMPLEMENTED;      // CIGARs need the distances on the host first
+        quicked_params_t p = quicked_default_params();
+        p.algo = BANDED;
+        p.only_score = x->only_score != 0;
+        return run_batch(*B, p, x->sync != 0, &x->bd);
+    }, &arg);
+}
+
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {
     return guard(batch, [](quicked_batch* B, void*) {
         tl_device = B->device;

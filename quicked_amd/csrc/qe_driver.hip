@@ -32,6 +32,7 @@
 #include "qe_types.h"
 #include "qe_pool.h"
 #include "qe_batch.h"
+#include "qe_bounded.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
 // without a GPU names tests/native/hip_stub/qe_kernels_stub.h here -- tests/test_host_sanitizers.py; never set in the product)
 #ifndef QE_KERNELS_HEADER
@@ -181,6 +182,24 @@ static TaskList all_pairs(const quicked_batch& B, const quicked_params_t& p) {
     }
     L.pad();
     return L;
+}
+
+// A bounded run's list: the cutoff is the pair's bound -- clamped to max(m, n), which no distance exceeds (the same answers,
+// and a band the geometry can hold whatever the caller passes).  A pair whose lengths differ by more than its bound is
+// beyond it without a task (`beyond`).
+static int bounded_bound(const BoundedRun& bd, int pr) { return bd.max_dist ? bd.max_dist[pr] : bd.max_dist_all; }
+static void bounded_pairs(const quicked_batch& B, const BoundedRun& bd, std::vector<int32_t>& beyond, TaskList& Ld, TaskList& Lg) {
+    for (std::vector<int32_t>* v : {&Ld.pair, &Ld.p0, &Ld.m, &Ld.t0, &Ld.n, &Ld.cutoff, &Ld.tfin}) v->reserve((size_t)B.n + 64);
+    for (int64_t i = 0; i < B.n; ++i) {
+        const int pr = B.order[(size_t)i];
+        const int m = B.p_len[pr], n = B.t_len[pr];
+        if (m == 0 || n == 0) continue;                             // QUICKED_EMPTY_SEQUENCE, as in every run
+        const int bound = bounded_bound(bd, pr);
+        if (std::abs(m - n) > bound) { beyond.push_back(pr); continue; }
+        const int eff = bounded_effective(bound, m, n);
+        (bounded_diag_wanted(eff, m, n) ? Ld : Lg).push(pr, 0, m, 0, n, eff, n);      // which form takes the task
+    }
+    Ld.pad(); Lg.pad();
 }
 
 static void scatter_scores(quicked_batch& B, const TaskList& L, const std::vector<int32_t>& s, int32_t ok_status) {
@@ -503,7 +522,8 @@ static size_t classic_need_estimate(const quicked_params_t& p, const TaskList& L
 
 // The classic flow for the pairs a fast run left (W), on idle streams.  X is the batch object the pairs belong to, or the
 // stand-in for the pairs of several (merged_finish).
-static void fast_finish_classic(quicked_batch& X, Context& C, const quicked_params_t& p, FastLeft& W, size_t matrix_budget, int parity) {
+static void fast_finish_classic(quicked_batch& X, Context& C, const quicked_params_t& p, FastLeft& W, size_t matrix_budget, int parity,
+                                bool stage1_known = true) {
     W.Ls.pad();
     W.K1.score.resize(W.Ls.pair.size(), 0); W.K1.stage2.resize(W.Ls.pair.size(), 0);
     C.sync_all();
@@ -530,8 +550,38 @@ static void fast_finish_classic(quicked_batch& X, Context& C, const quicked_para
     }
     C.phase_w();
     auto enter_a = [&]() { C.phase_a(); };
-    quicked_classic(X, C, p, W.Ls, true, matrix_budget, nullptr, enter_a, false, &W.K1);
+    quicked_classic(X, C, p, W.Ls, true, matrix_budget, nullptr, enter_a, false, stage1_known ? &W.K1 : nullptr);
     C.sync_all();
+}
+
+// Bounded runs, pairs with lower-case / IUPAC bytes (FLAG_NONCANON).  The library's distance of such a pair is what
+// algo = QUICKED returns for it: the edit count of ITS alignment, in which two symbols of one class that differ as bytes
+// ('a' / 'A', 'R' / 'Y') are a mismatch (the traceback compares raw bytes, cigar.c) -- not the end cell of the matrix, and
+// not a function of the pair alone (it depends on the path QuickEd's band leaves the traceback).  So these pairs go
+// through that very flow, host-driven like the pairs a fast QuickEd run leaves, once the run's other results are on the
+// host, and its score is thresholded here.  Packed batches cannot hold such bytes.
+static void bounded_noncanon(quicked_batch& B, Context& C, const std::vector<u32>& flags, const std::vector<int32_t>& pair_bound,
+                             bool want_cigar, size_t matrix_budget, int parity) {
+    quicked_params_t p = quicked_default_params();
+    p.only_score = !want_cigar;
+    FastLeft W;
+    for (int64_t i = 0; i < B.n; ++i) {
+        const int pr = B.order[(size_t)i];
+        const int m = B.p_len[pr], n = B.t_len[pr];
+        if (m == 0 || n == 0 || !(flags[(size_t)pr] & FLAG_NONCANON) || std::abs(m - n) > pair_bound[(size_t)pr]) continue;
+        W.Ls.push(pr, 0, m, 0, n, max_cutoff(p.bandwidth, m, n), n);
+    }
+    if (W.Ls.pair.empty()) return;
+    const std::vector<int32_t> mine = W.Ls.pair;
+    fast_finish_classic(B, C, p, W, matrix_budget, parity, false);
+    for (int32_t pr : mine) {
+        int32_t& st = B.wr->status[(size_t)pr];
+        if (st == QUICKED_WIP || st == QUICKED_FAIL_NON_CONVERGENCE) st = QUICKED_OK;
+        int32_t& sc = B.wr->score[(size_t)pr];
+        const bool within = st >= 0 && sc >= 0 && sc <= pair_bound[(size_t)pr];
+        if (!within) { sc = -1; B.wr->check_ok[(size_t)pr] = -1; }
+        if (!within || !want_cigar) B.wr->cigar_off[(size_t)pr] = -1;
+    }
 }
 
 static void quicked_fast_finish(quicked_batch& B, Context& C, const quicked_params_t& p, const TaskList& L, const int32_t* d_cut,
@@ -607,7 +657,7 @@ static int rotation_depth(int64_t n, int floor_sets = 5) {
 
 static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 
-quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch) {
+quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd) {
     double tr_last = now_ms();
     tl_device = B.device;
     Context& C = ctx();
@@ -650,10 +700,11 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         for (int64_t i = 0; i < B.n; ++i) {
             const int m = B.p_len[(size_t)i], n = B.t_len[(size_t)i];
             if (m == 0 || n == 0) continue;
-            const HGeom G = host_geometry(m, n, max_cutoff(p.bandwidth, m, n));
+            // (a bounded run aligns with cutoff = the distance it found, which is within the pair's bound)
+            const HGeom G = host_geometry(m, n, bd ? bounded_effective(std::max(0, bounded_bound(*bd, (int)i)), m, n) : max_cutoff(p.bandwidth, m, n));
             const uint64_t full = (uint64_t)(QE_CPC + 1) * (uint64_t)(n / 64 + 3) * (uint64_t)G.ebb * 16;
             need_mat += (size_t)std::min<uint64_t>(full, (uint64_t)18 << 20);             // per pair; splits cap a leaf at 16 MiB of matrix
-            need_fixed += (size_t)(p.algo == QUICKED ? std::min<int64_t>((int64_t)m + n + 2, (int64_t)2 * G.cutoff + 8) : (int64_t)m + n + 2) * 15 + 512;
+            need_fixed += (size_t)((p.algo == QUICKED || bd) ? std::min<int64_t>((int64_t)m + n + 2, (int64_t)2 * G.cutoff + 8) : (int64_t)m + n + 2) * 15 + 512;
         }
         need_groups = (int)((B.n + 63) / 64);
     }
@@ -785,11 +836,55 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     const size_t matrix_budget = C.pool_budget;      // run_align subtracts what the stage needs besides the matrices
     quicked_status_t ret = QUICKED_WIP;
     QE_TRACE_POINT("setup+pack launch");
-    TaskList L = all_pairs(B, p);
+    std::vector<int32_t> beyond;
+    TaskList L, Ld, Lg;
+    if (bd) bounded_pairs(B, *bd, beyond, Ld, Lg); else L = all_pairs(B, p);
     QE_TRACE_POINT("task list");
-    if (L.pair.empty()) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
+    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty()) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
     StageResult R;
 
+    if (bd) {
+        // Bounded run: the score pass (diagonal word / general path) gives every task "d, or -1 = beyond"; with CIGARs wanted
+        // the pairs found within their bound are then aligned with cutoff = d -- exact, so the run buffers are tight
+        enter_a();
+        const BoundedOut BO = run_bounded_score(B, C, Ld, Lg);
+        B.d_score = BO.d_score;
+        std::vector<int32_t> pair_bound((size_t)B.n);
+        for (int64_t i = 0; i < B.n; ++i) pair_bound[(size_t)i] = bounded_bound(*bd, (int)i);
+        if (pf) {
+            pf->kind = 1; pf->task_pair = BO.task_pair; pf->d_score = BO.d_score; pf->d_adv = BO.d_adv; pf->counter_slot = 0;
+            pf->ok_status = QUICKED_OK; pf->beyond_pair = beyond; pf->pair_bound = std::move(pair_bound); pf->matrix_budget = matrix_budget;
+        } else {
+            std::vector<int32_t> sc; std::vector<u32> adv, flags;
+            {
+                FetchBatch fb(C);
+                fb.add(sc, (const int32_t*)BO.d_score, BO.task_pair.size()); fb.add(adv, (const u32*)BO.d_adv, BO.task_pair.size());
+                if (!B.packed) fb.add(flags, (const u32*)B.d_flags[par], (size_t)B.n);
+                fb.sync();
+            }
+            B.counters[0] = (int64_t)sum_u32(adv);
+            for (int32_t pr : beyond) B.wr->status[pr] = QUICKED_OK;
+            bool noncanon = false;
+            TaskList LA;
+            for (size_t t = 0; t < BO.task_pair.size(); ++t) {
+                const int pr = BO.task_pair[t];
+                if (pr < 0) continue;
+                B.wr->score[pr] = sc[t]; B.wr->status[pr] = QUICKED_OK;
+                if (!flags.empty() && (flags[(size_t)pr] & FLAG_NONCANON)) { noncanon = true; continue; }      // bounded_noncanon
+                if (want_cigar && sc[t] >= 0) LA.push(pr, 0, B.p_len[pr], 0, B.t_len[pr], sc[t], B.t_len[pr]);
+            }
+            if (!LA.pair.empty()) {
+                AlignStats AS;
+                run_align(B, C, LA, true, true, matrix_budget, split_threshold(), QUICKED_OK, &B.d_score, &AS, nullptr, true);
+                C.phase_a();
+                B.counters[1] = (int64_t)AS.fill_adv; B.counters[3] = (int64_t)AS.tb_steps;
+                // (a split that does not converge is not an error where the distance is known: run_quicked, quicked.c:290-291)
+                for (int32_t pr : LA.pair) if (pr >= 0 && B.wr->status[pr] == QUICKED_FAIL_NON_CONVERGENCE) B.wr->status[pr] = QUICKED_OK;
+            }
+            if (noncanon) { bounded_noncanon(B, C, flags, pair_bound, want_cigar, matrix_budget, par); C.phase_a(); }
+        }
+        ret = QUICKED_OK;
+    } else
     switch (p.algo) {
     case BANDED:                                                    // run_banded, quicked.c:58-89
         enter_a();
@@ -951,6 +1046,16 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
             const int pr = F.task_pair[t];
             if (pr < 0) continue;
             B.wr->score[pr] = sc[t]; B.wr->status[pr] = F.ok_status;
+        }
+        for (int32_t pr : F.beyond_pair) B.wr->status[pr] = F.ok_status;
+        if (!F.pair_bound.empty() && !B.packed) {
+            // a bounded run: its pairs with lower-case / IUPAC bytes get their distance from the QuickEd flow now.  The flags are
+            // the batch's own memory and a function of its bytes: any run that used the plane set since wrote the same values
+            std::vector<u32> flags;
+            { FetchBatch fb(C); fb.add(flags, (const u32*)B.d_flags[F.parity], (size_t)B.n); fb.sync(); }
+            bool noncanon = false;
+            for (u32 f : flags) noncanon |= (f & FLAG_NONCANON) != 0;
+            if (noncanon) bounded_noncanon(B, C, flags, F.pair_bound, false, F.matrix_budget, F.parity);
         }
         B.counters[F.counter_slot] += (int64_t)sum_u32(w);
         for (int32_t x : ab) B.counters[6] += (x != 0);

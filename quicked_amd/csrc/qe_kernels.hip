@@ -29,6 +29,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include "qe_types.h"
+#include "qe_bounded.h"
 
 namespace qe {
 
@@ -1129,6 +1130,64 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
 
 template __global__ void k_banded<false>(BandedArgs);
 template __global__ void k_banded<true>(BandedArgs);
+
+// ===========================================================================
+// Bounded edit distance, diagonal-word form (qe_bounded.h): one lane per pair, score only, for tasks whose Ukkonen band
+// fits one 64-bit word (bounded_diag_takes: min(bound, max(m, n)) <= 63, |m - n| within it).  The whole state -- the
+// vertical deltas of the word's 64 rows, the pattern-plane window that slides with them, the tracked cell's value --
+// lives in registers for the whole pair: no group workspace, nothing written but the result.  Memory traffic per 64 text
+// columns: the text's three plane words and the pattern's next 64 rows (six words).
+// A lane whose tracked value has passed its bound is decided (values along a diagonal never decrease) and stops; the wave
+// leaves the column loop when all its lanes are decided or done.  Whole pairs only (p0 = t0 = 0).
+// ===========================================================================
+#define QE_HAVE_K_BOUNDED_DIAG 1
+__global__ __launch_bounds__(256) void k_bounded_diag(BoundedArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
+    if (g * 64 >= A.T.ntasks) return;
+    const int pair = (t < A.T.ntasks) ? A.T.pair[t] : -1;
+    const bool valid = pair >= 0;
+    if (!__any(valid)) return;
+    int m = 1, n = 1, bound = 0;
+    const u64* pp = A.P.pl_p;
+    const u64* tp = A.P.pl_t;
+    BoundedDiag S;
+    S.Pv = S.Mv = S.wa = S.wb = S.wn = S.xa = S.xb = S.xn = S.force = S.track = 0; S.score = 0; S.dlo = 0;
+    if (valid) {
+        m = A.T.m[t]; n = A.T.n[t]; bound = A.T.cutoff[t];
+        pp = A.P.pl_p + A.P.pl_p_off[pair];
+        tp = A.P.pl_t + A.P.pl_t_off[pair];
+        bounded_diag_init(S, pp, m, n, bound);
+    }
+    const int my_chunks = valid ? (n + 63) >> 6 : 0;
+    const int wave_chunks = wave_max(my_chunks);
+    u32 adv = 0;
+    for (int k = 0; k < wave_chunks; ++k) {
+        const int ncols = (k < my_chunks) ? min(64, n - 64 * k) : 0;
+        const bool live = ncols > 0 && S.score <= bound;
+        if (!__any(live)) break;
+        if (live) {
+            const u64* q = tp + 3 * (int64_t)k;
+            const u64 T0 = q[0], T1 = q[1], TN = q[2];
+            bounded_diag_chunk(S, pp, m, k, ncols, T0, T1, TN);
+            adv += (u32)ncols;
+        }
+    }
+    if (valid) {
+        A.o_score[t] = bounded_answer(S.score, bound);
+        A.o_adv[t] = adv;                                     // one block step per column
+    }
+}
+
+// The rule of a bounded run for the tasks a general score-only pass took: its value r is the cost of a real path (r >= d),
+// and its band contains Ukkonen's for the bound, so r <= bound <=> d <= bound, and then r = d.  Anything else -- a larger
+// value, "the band never reached the end cell" (-1) -- is "beyond".
+__global__ __launch_bounds__(256) void k_bounded_threshold(int nt, const int32_t* __restrict__ score, const u32* __restrict__ adv,
+                                                           const int32_t* __restrict__ bound, int32_t* __restrict__ o_score, u32* __restrict__ o_adv) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    o_score[t] = bounded_answer(score[t], bound[t]);
+    o_adv[t] = adv[t];
+}
 
 
 // ===========================================================================

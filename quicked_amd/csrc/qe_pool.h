@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -106,6 +106,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::FillSys, "QE_FILL_SYS", -1},                  {Sw::FillMulti, "QE_FILL_MULTI", 1},
     {Sw::TraceSys, "QE_TRACE_SYS", -1},                {Sw::Trace, "QE_TRACE", 0},
     {Sw::TracePool, "QE_TRACE_POOL", 0},               {Sw::OomWaitMs, "QE_OOM_WAIT_MS", 10000},
+    {Sw::BoundedDiag, "QE_BOUNDED_DIAG", -1},          // bounded runs: -1 the library's choice, 0 never (general path), 1 wherever k_bounded_diag's precondition holds
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {

@@ -434,6 +434,8 @@ struct PendingFetch {
     const int32_t* d_cut = nullptr; const int32_t* d_skip = nullptr; const u32* d_stage_steps = nullptr;
     quicked_params_t params; TaskList L; size_t matrix_budget = 0;
     int parity = 0;                           // the plane set / ev_done slot of the run
+    std::vector<int32_t> beyond_pair;         // bounded runs: pairs that are beyond their bound by their lengths alone (no task): score -1, ok_status
+    std::vector<int32_t> pair_bound;          // bounded runs: every pair's bound (the fetch thresholds the pairs it hands to the QuickEd flow)
 };
 
 // One wavefront per alignment (k_banded_wave) is for few, long alignments: up to ~1000 tasks every task gets a wave of its
@@ -615,6 +617,78 @@ static void run_fill_score(quicked_batch& B, Context& C, const TaskList& L, Stag
         fb.add(R->score, S.O.score, S.nt); fb.add(R->adv, S.O.adv, S.nt);
         fb.sync();
     }
+}
+
+// ---------------------------------------------------------------------------
+// Bounded runs (quicked_batch_run_bounded): per task "the distance if it is within the task's bound, else -1".
+// ---------------------------------------------------------------------------
+#ifndef QE_HAVE_K_BOUNDED_DIAG
+// a kernels header without the two (the host-only build's stand-ins): the same source on the host
+static void k_bounded_diag(BoundedArgs A) {
+    for (int t = 0; t < A.T.ntasks; ++t) {
+        const int pr = A.T.pair[t];
+        if (pr < 0) continue;
+        A.o_score[t] = bounded_diag_pair(A.P.pl_p + A.P.pl_p_off[pr], A.T.m[t], A.P.pl_t + A.P.pl_t_off[pr], A.T.n[t], A.T.cutoff[t]);
+        A.o_adv[t] = (u32)A.T.n[t];
+    }
+}
+static void k_bounded_threshold(int nt, const int32_t* score, const u32* adv, const int32_t* bound, int32_t* o_score, u32* o_adv) {
+    for (int t = 0; t < nt; ++t) { o_score[t] = bounded_answer(score[t], bound[t]); o_adv[t] = adv[t]; }
+}
+#endif
+
+// Which form takes a task.  QE_BOUNDED_DIAG = 1: the diagonal word (k_bounded_diag) wherever its precondition holds --
+// bounded_diag_takes: min(bound, max(m, n)) <= 63; 0: never.  Unset, the library's choice: the diagonal word for pairs of
+// 2000 bases and more, the lengths at which it was measured ahead of both the general path and a BANDED run at bandwidth 1
+// by more than their spread (ms per queued run, diagonal word / general / BANDED: 400 k x 2 kb 4.4 / 9.8 / 8.1, 200 k x 4 kb
+// 2.4 / 4.4 / 3.7, 100 k x 10 kb 2.5 / 3.4 / 3.1).  On 800 k x 1 kb (16.1 / 22.8 / 16.5) and 1 M x 150 b (19.7 / 27.8 / 20.4) it
+// ties with the BANDED run -- such runs spend their time on the task list and the pack, which all three do -- although it
+// is well ahead of the general path: by the rule of DESIGN.md 4.9 that is not enough for a default.
+// Everything else goes through the general path: the score-only pass over the FILL's band geometry with cutoff = the bound
+// (run_fill_score), then k_bounded_threshold.  That geometry (bpm_banded.c:121-135) holds the diagonals -rel .. diff + rel,
+// rel = ceil((cutoff - |diff|) / 2), of Ukkonen's band in whole blocks, and "cutoff >= distance => end cell = distance" is
+// what QuickEd's only_score rests on.
+enum : int { QE_BOUNDED_DIAG_DEFAULT_MIN_LEN = 2000 };
+static bool bounded_diag_wanted(int bound, int m, int n) {
+    const int force = sw(Sw::BoundedDiag);
+    if (force == 0 || !bounded_diag_takes(bound, m, n)) return false;
+    return force == 1 || std::max(m, n) >= QE_BOUNDED_DIAG_DEFAULT_MIN_LEN;
+}
+
+// Ld / Lg: the tasks of the diagonal word / of the general path (bounded_pairs: cutoff = the effective bound, padded).  Leaves
+// one score and one column count per task of `task_pair` on the device; the diagonal-word launch is timed as kind 3
+// (quicked_batch_kernel_times)
+struct BoundedOut { std::vector<int32_t> task_pair; int32_t* d_score = nullptr; u32* d_adv = nullptr; };
+static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList& Ld, const TaskList& Lg) {
+    BoundedOut O;
+    const size_t nd = Ld.pair.size(), ng = Lg.pair.size();
+    O.task_pair = Ld.pair;
+    O.task_pair.insert(O.task_pair.end(), Lg.pair.begin(), Lg.pair.end());
+    if (nd + ng == 0) return O;
+    O.d_score = C.scratch_p->take<int32_t>(nd + ng);
+    O.d_adv = C.scratch_p->take<u32>(nd + ng);
+    HIP_CHECK(hipMemsetAsync(O.d_score, 0xFF, (nd + ng) * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, (nd + ng) * sizeof(u32), C.stream));
+    if (nd) {
+        const DevTasks T = upload_tasks(Ld, C);
+        BoundedArgs a{};
+        a.P = pair_view(B, false); a.T = T.v; a.o_score = O.d_score; a.o_adv = O.d_adv;
+        auto* ke = C.kernel_events(3);
+        if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+        launch_groups(C, k_bounded_diag, a, (size_t)Ld.ngroups(), 4, 0);
+        if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    }
+    if (ng) {
+        PendingFetch G;                                // where the pass leaves its scores and block-advance counts
+        int32_t* d_pass = nullptr;
+        run_fill_score(B, C, Lg, nullptr, false, &d_pass, &G);
+        int32_t* d_bound = C.scratch_p->take<int32_t>(ng);
+        h2d(d_bound, Lg.cutoff, C.stream);
+        hipLaunchKernelGGL(k_bounded_threshold, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, C.stream, (int)ng, G.d_score, G.d_adv,
+                           (const int32_t*)d_bound, O.d_score + nd, O.d_adv + nd);
+        HIP_CHECK(hipGetLastError());
+    }
+    return O;
 }
 
 // One wave per alignment wherever the strings are more than a few runs long, else one lane per alignment.  Decided before the

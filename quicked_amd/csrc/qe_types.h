@@ -92,6 +92,15 @@ struct BandedArgs {
                                   // only_score takes its score from such a pass instead of filling, tracing back and counting edits
 };
 
+// Bounded edit distance, diagonal-word form (k_bounded_diag, qe_bounded.h): whole pairs (p0 = t0 = 0), T.cutoff = the pair's
+// bound; no workspace
+struct BoundedArgs {
+    PairView P;
+    TaskView T;
+    int32_t* o_score;        // the distance if it is within the bound, else -1
+    u32* o_adv;              // text columns walked (one block step each)
+};
+
 // BandEd score-only, G lanes per alignment (cooperative form of k_banded<false>)
 struct CoopArgs {
     PairView P;
