@@ -166,7 +166,10 @@ quicked_status_t quicked_batch_validate(quicked_batch_t* batch, const char* ciga
  *   [0] block-advances of score-only BandEd passes   [1] of fills
  *   [2] WindowEd block steps   [3] traceback steps   [4] CIGAR ops
  *   [5] last kernel-only time in ns (HIP events on the batch's stream)
- *   [6] pairs that went past stage 1   [7] pairs that went past stage 2 */
+ *   [6] pairs that went past stage 1   [7] pairs that went past stage 2
+ * BANDED with only_score: a large list takes a first pass at half the cutoff and the full band only for the tasks whose
+ * first result proves nothing (same scores; QE_SCORE_NARROW=0: one pass): [0] counts both passes' block-advances, so
+ * two identical runs may report different [0]; [7] = tasks the second pass ran */
 quicked_status_t quicked_batch_counters(quicked_batch_t* batch, int64_t counters_out[8]);
 /* QUICKED runs that queue stage 1 and the align step together (see quicked_batch_run) align the pairs that leave stage 1,
  * or whose bound exceeds the planned buffers, after the run (early-finish threads, or the fetch): how many pairs of the last

@@ -334,6 +334,10 @@ QE_API quicked_status_t quicked_pool_trim(void) {
 // suites change switches between runs and reach it through capi.reload_env().
 QE_API quicked_status_t quicked_debug_reload_env(void) {
     qe::switches_reload();
+    {   // ... and what the library has learnt under the old switches: the two-pass verdicts of every context (narrow_take)
+        std::lock_guard<std::mutex> lk(qe::g_ctx_mu);
+        for (qe::Context* c : qe::g_ctx_all) for (auto& v : c->narrow_off) v = 0;
+    }
     return QUICKED_OK;
 }
 

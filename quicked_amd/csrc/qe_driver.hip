@@ -601,6 +601,7 @@ static void stash_results(quicked_batch& B, Context& C, PendingFetch& F) {
     std::vector<StashItem> items;
     const size_t nt = F.task_pair.size(), nr = F.AO.nroots, nl = F.leaf_pair.size(), nq = F.L.pair.size();
     stash_add(items, F.d_score, nt * 4); stash_add(items, F.d_adv, nt * 4); stash_add(items, F.d_steps, nt * 4); stash_add(items, F.d_abort, nt * 4);
+    stash_add(items, F.d_narrow, 32);
     if (F.kind == 2) {
         stash_add(items, F.AO.len, nr * 4); stash_add(items, F.AO.edits, nr * 4); stash_add(items, F.AO.nops, nr * 4);
         stash_add(items, F.AO.ok, nr * 4); stash_add(items, F.AO.str_off, nr * 8);
@@ -889,10 +890,11 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     case BANDED:                                                    // run_banded, quicked.c:58-89
         enter_a();
         if (p.only_score) {
-            run_banded_score(B, C, L, false, &R, fetch, &B.d_score, pf);
+            run_banded_score(B, C, L, false, &R, fetch, &B.d_score, pf, true);
             if (fetch) {
                 scatter_scores(B, L, R.score, QUICKED_WIP);
                 B.counters[0] = (int64_t)sum_u32(R.adv);
+                if (!R.narrow.empty() && !R.narrow_probe) B.counters[7] = (int64_t)R.narrow[0];     // tasks the second pass ran (launch_banded_narrow)
                 for (int32_t x : R.hew) B.counters[6] += (x != 0);     // tasks the cooperative kernel handed to the fallback pass
             }
         } else {
@@ -1034,14 +1036,16 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {
         const size_t nt = F.task_pair.size();
-        std::vector<int32_t> sc, ab; std::vector<u32> w;
+        std::vector<int32_t> sc, ab; std::vector<u32> w; std::vector<unsigned long long> nar;
         {
             FetchBatch fb(C);
             fb.add(sc, F.d_score, nt);
             if (F.d_adv) fb.add(w, F.d_adv, nt); else if (F.d_steps) fb.add(w, F.d_steps, nt);
             if (F.d_abort) fb.add(ab, F.d_abort, nt);
+            if (F.d_narrow) fb.add(nar, F.d_narrow, 4);
             fb.sync();
         }
+        if (F.d_narrow) { if (!F.narrow_probe) B.counters[7] = (int64_t)nar[0]; narrow_report(F.narrow_ctx, F.narrow_cls, nar); }
         for (size_t t = 0; t < nt; ++t) {
             const int pr = F.task_pair[t];
             if (pr < 0) continue;

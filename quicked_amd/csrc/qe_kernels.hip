@@ -4123,6 +4123,79 @@ __global__ __launch_bounds__(256) void k_apply_cutoffs(int nt, int32_t* cutoff, 
 }
 
 // ===========================================================================
+// BandEd score-only in two passes (NarrowArgs, qe_types.h): what runs between and around the two k_banded<false> launches.
+// Blocks of 256 threads = four waves; every wave takes part as a whole (no early return before the ballots).
+// ===========================================================================
+#define QE_HAVE_K_NARROW 1
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+    const int nt = A.T.ntasks;
+    if (A.phase == 0) {
+        if (t < 4) A.stat[t] = 0;
+        if (t >= nt) return;
+        A.q_pair[t] = -1;
+        A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+        return;
+    }
+    if (A.phase == 1) {
+        const bool live = t < nt && A.T.pair[t] >= 0;
+        bool halved = false, miss = false;
+        if (live) {
+            const int c1 = A.cut1[t];
+            halved = c1 != A.T.cutoff[t];
+            miss = halved && !narrow_accepts(A.T.m[t], A.T.n[t], c1, A.T.cutoff[t], A.score[t]);
+        }
+        const unsigned long long a1 = wave_sum_u64(halved ? (unsigned long long)A.adv[t] : 0ull);
+        const u64 mask = __ballot(miss), hmask = __ballot(halved);
+        unsigned long long base = 0;
+        if (lane == 0) {
+            if (hmask) { atomicAdd(&A.stat[1], a1); atomicAdd(&A.stat[3], (unsigned long long)__popcll(hmask)); }
+            if (mask) base = atomicAdd(&A.stat[0], (unsigned long long)__popcll(mask));
+        }
+        base = __shfl(base, 0);
+        if (miss) {
+            const int j = (int)base + __popcll(mask & (((u64)1 << lane) - 1));      // j < nt: every miss is one of the nt tasks
+            A.q_pair[j] = A.T.pair[t]; A.q_p0[j] = A.T.p0[t]; A.q_m[j] = A.T.m[t]; A.q_t0[j] = A.T.t0[t]; A.q_n[j] = A.T.n[t];
+            A.q_cutoff[j] = A.T.cutoff[t]; A.q_tfin[j] = A.T.tfin[t]; A.q_src[j] = t;
+        }
+        return;
+    }
+    if (A.phase == 3) {
+        const bool live = t < nt && A.T.pair[t] >= 0;                 // (the sample holds only tasks whose cutoff was halved)
+        unsigned long long a1 = 0, a2 = 0;
+        bool miss = false;
+        if (live) {
+            const int src = (((t >> 6) * A.stride) << 6) + (t & 63);
+            a1 = A.q_adv[t];
+            miss = !narrow_accepts(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.main_cutoff[src], A.q_score[t]);
+            if (miss) a2 = A.adv[src];
+            A.adv[src] += (u32)a1;
+        }
+        a1 = wave_sum_u64(a1); a2 = wave_sum_u64(a2);
+        const u64 mask = __ballot(miss), lmask = __ballot(live);
+        if (lane == 0 && lmask) {
+            atomicAdd(&A.stat[1], a1); atomicAdd(&A.stat[3], (unsigned long long)__popcll(lmask));
+            if (mask) { atomicAdd(&A.stat[0], (unsigned long long)__popcll(mask)); atomicAdd(&A.stat[2], a2); }
+        }
+        return;
+    }
+    const bool mine = t < nt && (unsigned long long)t < A.stat[0];
+    unsigned long long a2 = 0;
+    if (mine) {
+        const int src = A.q_src[t];
+        a2 = A.q_adv[t];
+        A.score[src] = A.q_score[t];
+        A.adv[src] += (u32)a2;
+    }
+    a2 = wave_sum_u64(a2);
+    if (lane == 0 && a2) atomicAdd(&A.stat[2], a2);
+}
+
+// ===========================================================================
 // CIGAR formatting (cigar_sprint, cigar.c:453-488): runs are stored back to
 // front, the string goes front to back: "<len><op>" per run.
 // ===========================================================================

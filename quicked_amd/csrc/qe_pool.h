@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -107,6 +107,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::TraceSys, "QE_TRACE_SYS", -1},                {Sw::Trace, "QE_TRACE", 0},
     {Sw::TracePool, "QE_TRACE_POOL", 0},               {Sw::OomWaitMs, "QE_OOM_WAIT_MS", 10000},
     {Sw::BoundedDiag, "QE_BOUNDED_DIAG", -1},          // bounded runs: -1 the library's choice, 0 never (general path), 1 wherever k_bounded_diag's precondition holds
+    {Sw::ScoreNarrow, "QE_SCORE_NARROW", -1},          // BandEd score-only runs: -1 a first pass at half the cutoff where it pays (narrow_wanted), 0 never (the reference's band, cell for cell), 1 wherever a task's band is narrower there (tests), -2 as -1 without the policy's probes (diagnosis)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {
@@ -434,6 +435,10 @@ struct Context {
     int last_na = 0, last_sub_batches = 0;   // what the planner chose for the last run (quicked_pool_stats)
     int in_flight = 1;                       // runs of this thread that may be on the device at once while the current one executes
     size_t pool_budget = 0;                  // bytes one A pool may hold in this run (plan_pools)
+    // BandEd score-only in two passes (qe_stages.hip: narrow_wanted): per length class (log2 of the list's longest text), 0 while
+    // the first pass pays or nothing is known, else 1 + the eligible runs that took the single pass since it last did not.
+    // Written when a run's counts reach the host -- by whichever thread fetches it: atomics
+    std::atomic<int> narrow_off[32] = {};
     size_t seen_free = 0, seen_total = 0;    // last hipMemGetInfo reading of this device ...
     uint64_t seen_epoch = ~(uint64_t)0;      // ... and the book's epoch it was taken in
     hipStream_t& sa() { return stream_a2[ai]; }

@@ -223,6 +223,8 @@ static void apply_device_cutoffs(Context& C, const DevTasks& T, size_t nt, int32
 struct StageResult {
     std::vector<int32_t> score, hew, first, last, posv, nruns, nops, edits, len;
     std::vector<u32> adv, steps;
+    std::vector<unsigned long long> narrow;   // a two-pass BandEd score-only run's (or a probe's) NarrowArgs::stat
+    bool narrow_probe = false;
 };
 
 static uint64_t sum_u32(const std::vector<u32>& v) { uint64_t s = 0; for (u32 x : v) s += x; return s; }
@@ -233,6 +235,7 @@ struct ScoreLaunch {
     DevTasks T; DevLayout D; TaskOut O; size_t nt = 0;
     int G = 1;                                                          // >= 2: cooperative launch + fallback pass
     uint8_t* cws = nullptr; int64_t* c_off = nullptr; int32_t *c_ns = nullptr, *c_nr = nullptr, *c_nch = nullptr;
+    unsigned long long* narrow = nullptr; bool narrow_probe = false;   // launch_banded_narrow / launch_banded_probe: NarrowArgs::stat
 };
 static BandState coop_state(const ScoreLaunch& S) {
     BandState b;
@@ -277,6 +280,189 @@ static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskL
     auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    return S;
+}
+
+// ---------------------------------------------------------------------------
+// BandEd score-only in two passes: k_banded<false> over the list with every task's cutoff halved where
+// that makes its band narrower, k_narrow packs the tasks whose result proves nothing (-1, or above the halved cutoff) into
+// dense groups of 64, k_banded<false> again over those at their own cutoffs.  A result 0 .. C' of the first pass is the cost
+// of a real path, so the distance is within C', and the pass at C >= C' returns the same value: the scores are the single
+// pass's.  Nothing waits for the host: the second launch has the grid of the whole list, and the groups beyond the misses
+// find pair = -1 and return.  Both launches share one group workspace, laid out for the list's largest geometry at the
+// full cutoff -- the membership of the second launch's groups is decided on the device.
+// ---------------------------------------------------------------------------
+struct NarrowPlan { bool ok = false; int cls = 0; size_t live = 0, narrower = 0; };
+// whole-text passes only (a stopped band is exported from ONE pass: Hirschberg half passes keep the single pass)
+static NarrowPlan narrow_plan(const TaskList& L) {
+    NarrowPlan P;
+    int n_max = 1;
+    for (size_t t = 0; t < L.pair.size(); ++t) {
+        if (L.pair[t] < 0) continue;
+        if (L.tfin[t] != L.n[t]) return P;
+        ++P.live;
+        P.narrower += narrow_cutoff(L.m[t], L.n[t], L.cutoff[t]) != L.cutoff[t];
+        n_max = std::max(n_max, L.n[t]);
+    }
+    while ((n_max >> (P.cls + 1)) != 0 && P.cls < 31) ++P.cls;
+    P.ok = P.narrower > 0;
+    return P;
+}
+// The verdict per context and length class: the first pass pays while the tasks it halved advance fewer block-columns in
+// both passes together than the single pass costs them -- estimated from what the second pass advanced per task it ran,
+// times their number.  It is taken when a run's counts reach the host: at the end of a synchronous run, in the fetch of a
+// queued one (a queued run that is never fetched teaches nothing).  A run without misses has paid (its band is the
+// narrower one); unknown data take the first pass; after a run that did not pay the class takes the single pass and probes
+// every QE_NARROW_PROBE-th eligible run.  A probe is a single-pass run like its neighbours, plus a pass at the halved cutoffs
+// over the tasks of every QE_NARROW_PROBE-th group on the side stream (launch_banded_probe): no result waits for it, and it
+// is over before the run's own launch is.  (Two passes over a sample IN the run were measured first: the second launch's few
+// waves walk a whole band at the full cutoff behind the first launch, the run holds its set of the rotation for two
+// chains' time, and a stream of 10 kb pairs at 10 % ran 4.5-5 % behind the single pass: profiles/narrow_headline.md.)
+enum : int { QE_NARROW_PROBE = 16 };
+// -> 0: the single pass, 1: two passes, 2: the single pass and a probe
+static int narrow_take(Context& C, int cls) {
+    const int v = C.narrow_off[cls].load();
+    if (v == 0) return 1;
+    if (v >= QE_NARROW_PROBE) { C.narrow_off[cls] = 1; return sw(Sw::ScoreNarrow) == -2 ? 0 : 2; }      // -2: no probes (diagnosis)
+    C.narrow_off[cls] = v + 1;
+    return 0;
+}
+static void narrow_report(Context* C, int cls, const std::vector<unsigned long long>& st) {
+    if (!C || st.size() < 4) return;
+    const double misses = (double)st[0], a1 = (double)st[1], a2 = (double)st[2], halved = (double)st[3];
+    const bool paid = st[0] == 0 || (a1 + a2) * misses < a2 * halved;
+    int unknown = 0;
+    if (paid) C->narrow_off[cls] = 0; else C->narrow_off[cls].compare_exchange_strong(unknown, 1);
+}
+
+#ifndef QE_HAVE_K_NARROW
+// a kernels header without it (the host-only build's stand-ins): the same phases on the host
+static void k_narrow(NarrowArgs A) {
+    const int nt = A.T.ntasks;
+    if (A.phase == 0) {
+        for (int q = 0; q < 4; ++q) A.stat[q] = 0;
+        for (int t = 0; t < nt; ++t) {
+            A.q_pair[t] = -1;
+            A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+        }
+    } else if (A.phase == 1) {
+        for (int t = 0; t < nt; ++t) {
+            if (A.T.pair[t] < 0 || A.cut1[t] == A.T.cutoff[t]) continue;
+            A.stat[1] += A.adv[t]; ++A.stat[3];
+            if (narrow_accepts(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.score[t])) continue;
+            const int j = (int)A.stat[0]++;
+            A.q_pair[j] = A.T.pair[t]; A.q_p0[j] = A.T.p0[t]; A.q_m[j] = A.T.m[t]; A.q_t0[j] = A.T.t0[t]; A.q_n[j] = A.T.n[t];
+            A.q_cutoff[j] = A.T.cutoff[t]; A.q_tfin[j] = A.T.tfin[t]; A.q_src[j] = t;
+        }
+    } else if (A.phase == 2) {
+        for (int j = 0; j < (int)A.stat[0]; ++j) { A.score[A.q_src[j]] = A.q_score[j]; A.adv[A.q_src[j]] += A.q_adv[j]; A.stat[2] += A.q_adv[j]; }
+    } else {
+        for (int t = 0; t < nt; ++t) {
+            if (A.T.pair[t] < 0) continue;
+            const int src = (((t >> 6) * A.stride) << 6) + (t & 63);
+            A.stat[1] += A.q_adv[t]; ++A.stat[3];
+            if (!narrow_accepts(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.main_cutoff[src], A.q_score[t])) { ++A.stat[0]; A.stat[2] += A.adv[src]; }
+            A.adv[src] += A.q_adv[t];
+        }
+    }
+}
+#endif
+
+// every group: the tallest band, the most rows and the most chunks of the list
+static BandLayout narrow_uniform(BandLayout lay) {
+    int ns = 3, nr = 4, nch = 2;
+    for (size_t g = 0; g < lay.nslots.size(); ++g) { ns = std::max(ns, (int)lay.nslots[g]); nr = std::max(nr, (int)lay.nrows[g]); nch = std::max(nch, (int)lay.nch[g]); }
+    const size_t bytes = ((size_t)2 * (ns + 1) * 64 * 8 + (size_t)nr * 64 * 4 + (size_t)2 * nch * 64 * 2 + 255) & ~(size_t)255;
+    for (size_t g = 0; g < lay.nslots.size(); ++g) { lay.nslots[g] = ns; lay.nrows[g] = nr; lay.nch[g] = nch; lay.ws_off[g] = (int64_t)(g * bytes); }
+    lay.ws_bytes = bytes * lay.nslots.size();
+    lay.mat_u4 = 0;
+    return lay;
+}
+
+// A probe: the list's single pass as launch_banded_score queues it, and beside it, on the side stream, k_banded<false> at the
+// halved cutoffs over the tasks of every QE_NARROW_PROBE-th group whose band is narrower there.  k_narrow phase 3 then counts
+// what two passes would have cost that sample.  The sample's pass starts with the run's launch and walks half its band.
+static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed) {
+    ScoreLaunch S;
+    S.nt = L.pair.size();
+    TaskList Ls;
+    for (size_t g = 0; g < S.nt / 64; g += QE_NARROW_PROBE)
+        for (size_t t = g * 64; t < g * 64 + 64; ++t) {
+            const int c1 = L.pair[t] >= 0 ? narrow_cutoff(L.m[t], L.n[t], L.cutoff[t]) : 0;
+            if (L.pair[t] >= 0 && c1 != L.cutoff[t]) Ls.push(L.pair[t], L.p0[t], L.m[t], L.t0[t], L.n[t], c1, L.tfin[t]);
+            else Ls.push(-1, 0, 1, 0, 1, 0, 0);
+        }
+    BandLayout lay = band_layout(L, false, false), lays = band_layout(Ls, false, false);
+    lay.mat_u4 = 0; lays.mat_u4 = 0;
+    S.T = upload_tasks(L, C);
+    S.D = upload_layout(lay, C);
+    S.O = take_out(C, S.nt);
+    ScoreLaunch P;
+    P.nt = Ls.pair.size();
+    P.T = upload_tasks(Ls, C);
+    P.D = upload_layout(lays, C);
+    P.O = take_out(C, P.nt);
+    S.narrow = C.scratch_p->take<unsigned long long>(4);
+    S.narrow_probe = true;
+    HIP_CHECK(hipMemsetAsync(S.narrow, 0, 4 * sizeof(unsigned long long), C.stream));
+    hipStream_t main_s = C.stream, side = C.side_stream();
+    HIP_CHECK(hipEventRecord(C.ev_fork, main_s)); HIP_CHECK(hipStreamWaitEvent(side, C.ev_fork, 0));
+    BandedArgs a = score_args(B, S, reversed);
+    a.lane_rel = sw(Sw::LaneRel);
+    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, main_s));
+    launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, main_s));
+    C.stream = side;
+    BandedArgs b = score_args(B, P, reversed);
+    b.lane_rel = a.lane_rel;
+    launch_groups(C, k_banded<false>, b, Ls.ngroups(), 8, 0);
+    C.stream = main_s;
+    HIP_CHECK(hipEventRecord(C.ev_join, side)); HIP_CHECK(hipStreamWaitEvent(main_s, C.ev_join, 0));
+    NarrowArgs x{};
+    x.phase = 3; x.stride = QE_NARROW_PROBE;
+    x.T = P.T.v; x.score = S.O.score; x.adv = S.O.adv; x.q_score = P.O.score; x.q_adv = P.O.adv; x.main_cutoff = S.T.cutoff; x.stat = S.narrow;
+    hipLaunchKernelGGL(k_narrow, dim3((unsigned)((P.nt + 255) / 256)), dim3(256), 0, main_s, x);
+    HIP_CHECK(hipGetLastError());
+    return S;
+}
+
+static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay) {
+    ScoreLaunch S;
+    S.nt = L.pair.size();
+    const size_t nt = S.nt;
+    S.T = upload_tasks(L, C);
+    S.D = upload_layout(lay, C);
+    S.O = take_out(C, nt);
+    ScoreLaunch S2 = S;                              // the packed list of the misses, its outputs; the same workspace
+    S2.O = take_out(C, nt);
+    int32_t* blk = C.scratch_p->take<int32_t>(9 * nt);
+    S.narrow = C.scratch_p->take<unsigned long long>(4);
+    NarrowArgs x{};
+    x.T = S.T.v; x.cut1 = blk; x.score = S.O.score; x.adv = S.O.adv;
+    x.q_pair = blk + nt; x.q_p0 = blk + 2 * nt; x.q_m = blk + 3 * nt; x.q_t0 = blk + 4 * nt; x.q_n = blk + 5 * nt;
+    x.q_cutoff = blk + 6 * nt; x.q_tfin = blk + 7 * nt; x.q_src = blk + 8 * nt;
+    x.q_score = S2.O.score; x.q_adv = S2.O.adv; x.stat = S.narrow;
+    S2.T.v.pair = x.q_pair; S2.T.v.p0 = x.q_p0; S2.T.v.m = x.q_m; S2.T.v.t0 = x.q_t0; S2.T.v.n = x.q_n;
+    S2.T.v.cutoff = x.q_cutoff; S2.T.v.tfin = x.q_tfin;
+    const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
+    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    x.phase = 0;
+    hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
+    BandedArgs a = score_args(B, S, reversed);
+    a.T.cutoff = x.cut1;
+    a.lane_rel = sw(Sw::LaneRel);
+    launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
+    x.phase = 1;
+    hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
+    BandedArgs b = score_args(B, S2, reversed);
+    b.lane_rel = a.lane_rel;
+    launch_groups(C, k_banded<false>, b, L.ngroups(), 8, 0);
+    x.phase = 2;
+    hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
+    HIP_CHECK(hipGetLastError());
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     return S;
 }
@@ -424,6 +610,8 @@ struct PendingFetch {
     std::vector<int32_t> task_pair;
     const int32_t* d_score = nullptr; const u32* d_adv = nullptr; const u32* d_steps = nullptr; const int32_t* d_abort = nullptr;
     int counter_slot = 0;                     // where sum(adv) / sum(steps) goes in counters[]
+    // a two-pass BandEd score-only run (launch_banded_narrow): its counts, and whose verdict they feed (narrow_report)
+    const unsigned long long* d_narrow = nullptr; Context* narrow_ctx = nullptr; int narrow_cls = 0; bool narrow_probe = false;
     // kind 2
     SegList SL; AlignOut AO; std::vector<int32_t> root_status;
     std::vector<int32_t> leaf_pair; const u32* d_leaf_adv = nullptr; const u32* d_leaf_steps = nullptr;
@@ -548,7 +736,7 @@ static bool stage3_on_device(quicked_batch& B, Context& C, const TaskList& L, st
 }
 
 static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bool reversed, StageResult* R,
-                             bool fetch, int32_t** d_score_out, PendingFetch* pf = nullptr) {
+                             bool fetch, int32_t** d_score_out, PendingFetch* pf = nullptr, bool narrow_ok = false) {
     // one wavefront per alignment only where the cooperative on-chip form has no room (a band of fewer than 8 slots): with
     // G = 8 lanes per alignment and 4-slot passes that form does a 10 kb pair in 2.7 ms, the wave form in 4.3
     const bool forced = sw_set(Sw::CoopG) || sw(Sw::Wave) == 1;      // tests of the other forms
@@ -556,19 +744,49 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
     const int G0 = lg ? 1 : coop_lanes(L, fetch ? 1 : C.in_flight);
     const bool wave = !lg && wave_form_wanted(L) && (G0 < 2 || sw(Sw::Wave) == 1);
     const int G = wave ? 1 : G0;
-    const ScoreLaunch S = lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
+    // two passes (launch_banded_narrow).  QE_SCORE_NARROW = 1: wherever a task's band at half its cutoff is narrower, in the
+    // one-lane form whatever the list's size (tests); by default only where the one-lane form is the choice anyway, the list
+    // has a group per SIMD (smaller ones are one wave's serial chain, and the forms that serve them were measured at full band
+    // height), at least half of its tasks have a narrower band there, the workspace of the uniform layout is at most twice
+    // the list's own (one outlier among short reads would otherwise size every group for itself: such a list keeps the single
+    // pass, whose workspace is the sum of what the groups need), and the first pass has been paying (narrow_take)
+    const int nmode = narrow_ok ? sw(Sw::ScoreNarrow) : 0;
+    NarrowPlan np;
+    BandLayout ulay;
+    bool narrow = false, policy = false, probe = false;
+    auto fits = [&]() {
+        const BandLayout own = band_layout(L, false, false);
+        ulay = narrow_uniform(own);
+        return ulay.ws_bytes <= 2 * own.ws_bytes;
+    };
+    if (nmode == 1) { np = narrow_plan(L); narrow = np.ok && fits(); }
+    else if (nmode != 0 && !forced && !lg && !wave && G < 2 && (size_t)L.ngroups() >= (size_t)chip(C.device).simds) {
+        np = narrow_plan(L);
+        policy = np.ok && 2 * np.narrower >= np.live;
+        const int take = policy ? narrow_take(C, np.cls) : 0;
+        if (take == 1 && !fits()) policy = false;
+        narrow = policy && take == 1;
+        probe = policy && take == 2;
+    }
+    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay) :
+                          probe ? launch_banded_probe(B, C, L, reversed, 1) :
+                          lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
                           wave ? launch_banded_wave(B, C, L, reversed, 1)
                                : ((G >= 2) ? launch_banded_coop(B, C, L, reversed, G, 1) : launch_banded_score(B, C, L, reversed, 1));
     if (d_score_out) *d_score_out = S.O.score;
     if (pf && !fetch) {
         pf->kind = 1; pf->task_pair = L.pair; pf->d_score = S.O.score; pf->d_adv = S.O.adv; pf->counter_slot = 0;
-        pf->d_abort = (G >= 2) ? S.O.hew : nullptr;
+        pf->d_abort = (!narrow && !probe && G >= 2) ? S.O.hew : nullptr;
+        pf->d_narrow = S.narrow; pf->narrow_ctx = policy ? &C : nullptr; pf->narrow_cls = np.cls; pf->narrow_probe = probe;
     }
     if (fetch && R) {
         FetchBatch fb(C);
-        if (G >= 2) fb.add(R->hew, S.O.hew, S.nt);              // abort flags (diagnostics)
+        if (!narrow && !probe && G >= 2) fb.add(R->hew, S.O.hew, S.nt);              // abort flags (diagnostics)
         fb.add(R->score, S.O.score, S.nt); fb.add(R->adv, S.O.adv, S.nt);
+        if (S.narrow) fb.add(R->narrow, (const unsigned long long*)S.narrow, 4);
         fb.sync();
+        R->narrow_probe = probe;
+        if (S.narrow && policy) narrow_report(&C, np.cls, R->narrow);
     }
 }
 

@@ -181,6 +181,69 @@ struct Stage1Args {
                                   // FLAG_NONCANON leaves the list too (bit 2 of o_skip) -- its edit count is not the matrix's end value
 };
 
+// BandEd score-only in two passes (run_banded_score): a first pass of k_banded<false> at half of every
+// task's cutoff, then the full band only for the tasks whose first result proves nothing.  The cutoff a task's first pass
+// runs at: C / 2 where that band has fewer slots than the band at C, else C itself (such a task's first result is final).
+// Host and device decide with the same functions.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define QE_T_HD __host__ __device__ __forceinline__
+#else
+#define QE_T_HD inline
+#endif
+QE_T_HD int narrow_effective(int m, int n, int cutoff_in) {          // banded_matrix_allocate's clamps (band_geometry)
+    const int d = n > m ? n - m : m - n;
+    const int c = d + 1 > cutoff_in ? d + 1 : cutoff_in;
+    return c < 65 ? 65 : c;
+}
+QE_T_HD int narrow_slots(int m, int n, int cutoff_in) {
+    return ((narrow_effective(m, n, cutoff_in) + 63) >> 6) + 1;      // the score-only band (bpm_banded.c:801-803)
+}
+QE_T_HD int narrow_cutoff(int m, int n, int cutoff_in) {
+    const int half = cutoff_in / 2;
+    return narrow_slots(m, n, half) < narrow_slots(m, n, cutoff_in) ? half : cutoff_in;
+}
+// The diagonals i - j below the main one that the score-only band at this cutoff holds in EVERY column.  The band starts
+// `prolog` blocks above row 0 and moves down a block per 64 columns, so in the last column of a chunk it ends 64 (slots -
+// prolog - 1) rows below the main diagonal.  The fill's geometry has a slot more wherever the two roundings to whole blocks
+// add up to more than the rounding of the sum; the score-only one (slots = ceil(cutoff / 64) + 1) then holds fewer diagonals
+// below the corridor than Ukkonen's band for the cutoff needs (cutoff 127, m - n = -3: none at all).
+QE_T_HD int narrow_cover(int m, int n, int cutoff_in) {
+    const int ce = narrow_effective(m, n, cutoff_in), diff = m - n, ad = diff < 0 ? -diff : diff;
+    const int rel = (ce - ad + 1) / 2, prolog = (rel + (diff < 0 ? -diff : 0) + 63) / 64;
+    return 64 * (((ce + 63) >> 6) - prolog);
+}
+// A first-pass result r at cutoff c1 stands for the pass at `cutoff` when it is the cost of a path within c1 AND both bands
+// hold every diagonal a path of that cost can touch: max(0, diff) + floor((r - |diff|) / 2) below the main one (above it both
+// always do: prolog is sized for the cutoff).  Then both passes return the distance.
+QE_T_HD bool narrow_accepts(int m, int n, int c1, int cutoff_in, int r) {
+    const int diff = m - n, ad = diff < 0 ? -diff : diff;
+    if (r < ad || r > c1) return false;          // (no path costs less than |diff|; -1: the band never reached the end cell)
+    const int need = (diff > 0 ? diff : 0) + (r - ad) / 2;
+    const int a = narrow_cover(m, n, c1), b = narrow_cover(m, n, cutoff_in);
+    return need <= (a < b ? a : b);
+}
+// k_narrow, one thread per task of the list T (whole-text passes: tfin = n).  phase 0: cut1 = narrow_cutoff of every task,
+// the packed list emptied, the statistics zeroed.  phase 1, after the first pass: a task whose cutoff was halved and whose
+// score narrow_accepts() does not take is a miss; the misses go, with their original cutoffs, into the packed list q_* in dense
+// groups of 64 (order: as the waves get there; nothing depends on it), q_src = the task's index.  phase 2, after the second
+// pass over the packed list: the misses' scores replace the first pass's at q_src, their block-columns are added there.
+// phase 3, a probe of the policy (no result depends on it): T is a SAMPLE of a list that ran its single pass -- the tasks of
+// every stride-th group of 64, at halved cutoffs -- whose pass beside that launch left q_score / q_adv; score / adv and
+// main_cutoff are the whole list's.  It counts what two passes would have cost the sample (stat; [2] from what the single
+// pass did advance for the misses) and adds the sample pass's block-columns to the tasks' own (work really done).
+struct NarrowArgs {
+    int32_t phase, stride;
+    TaskView T;
+    int32_t* cut1;
+    int32_t* score;  u32* adv;                   // the list's outputs (first pass; phase 2 merges the second into them)
+    int32_t *q_pair, *q_p0, *q_m, *q_t0, *q_n, *q_cutoff, *q_tfin, *q_src;
+    const int32_t* q_score;  const u32* q_adv;   // the second pass's outputs, by packed index
+    const int32_t* main_cutoff;
+    // [0] misses  [1] block-columns the tasks with a halved cutoff advanced in the first pass  [2] block-columns of the second
+    // pass  [3] tasks with a halved cutoff
+    unsigned long long* stat;
+};
+
 // Where a stopped score-only BandEd launch left its band (what the Hirschberg join reads)
 struct BandState {
     int32_t G;     // 1: k_banded<false> layout (per 64-task group, column = lane); >= 2: k_banded_coop layout (per wave of 64/G tasks)
