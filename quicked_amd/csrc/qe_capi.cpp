@@ -336,7 +336,10 @@ QE_API quicked_status_t quicked_debug_reload_env(void) {
     qe::switches_reload();
     {   // ... and what the library has learnt under the old switches: the two-pass verdicts of every context (narrow_take)
         std::lock_guard<std::mutex> lk(qe::g_ctx_mu);
-        for (qe::Context* c : qe::g_ctx_all) for (auto& v : c->narrow_off) v = 0;
+        for (qe::Context* c : qe::g_ctx_all) {
+            for (auto& v : c->narrow_off) v = 0;
+            for (auto& ring : c->narrow_q) for (auto& v : ring) v = 0;      // ... and the fitted ratios (narrow_fit_q)
+        }
     }
     return QUICKED_OK;
 }

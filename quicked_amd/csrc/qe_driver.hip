@@ -601,7 +601,7 @@ static void stash_results(quicked_batch& B, Context& C, PendingFetch& F) {
     std::vector<StashItem> items;
     const size_t nt = F.task_pair.size(), nr = F.AO.nroots, nl = F.leaf_pair.size(), nq = F.L.pair.size();
     stash_add(items, F.d_score, nt * 4); stash_add(items, F.d_adv, nt * 4); stash_add(items, F.d_steps, nt * 4); stash_add(items, F.d_abort, nt * 4);
-    stash_add(items, F.d_narrow, 32);
+    stash_add(items, F.d_narrow, QE_NARROW_STAT * sizeof(unsigned long long));
     if (F.kind == 2) {
         stash_add(items, F.AO.len, nr * 4); stash_add(items, F.AO.edits, nr * 4); stash_add(items, F.AO.nops, nr * 4);
         stash_add(items, F.AO.ok, nr * 4); stash_add(items, F.AO.str_off, nr * 8);
@@ -1042,10 +1042,10 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
             fb.add(sc, F.d_score, nt);
             if (F.d_adv) fb.add(w, F.d_adv, nt); else if (F.d_steps) fb.add(w, F.d_steps, nt);
             if (F.d_abort) fb.add(ab, F.d_abort, nt);
-            if (F.d_narrow) fb.add(nar, F.d_narrow, 4);
+            if (F.d_narrow) fb.add(nar, F.d_narrow, QE_NARROW_STAT);
             fb.sync();
         }
-        if (F.d_narrow) { if (!F.narrow_probe) B.counters[7] = (int64_t)nar[0]; narrow_report(F.narrow_ctx, F.narrow_cls, nar); }
+        if (F.d_narrow) { if (!F.narrow_probe) B.counters[7] = (int64_t)nar[0]; narrow_report(F.narrow_ctx, F.narrow_cls, nar, F.narrow_probe); }
         for (size_t t = 0; t < nt; ++t) {
             const int pr = F.task_pair[t];
             if (pr < 0) continue;

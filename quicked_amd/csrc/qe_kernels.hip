@@ -4135,10 +4135,21 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const int nt = A.T.ntasks;
     if (A.phase == 0) {
-        if (t < 4) A.stat[t] = 0;
+        if (t < QE_NARROW_STAT) A.stat[t] = 0;
+        if (A.q <= 0) {
+            if (t >= nt) return;
+            A.q_pair[t] = -1;
+            A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+            return;
+        }
+        // the fit: this wave is the group t >> 6 of k_banded; its lanes take one slot count (the wave takes part as a whole)
+        const bool live = t < nt && A.T.pair[t] >= 0;
+        const int m = live ? A.T.m[t] : 1, n = live ? A.T.n[t] : 1, cut = live ? A.T.cutoff[t] : 0;
+        int sg = live ? narrow_fit_slots(m, n, cut, narrow_rhat(A.q, cut)) : 0;
+        for (int o = 32; o > 0; o >>= 1) sg = max(sg, __shfl_xor(sg, o));
         if (t >= nt) return;
         A.q_pair[t] = -1;
-        A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+        A.cut1[t] = live ? narrow_fit_lane(m, n, cut, A.q, sg) : A.T.cutoff[t];
         return;
     }
     if (A.phase == 1) {
@@ -4151,9 +4162,12 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
         }
         const unsigned long long a1 = wave_sum_u64(halved ? (unsigned long long)A.adv[t] : 0ull);
         const u64 mask = __ballot(miss), hmask = __ballot(halved);
+        int ratio = (halved && !miss) ? narrow_ratio(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.score[t]) : 0;
+        for (int o = 32; o > 0; o >>= 1) ratio = max(ratio, __shfl_xor(ratio, o));
         unsigned long long base = 0;
         if (lane == 0) {
             if (hmask) { atomicAdd(&A.stat[1], a1); atomicAdd(&A.stat[3], (unsigned long long)__popcll(hmask)); }
+            if (ratio > 0) atomicMax(&A.stat[4], (unsigned long long)ratio);
             if (mask) base = atomicAdd(&A.stat[0], (unsigned long long)__popcll(mask));
         }
         base = __shfl(base, 0);
@@ -4185,14 +4199,19 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
     }
     const bool mine = t < nt && (unsigned long long)t < A.stat[0];
     unsigned long long a2 = 0;
+    int ratio = -1;
     if (mine) {
         const int src = A.q_src[t];
         a2 = A.q_adv[t];
         A.score[src] = A.q_score[t];
         A.adv[src] += (u32)a2;
+        ratio = narrow_ratio(A.q_m[t], A.q_n[t], A.q_cutoff[t], A.q_score[t]);      // >= 0: a miss owed to the fit alone
     }
     a2 = wave_sum_u64(a2);
+    const u64 fmask = __ballot(ratio >= 0);
+    for (int o = 32; o > 0; o >>= 1) ratio = max(ratio, __shfl_xor(ratio, o));
     if (lane == 0 && a2) atomicAdd(&A.stat[2], a2);
+    if (lane == 0 && fmask) { atomicAdd(&A.stat[5], (unsigned long long)__popcll(fmask)); if (ratio > 0) atomicMax(&A.stat[4], (unsigned long long)ratio); }
 }
 
 // ===========================================================================

@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -108,6 +108,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::TracePool, "QE_TRACE_POOL", 0},               {Sw::OomWaitMs, "QE_OOM_WAIT_MS", 10000},
     {Sw::BoundedDiag, "QE_BOUNDED_DIAG", -1},          // bounded runs: -1 the library's choice, 0 never (general path), 1 wherever k_bounded_diag's precondition holds
     {Sw::ScoreNarrow, "QE_SCORE_NARROW", -1},          // BandEd score-only runs: -1 a first pass at half the cutoff where it pays (narrow_wanted), 0 never (the reference's band, cell for cell), 1 wherever a task's band is narrower there (tests), -2 as -1 without the policy's probes (diagnosis)
+    {Sw::NarrowFit, "QE_NARROW_FIT", -1},              // ... their first pass: -1 the fewest slots that prove the distances the class's last runs saw (narrow_fit_q), 0 always half the cutoff, k > 0 fitted to k / 1024 of every cutoff whatever ran before (tests)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {
@@ -439,6 +440,9 @@ struct Context {
     // the first pass pays or nothing is known, else 1 + the eligible runs that took the single pass since it last did not.
     // Written when a run's counts reach the host -- by whichever thread fetches it: atomics
     std::atomic<int> narrow_off[32] = {};
+    // ... and the fit of the first pass (narrow_fit_q): a ring of the ratios the class's last reported two-pass runs saw
+    std::atomic<int> narrow_q[32][16] = {};
+    std::atomic<unsigned> narrow_qn[32] = {};
     size_t seen_free = 0, seen_total = 0;    // last hipMemGetInfo reading of this device ...
     uint64_t seen_epoch = ~(uint64_t)0;      // ... and the book's epoch it was taken in
     hipStream_t& sa() { return stream_a2[ai]; }

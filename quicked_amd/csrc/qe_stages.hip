@@ -328,10 +328,27 @@ static int narrow_take(Context& C, int cls) {
     C.narrow_off[cls] = v + 1;
     return 0;
 }
-static void narrow_report(Context* C, int cls, const std::vector<unsigned long long>& st) {
-    if (!C || st.size() < 4) return;
-    const double misses = (double)st[0], a1 = (double)st[1], a2 = (double)st[2], halved = (double)st[3];
-    const bool paid = st[0] == 0 || (a1 + a2) * misses < a2 * halved;
+// The fit (qe_types.h: narrow_fit_lane): a class's q is the largest ratio of distance to cutoff that its last QE_NARROW_FIT_RUNS
+// reported two-pass runs saw (NarrowArgs::stat[4]; 0 = unknown data: half the cutoff) -- the cadence the probes have.  A run
+// whose fit caused misses reports the ratios of those too, so it has raised q for the next run; and its verdict is taken as
+// if the fit's own misses (stat[5]) had been accepted: a stale fit never sends a class to the single pass where half the
+// cutoff would have paid.  QE_NARROW_FIT = 0: never, k > 0: q = k for every list (tests).
+enum : int { QE_NARROW_FIT_RUNS = 16 };
+static int narrow_fit_q(Context& C, int cls, bool policy) {
+    const int f = sw(Sw::NarrowFit);
+    if (f >= 0) return f;
+    if (!policy) return 0;
+    int q = 0;
+    for (auto& v : C.narrow_q[cls]) q = std::max(q, v.load());
+    return q;
+}
+static void narrow_report(Context* C, int cls, const std::vector<unsigned long long>& st, bool probe) {
+    static_assert(sizeof(C->narrow_q[0]) / sizeof(C->narrow_q[0][0]) == QE_NARROW_FIT_RUNS, "the ring holds the window");
+    if (!C || st.size() < QE_NARROW_STAT) return;
+    if (!probe) C->narrow_q[cls][C->narrow_qn[cls].fetch_add(1) % QE_NARROW_FIT_RUNS] = (int)st[4];
+    const double misses = (double)(st[0] - st[5]), a1 = (double)st[1], halved = (double)st[3];
+    const double a2 = st[0] ? (double)st[2] * misses / (double)st[0] : 0.0;
+    const bool paid = st[0] == st[5] || (a1 + a2) * misses < a2 * halved;
     int unknown = 0;
     if (paid) C->narrow_off[cls] = 0; else C->narrow_off[cls].compare_exchange_strong(unknown, 1);
 }
@@ -341,22 +358,35 @@ static void narrow_report(Context* C, int cls, const std::vector<unsigned long l
 static void k_narrow(NarrowArgs A) {
     const int nt = A.T.ntasks;
     if (A.phase == 0) {
-        for (int q = 0; q < 4; ++q) A.stat[q] = 0;
-        for (int t = 0; t < nt; ++t) {
-            A.q_pair[t] = -1;
-            A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+        for (int q = 0; q < QE_NARROW_STAT; ++q) A.stat[q] = 0;
+        for (int g = 0; g < nt; g += 64) {
+            int sg = 0;
+            if (A.q > 0)
+                for (int t = g; t < std::min(nt, g + 64); ++t)
+                    if (A.T.pair[t] >= 0) sg = std::max(sg, narrow_fit_slots(A.T.m[t], A.T.n[t], A.T.cutoff[t], narrow_rhat(A.q, A.T.cutoff[t])));
+            for (int t = g; t < std::min(nt, g + 64); ++t) {
+                A.q_pair[t] = -1;
+                A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_fit_lane(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.q, sg) : A.T.cutoff[t];
+            }
         }
     } else if (A.phase == 1) {
         for (int t = 0; t < nt; ++t) {
             if (A.T.pair[t] < 0 || A.cut1[t] == A.T.cutoff[t]) continue;
             A.stat[1] += A.adv[t]; ++A.stat[3];
-            if (narrow_accepts(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.score[t])) continue;
+            if (narrow_accepts(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.score[t])) {
+                A.stat[4] = std::max(A.stat[4], (unsigned long long)std::max(0, narrow_ratio(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.score[t])));
+                continue;
+            }
             const int j = (int)A.stat[0]++;
             A.q_pair[j] = A.T.pair[t]; A.q_p0[j] = A.T.p0[t]; A.q_m[j] = A.T.m[t]; A.q_t0[j] = A.T.t0[t]; A.q_n[j] = A.T.n[t];
             A.q_cutoff[j] = A.T.cutoff[t]; A.q_tfin[j] = A.T.tfin[t]; A.q_src[j] = t;
         }
     } else if (A.phase == 2) {
-        for (int j = 0; j < (int)A.stat[0]; ++j) { A.score[A.q_src[j]] = A.q_score[j]; A.adv[A.q_src[j]] += A.q_adv[j]; A.stat[2] += A.q_adv[j]; }
+        for (int j = 0; j < (int)A.stat[0]; ++j) {
+            A.score[A.q_src[j]] = A.q_score[j]; A.adv[A.q_src[j]] += A.q_adv[j]; A.stat[2] += A.q_adv[j];
+            const int ratio = narrow_ratio(A.q_m[j], A.q_n[j], A.q_cutoff[j], A.q_score[j]);
+            if (ratio >= 0) { ++A.stat[5]; A.stat[4] = std::max(A.stat[4], (unsigned long long)ratio); }
+        }
     } else {
         for (int t = 0; t < nt; ++t) {
             if (A.T.pair[t] < 0) continue;
@@ -403,9 +433,9 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
     P.T = upload_tasks(Ls, C);
     P.D = upload_layout(lays, C);
     P.O = take_out(C, P.nt);
-    S.narrow = C.scratch_p->take<unsigned long long>(4);
+    S.narrow = C.scratch_p->take<unsigned long long>(QE_NARROW_STAT);
     S.narrow_probe = true;
-    HIP_CHECK(hipMemsetAsync(S.narrow, 0, 4 * sizeof(unsigned long long), C.stream));
+    HIP_CHECK(hipMemsetAsync(S.narrow, 0, QE_NARROW_STAT * sizeof(unsigned long long), C.stream));
     hipStream_t main_s = C.stream, side = C.side_stream();
     HIP_CHECK(hipEventRecord(C.ev_fork, main_s)); HIP_CHECK(hipStreamWaitEvent(side, C.ev_fork, 0));
     BandedArgs a = score_args(B, S, reversed);
@@ -428,7 +458,7 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
     return S;
 }
 
-static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay) {
+static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q) {
     ScoreLaunch S;
     S.nt = L.pair.size();
     const size_t nt = S.nt;
@@ -438,12 +468,12 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     ScoreLaunch S2 = S;                              // the packed list of the misses, its outputs; the same workspace
     S2.O = take_out(C, nt);
     int32_t* blk = C.scratch_p->take<int32_t>(9 * nt);
-    S.narrow = C.scratch_p->take<unsigned long long>(4);
+    S.narrow = C.scratch_p->take<unsigned long long>(QE_NARROW_STAT);
     NarrowArgs x{};
     x.T = S.T.v; x.cut1 = blk; x.score = S.O.score; x.adv = S.O.adv;
     x.q_pair = blk + nt; x.q_p0 = blk + 2 * nt; x.q_m = blk + 3 * nt; x.q_t0 = blk + 4 * nt; x.q_n = blk + 5 * nt;
     x.q_cutoff = blk + 6 * nt; x.q_tfin = blk + 7 * nt; x.q_src = blk + 8 * nt;
-    x.q_score = S2.O.score; x.q_adv = S2.O.adv; x.stat = S.narrow;
+    x.q_score = S2.O.score; x.q_adv = S2.O.adv; x.stat = S.narrow; x.q = q;
     S2.T.v.pair = x.q_pair; S2.T.v.p0 = x.q_p0; S2.T.v.m = x.q_m; S2.T.v.t0 = x.q_t0; S2.T.v.n = x.q_n;
     S2.T.v.cutoff = x.q_cutoff; S2.T.v.tfin = x.q_tfin;
     const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
@@ -768,7 +798,7 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
         narrow = policy && take == 1;
         probe = policy && take == 2;
     }
-    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay) :
+    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay, narrow_fit_q(C, np.cls, policy)) :
                           probe ? launch_banded_probe(B, C, L, reversed, 1) :
                           lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
                           wave ? launch_banded_wave(B, C, L, reversed, 1)
@@ -783,10 +813,10 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
         FetchBatch fb(C);
         if (!narrow && !probe && G >= 2) fb.add(R->hew, S.O.hew, S.nt);              // abort flags (diagnostics)
         fb.add(R->score, S.O.score, S.nt); fb.add(R->adv, S.O.adv, S.nt);
-        if (S.narrow) fb.add(R->narrow, (const unsigned long long*)S.narrow, 4);
+        if (S.narrow) fb.add(R->narrow, (const unsigned long long*)S.narrow, QE_NARROW_STAT);
         fb.sync();
         R->narrow_probe = probe;
-        if (S.narrow && policy) narrow_report(&C, np.cls, R->narrow);
+        if (S.narrow && policy) narrow_report(&C, np.cls, R->narrow, probe);
     }
 }
 

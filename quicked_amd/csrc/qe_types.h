@@ -222,6 +222,61 @@ QE_T_HD bool narrow_accepts(int m, int n, int c1, int cutoff_in, int r) {
     const int a = narrow_cover(m, n, c1), b = narrow_cover(m, n, cutoff_in);
     return need <= (a < b ? a : b);
 }
+// The fit: narrow_accepts() holds for ANY first-pass cutoff c1, so where the distances of a stream are known
+// -- as a ratio q of distance to cutoff in 1/1024ths -- the first pass takes the band of the fewest slots that still proves
+// them instead of the band at half the cutoff.  r_hat = the result the fit is made for.
+QE_T_HD int narrow_rhat(int q, int cutoff_in) { return (int)(((long long)q * cutoff_in + 1023) >> 10); }
+// the largest result narrow_accepts(m, n, c1, cutoff_in, .) takes, -1 if it takes none
+QE_T_HD int narrow_room(int m, int n, int c1, int cutoff_in) {
+    const int diff = m - n, ad = diff < 0 ? -diff : diff;
+    const int a = narrow_cover(m, n, c1), b = narrow_cover(m, n, cutoff_in);
+    const int k = (a < b ? a : b) - (diff > 0 ? diff : 0);
+    if (k < 0 || c1 < ad) return -1;
+    const int r = ad + 2 * k + 1;
+    return r < c1 ? r : c1;
+}
+// The candidates of the fit are the cutoffs c = narrow_effective(m, n, c) below cutoff_in whose band has fewer slots than the
+// band at cutoff_in (a cutoff under the floor max(|m - n| + 1, 65) walks the floor's band and only accepts less).
+// -> the least slot count among the candidates c >= r_hat that accept r_hat; 0: there is none
+QE_T_HD int narrow_fit_slots(int m, int n, int cutoff_in, int r_hat) {
+    const int diff = m - n, ad = diff < 0 ? -diff : diff;
+    if (r_hat < ad) return 0;                                                // (no cutoff accepts it)
+    if ((diff > 0 ? diff : 0) + (r_hat - ad) / 2 > narrow_cover(m, n, cutoff_in)) return 0;
+    const int full = narrow_slots(m, n, cutoff_in), floor_c = narrow_effective(m, n, 0);
+    for (int c = r_hat > floor_c ? r_hat : floor_c; c < cutoff_in; ++c) {
+        const int s = ((c + 63) >> 6) + 1;
+        if (s >= full) return 0;
+        if (narrow_accepts(m, n, c, cutoff_in, r_hat)) return s;
+    }
+    return 0;
+}
+// -> among the candidates of exactly s slots (at most 64 cutoffs) the one that accepts the largest result, the smallest such;
+// 0: no candidate has s slots.  This choice is the fit's margin: a lane gets all the room its slot count holds.
+QE_T_HD int narrow_fit_cutoff(int m, int n, int cutoff_in, int s) {
+    const int floor_c = narrow_effective(m, n, 0), hi = 64 * (s - 1) < cutoff_in - 1 ? 64 * (s - 1) : cutoff_in - 1;
+    int c = 64 * (s - 2) + 1, best = 0, room = -2;
+    if (s >= narrow_slots(m, n, cutoff_in)) return 0;
+    for (c = c > floor_c ? c : floor_c; c <= hi; ++c) {
+        const int r = narrow_room(m, n, c, cutoff_in);
+        if (r > room) { room = r; best = c; }
+    }
+    return best;
+}
+// The cutoff of a lane whose group of 64 walks s_g slots (the largest narrow_fit_slots of its lanes that have one): the fitted
+// one where that band is lower than the band at half the cutoff and proves the lane's own r_hat, else narrow_cutoff as ever.
+QE_T_HD int narrow_fit_lane(int m, int n, int cutoff_in, int q, int s_g) {
+    const int half = narrow_cutoff(m, n, cutoff_in);
+    if (s_g <= 0 || s_g >= narrow_slots(m, n, half)) return half;
+    const int c = narrow_fit_cutoff(m, n, cutoff_in, s_g);
+    return (c > 0 && narrow_accepts(m, n, c, cutoff_in, narrow_rhat(q, cutoff_in))) ? c : half;
+}
+// what a run reports of a task with a lowered cutoff and the final score r: ceil(1024 r / cutoff) where the pass at
+// narrow_cutoff would have accepted r (the ratio the next fit is made from), else -1
+QE_T_HD int narrow_ratio(int m, int n, int cutoff_in, int r) {
+    if (!narrow_accepts(m, n, narrow_cutoff(m, n, cutoff_in), cutoff_in, r)) return -1;
+    return (int)(((long long)r * 1024 + cutoff_in - 1) / cutoff_in);
+}
+
 // k_narrow, one thread per task of the list T (whole-text passes: tfin = n).  phase 0: cut1 = narrow_cutoff of every task,
 // the packed list emptied, the statistics zeroed.  phase 1, after the first pass: a task whose cutoff was halved and whose
 // score narrow_accepts() does not take is a miss; the misses go, with their original cutoffs, into the packed list q_* in dense
@@ -231,8 +286,11 @@ QE_T_HD bool narrow_accepts(int m, int n, int c1, int cutoff_in, int r) {
 // every stride-th group of 64, at halved cutoffs -- whose pass beside that launch left q_score / q_adv; score / adv and
 // main_cutoff are the whole list's.  It counts what two passes would have cost the sample (stat; [2] from what the single
 // pass did advance for the misses) and adds the sample pass's block-columns to the tasks' own (work really done).
+// With q > 0 (the fit, see above) phase 0 works per group of 64 tasks = one wave of k_banded: s_g = the largest narrow_fit_slots
+// of the group's live lanes that have one, cut1 = narrow_fit_lane(.., q, s_g); q = 0 is narrow_cutoff for every task.
+enum : int { QE_NARROW_STAT = 6 };               // words of NarrowArgs::stat
 struct NarrowArgs {
-    int32_t phase, stride;
+    int32_t phase, stride, q;
     TaskView T;
     int32_t* cut1;
     int32_t* score;  u32* adv;                   // the list's outputs (first pass; phase 2 merges the second into them)
@@ -240,7 +298,8 @@ struct NarrowArgs {
     const int32_t* q_score;  const u32* q_adv;   // the second pass's outputs, by packed index
     const int32_t* main_cutoff;
     // [0] misses  [1] block-columns the tasks with a halved cutoff advanced in the first pass  [2] block-columns of the second
-    // pass  [3] tasks with a halved cutoff
+    // pass  [3] tasks with a halved cutoff  [4] the largest narrow_ratio() of the lowered tasks' final scores (phases 1 and 2)
+    // [5] the misses among them that the pass at narrow_cutoff would have accepted: the misses owed to the fit alone
     unsigned long long* stat;
 };
 

@@ -12,6 +12,12 @@ the default switch:
     steady state    rounds of `steps` queued runs, this tree and the parent alternating round by round (--only this / parent:
                     one library per process, for alternating processes); with the default 16 steps a round holds exactly
                     one probe once the policy has left the first pass (--steady-switch 0 / -2: none)
+    --reseed K      real use instead of one replayed batch: K resident batches per error rate, every one of another seed,
+                    rotated, every run queued and fetched one run behind (so the policy and the fit see every run's counts);
+                    --schedule 0.05:12,0.06:8,0.05:8 shifts the error rate in the stream.  One library per process
+                    (--lib <libquicked_hip.so of the parent> for the baseline).  Reports every run's ms (fetch to fetch),
+                    block-columns and second-pass tasks, the steps after each shift included, and min / median / max per
+                    segment without its first two runs (the pipeline's fill and the run after a shift are listed, not hidden)
 min / median / max of the ms per run over the rounds; counters[0] (block-columns advanced) and counters[7] (tasks of the
 second pass) of a synchronous run after the rounds show what the policy settled on.  Scores must equal the parent's.
 """
@@ -29,6 +35,78 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 def stats(v):
     return dict(min=round(min(v), 4), median=round(statistics.median(v), 4), max=round(max(v), 4), samples=[round(x, 4) for x in v])
+
+
+def reseeded(args):
+    if args.lib:
+        os.environ["QUICKED_HIP_LIB"] = os.path.abspath(args.lib)
+    if args.steady_switch is not None:
+        os.environ["QE_SCORE_NARROW"] = args.steady_switch
+    from quicked_amd import capi, datagen
+    sched = [(float(e), int(n)) for e, n in (x.split(":") for x in (args.schedule or "%g:24" % args.error).split(","))]
+    params = capi.make_params(algo=capi.BANDED, only_score=True, bandwidth=args.bandwidth)
+    rbs, checks = {}, {}
+    for e in sorted({e for e, _ in sched}):
+        for i in range(args.reseed):
+            seed = args.seed + 1000 * int(round(e * 1000)) + i
+            rbs[(e, i)] = capi.ResidentBatch(datagen.generate(args.count, args.length, e, seed=seed))
+    # warm-up with the switch forced both ways on every batch (pools, code objects; the policy learns nothing from forced runs) ...
+    for v in ("1", "0"):
+        os.environ["QE_SCORE_NARROW"] = v
+        capi.reload_env()
+        for key, rb in rbs.items():
+            if rb.run(params, sync=False) < 0 or rb.fetch() < 0:
+                raise RuntimeError("warm-up run failed")
+            if v == "0":
+                checks[key] = rb.scores()[0].copy()               # the single pass's scores
+    if args.steady_switch is None:
+        os.environ.pop("QE_SCORE_NARROW", None)
+    else:
+        os.environ["QE_SCORE_NARROW"] = args.steady_switch
+    capi.reload_env()                                             # ... and the stream starts from unknown data
+    runs, prev, k = [], None, 0
+    host_ms = []
+
+    def finish(item):
+        key, rb, seg = item
+        if rb.fetch() < 0:
+            raise RuntimeError("quicked_batch_fetch failed")
+        c = rb.counters()
+        assert (rb.scores()[0] == checks[key]).all(), "scores differ from the single pass's"
+        runs.append(dict(segment=seg, error=key[0], batch=key[1], t=time.perf_counter(), block_columns=int(c[0]), second_pass_tasks=int(c[7])))
+
+    t_start = time.perf_counter()
+    for seg, (e, n) in enumerate(sched):
+        for _ in range(n):
+            key = (e, k % args.reseed)
+            k += 1
+            th = time.perf_counter()
+            if rbs[key].run(params, sync=False) < 0:
+                raise RuntimeError("quicked_batch_run failed")
+            host_ms.append((time.perf_counter() - th) * 1e3)
+            if prev:
+                finish(prev)
+            prev = (key, rbs[key], seg)
+    finish(prev)
+    last = t_start
+    for r in runs:
+        r["ms"] = round((r["t"] - last) * 1e3, 4)
+        last = r.pop("t")
+    out = dict(mode="reseeded", lib=os.environ.get("QUICKED_HIP_LIB", "this tree"), pairs=args.count, length=args.length,
+               batches_per_error=args.reseed, schedule=sched, bandwidth=args.bandwidth, unit="ms per run (fetch to fetch)",
+               host_ms_per_queued_run=stats(host_ms), runs=runs, segments=[])
+    for seg, (e, n) in enumerate(sched):
+        mine = [r for r in runs if r["segment"] == seg]
+        out["segments"].append(dict(error=e, runs=n, ms_without_first_two=stats([r["ms"] for r in mine[2:]]) if len(mine) > 2 else None,
+                                    ms_first_two=[r["ms"] for r in mine[:2]], second_pass_tasks=[r["second_pass_tasks"] for r in mine],
+                                    block_columns_last=mine[-1]["block_columns"]))
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    for rb in rbs.values():
+        rb.close()
 
 
 def main():
@@ -49,10 +127,15 @@ def main():
     ap.add_argument("--cold-queued", action="store_true",
                     help="also: rounds of queued runs that start from unknown data and are never fetched -- the verdict is taken "
                          "when a run's counts reach the host, so such a stream keeps the first pass")
+    ap.add_argument("--reseed", type=int, default=0, help="K > 0: a stream over K resident batches of different seeds per error rate")
+    ap.add_argument("--schedule", default=None, help="with --reseed: error:runs,error:runs,... (default: --error for 24 runs)")
+    ap.add_argument("--lib", default=None, help="with --reseed: the libquicked_hip.so to time (default: this tree's)")
     ap.add_argument("--out")
     args = ap.parse_args()
     os.environ.pop("QE_SCORE_NARROW", None)
     os.environ.pop("QUICKED_HIP_LIB", None)
+    if args.reseed > 0:
+        return reseeded(args)
 
     from bounded_bench import load_package
     from quicked_amd import capi, datagen
