@@ -385,21 +385,23 @@ __device__ __forceinline__ void run64_skew_fill(u64 (&P)[K], u64 (&M)[K], const 
 }
 
 // K adjacent band slots i .. i+K-1 of one chunk in one pass, with the loads, score bookkeeping and the in-place band
-// shift around it.  scores[] of the lowest row from its own bottom-row deltas, as always; of every row above from
+// shift around it.  A lane takes part with its nl live slots i .. i+nl-1 (0 .. K; qe_types.h: pass_plan): the slots below
+// them are never loaded or stored and compute on P = M = a = b = 0, which cannot reach the live ones (carries flow from slot
+// k to k + 1 only) and leaves the score rule below as it is.  scores[] of the lowest row from its own bottom-row deltas, as always; of every row above from
 //   sum_c hout_k(c) = sum_c hin_(k+1)(c) = sum_c hout_(k+1)(c) - (v_(k+1) after - v_(k+1) before),
 // v = sum of a block's vertical deltas -- exact for any block state, because every cell of the step satisfies
 // v' - v = h - h_above (the step evaluates the min-recurrence cell by cell).
 template <int K>
 // `stride` = elements between consecutive slots / rows of one lane's state (64 in k_banded's layout, the tasks per wave in
 // k_banded_coop's); scores[] is read from Srd and written to Swr (the cooperative kernel double-buffers it by chunk parity)
-__device__ __forceinline__ void slots_pass(bool act, int i, int r, u64* Pv, u64* Mv, const int32_t* Srd, int32_t* Swr, int64_t stride,
+__device__ __forceinline__ void slots_pass(int nl, int i, int r, u64* Pv, u64* Mv, const int32_t* Srd, int32_t* Swr, int64_t stride,
                                            const u64* pp, int p0, u64 T0, u64 T1, u64& hinP, u64& hinM, u32& adv) {
     u64 P[K], M[K], a[K], b[K];
     int sc[K], v0[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         P[k] = 0; M[k] = 0; a[k] = 0; b[k] = 0; sc[k] = 0;
-        if (act) {
+        if (k < nl) {
             u64 nn;
             P[k] = Pv[(int64_t)(i + k) * stride]; M[k] = Mv[(int64_t)(i + k) * stride]; sc[k] = Srd[(int64_t)(r + k) * stride];
             load_planes(pp, p0 + 64 * (r + k), a[k], b[k], nn);
@@ -408,15 +410,17 @@ __device__ __forceinline__ void slots_pass(bool act, int i, int r, u64* Pv, u64*
     }
     u64 houtP, houtM;
     run64_skew<K>(P, M, a, b, T0, T1, hinP, hinM, houtP, houtM);
-    if (act) {
+    if (nl > 0) {
         int d = __popcll(houtP) - __popcll(houtM);          // sum of the bottom-row deltas of slot k, from the lowest up
 #pragma unroll
         for (int k = K - 1; k >= 0; --k) {
-            Swr[(int64_t)(r + k) * stride] = sc[k] + d;
+            if (k < nl) {
+                Swr[(int64_t)(r + k) * stride] = sc[k] + d;
+                Pv[(int64_t)(i + k - 1) * stride] = P[k]; Mv[(int64_t)(i + k - 1) * stride] = M[k];   // band shift (bpm_banded.c:903-909)
+            }
             d -= (__popcll(P[k]) - __popcll(M[k])) - v0[k];
-            Pv[(int64_t)(i + k - 1) * stride] = P[k]; Mv[(int64_t)(i + k - 1) * stride] = M[k];   // band shift (bpm_banded.c:903-909)
         }
-        adv += 64u * K;
+        adv += 64u * (u32)nl;
     }
     hinP = houtP; hinM = houtM;
 }
@@ -985,17 +989,19 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             const bool act = on && i >= first && i <= rhi;
             const int r = i + pos_v;
             if (!FILL) {
-                // K slots in one pass when every lane has all of them or none, full ACGT chunks, not the last block row
+                // K slots in one pass, every lane with the slots of it that lie in its band (pass_plan: a prefix of the pass;
+                // score_masked = 0: all of them or none), full ACGT chunks, not the last block row
                 const int lo = on ? first : 0x7fffffff, hi_ = on ? rhi : -0x7fffffff;
                 const bool plain = !(on && (ncols != 64 || hasN));
-                auto uniform = [&](int K) {
-                    const bool all = i >= lo && i + K - 1 <= hi_, none = i + K - 1 < lo || i > hi_;
-                    const bool bad = !(all || none) || (all && (!plain || r + K - 1 >= nw - 1));
+                int nl = 0;
+                auto planned = [&](int K) {
+                    bool bad;
+                    nl = pass_plan(i, K, lo, hi_, r, nw, plain, A.score_masked != 0, bad);
                     return !__any(bad);
                 };
                 if (i == first) { hinP = QE_ONES; hinM = 0; }
-                if (x + 3 <= i1 && uniform(4)) { slots_pass<4>(act, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
-                if (x + 1 <= i1 && uniform(2)) { slots_pass<2>(act, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
+                if (x + 3 <= i1 && planned(4)) { slots_pass<4>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
+                if (x + 1 <= i1 && planned(2)) { slots_pass<2>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
             }
             if (FILL && QE_FILL_K > 1 && A.fill_multi && x + QE_FILL_K - 1 <= i1) {
                 // K slots in one skewed pass, every lane with the slots inside its own band, unless a lane needs the
@@ -1325,14 +1331,14 @@ __global__ __launch_bounds__(512) void k_banded_coop(CoopArgs A) {
                 };
                 const bool all4 = mine && i + 3 <= hi_m, all2 = mine && i + 1 <= hi_m;
                 if (it + 3 < maxit && uniform(4)) {
-                    slots_pass<4>(all4, i, r, Pv, Mv, Srd, Swr, NA, pp, p0, T0, T1, hinP, hinM, adv);
+                    slots_pass<4>(all4 ? 4 : 0, i, r, Pv, Mv, Srd, Swr, NA, pp, p0, T0, T1, hinP, hinM, adv);
                     if (all4) { lastP = hinP; lastM = hinM; }
                     it += 3;
                     QE_COOP_FENCE();
                     continue;
                 }
                 if (it + 1 < maxit && uniform(2)) {
-                    slots_pass<2>(all2, i, r, Pv, Mv, Srd, Swr, NA, pp, p0, T0, T1, hinP, hinM, adv);
+                    slots_pass<2>(all2 ? 2 : 0, i, r, Pv, Mv, Srd, Swr, NA, pp, p0, T0, T1, hinP, hinM, adv);
                     if (all2) { lastP = hinP; lastM = hinM; }
                     it += 1;
                     QE_COOP_FENCE();

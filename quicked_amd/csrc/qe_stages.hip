@@ -253,9 +253,11 @@ static BandState band_state(const ScoreLaunch& S) {
 }
 
 // What every BandEd score-only launch passes alike: the pairs, the list, its group workspace (null where it has none) and the
-// outputs (O.len doubles as maxrow).  Every other field keeps BandedArgs' default (fill_multi = lane_rel = 1) or is 0 / null.
+// outputs (O.len doubles as maxrow) and the pass rule of k_banded<false>.  Every other field keeps BandedArgs' default
+// (fill_multi = lane_rel = 1) or is 0 / null.
 static BandedArgs score_args(const quicked_batch& B, const ScoreLaunch& S, bool reversed) {
     BandedArgs a{};
+    a.score_masked = sw(Sw::ScoreMasked);
     a.P = pair_view(B, reversed); a.T = S.T.v;
     a.ws = S.D.ws; a.g_ws_off = S.D.ws_off; a.g_nslots = S.D.nslots; a.g_nrows = S.D.nrows; a.g_nch = S.D.nch;
     a.g_mat_off = S.D.mat_off;

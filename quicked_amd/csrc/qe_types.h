@@ -83,6 +83,7 @@ struct BandedArgs {
     const int32_t* only_if;  // run only tasks whose flag is non-zero (fallback pass after k_banded_coop); may be null
     int32_t fill_multi = 1;  // fill: K-slot skewed passes where no lane needs the general form (0: single-slot passes only; tests)
     int32_t lane_rel = 1;    // every lane walks ITS band (slot first + j at step j of a chunk) instead of the wave walking the union of its lanes' bands (0: tests)
+    int32_t score_masked = 1;     // k_banded<false>: a lane joins a multi-slot pass with the slots of it that are in its band (pass_plan; 0: all of them or none)
     int32_t* o_abort = nullptr;   // k_banded_sys: 1 where a task is left to k_banded<true> (N in the pair, a band of more than 15 slots)
     int32_t doubling = 0;         // k_banded_sys<.., false>: QuickEd's stage-3 band doubling in the launch (quicked.c:248-278)
     int32_t* o_cutoff = nullptr;  // ... the cutoff of every task's last pass (or, flagged, of the pass it was handed back before)
@@ -275,6 +276,27 @@ QE_T_HD int narrow_fit_lane(int m, int n, int cutoff_in, int q, int s_g) {
 QE_T_HD int narrow_ratio(int m, int n, int cutoff_in, int r) {
     if (!narrow_accepts(m, n, narrow_cutoff(m, n, cutoff_in), cutoff_in, r)) return -1;
     return (int)(((long long)r * 1024 + cutoff_in - 1) / cutoff_in);
+}
+
+// The pass plan of k_banded<false> ("Masked passes"): the part one lane takes in a K-slot pass over the slots
+// i .. i + K - 1 of a chunk.  lo .. hi are the band slots the lane computes in this chunk (first .. min(last, nw - 1 - pos_v);
+// lo > hi for a lane without columns here), r = the block row of slot i, nw = the pattern's block rows, plain = a full chunk
+// of 64 columns of a pair without N.  -> nl, the lane's live slots: i .. i + nl - 1, always a prefix of the pass (the slots
+// below them compute on zeros and are never loaded or stored: carries only flow downwards).  `fallback` = the wave must not
+// take this pass because of this lane: its live slots start inside the pass (the slots above them would feed the band's top
+// slot, whose carry-in is (1, 0)) or one of them needs the general form (partial chunk, N, the pattern's last block row).
+// The wave takes the pass when no lane says fallback.  masked = false is the all-or-none rule: a lane has all K slots or
+// none of them, anything else is a fallback.
+QE_T_HD int pass_plan(int i, int K, int lo, int hi, int r, int nw, bool plain, bool masked, bool& fallback) {
+    if (!masked) {
+        const bool all = i >= lo && i + K - 1 <= hi, none = i + K - 1 < lo || i > hi;
+        fallback = !(all || none) || (all && (!plain || r + K - 1 >= nw - 1));
+        return all ? K : 0;
+    }
+    const int a0 = i > lo ? i : lo, a1 = i + K - 1 < hi ? i + K - 1 : hi;
+    const int nl = a1 >= a0 ? a1 - a0 + 1 : 0;
+    fallback = nl > 0 && (a0 != i || !plain || r + nl - 1 >= nw - 1);
+    return nl;
 }
 
 // k_narrow, one thread per task of the list T (whole-text passes: tfin = n).  phase 0: cut1 = narrow_cutoff of every task,
