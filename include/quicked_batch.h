@@ -156,6 +156,46 @@ quicked_status_t quicked_batch_cigar_view(quicked_batch_t* batch, const char** c
  *              (1 valid, 0 not, -1 the pair has no alignment) after a sync != 0 run. */
 quicked_status_t quicked_batch_configure(quicked_batch_t* batch, int cigar_style, int check);
 quicked_status_t quicked_batch_check_results(quicked_batch_t* batch, int32_t* ok_out);
+/* ---- alignment tags: what a consumer of alignments wants besides, or instead of, the CIGAR strings ----
+ * Identity, gap counts and the longest exact stretch per pair cost 32 bytes of D2H per pair; the strings of a 10 kb pair
+ * about 2 kB (at 5 % error).  Computed on the device from the traceback's runs.
+ *   QUICKED_TAG_STATS     a quicked_pair_stats_t per pair
+ *   QUICKED_TAG_MD        the SAM MD:Z string per pair.  (NM is the score: there is no getter of its own.)
+ *   QUICKED_TAG_NO_CIGAR  the run aligns -- traceback and all -- but formats and downloads no CIGAR strings: cigar_off is -1
+ *                         for every pair and quicked_batch_cigar_bytes 0, scores and statuses are those of the CIGAR run,
+ *                         the in-run validator gives -1 for every pair
+ * Which runs: those that produce alignments -- only_score == 0 -- through quicked_batch_run with every algo and through
+ * quicked_batch_run_bounded.  The default is 0, and then nothing about a run changes: no extra launch, allocation or copy.
+ * The per-pair ABI (quicked_align) and quicked_align_batch never set tags.
+ * Where the results are: in the getters below after a sync != 0 run.  A sync == 0 run with only_score == 0 on a batch whose
+ * tags are not 0 returns QUICKED_UNIMPLEMENTED and queues nothing (as a queued bounded CIGAR run); queued only_score != 0
+ * runs ignore the tags.  After a run that produced no tag data (tags 0, or only_score != 0) the getters return
+ * QUICKED_ERROR, as quicked_batch_check_results does; so do a NULL batch and unknown bits.
+ * Packed batches: STATS and NO_CIGAR work (they need no bases); QUICKED_TAG_MD returns QUICKED_UNIMPLEMENTED from
+ * quicked_batch_configure_tags, as the validator does.
+ * Pairs without an alignment -- empty sequences, a run-buffer overflow (score -1, QUICKED_ERROR), "beyond" in a bounded run --
+ * get statistics of all -1 and md_off -1.
+ *
+ * Both are functions of the alignment's operation sequence -- what the style-0 CIGAR expands to, whatever style is
+ * configured; I consumes text, D consumes pattern -- with runs maximal (equal neighbours merged), and of the pattern's raw bytes.
+ * Statistics: the M / X / I / D columns, the numbers of maximal I and D runs, the longest maximal M run, all columns; hence
+ *   matches + mismatches + del_bases == pattern_len,  matches + mismatches + ins_bases == text_len,
+ *   mismatches + ins_bases + del_bases == score.
+ * MD is over the sequence D consumes: in the SAM styles this library prints I consumes the text, so the text is SAM's query
+ * and the PATTERN is SAM's reference: MD names pattern bytes, raw as stored, no case folding.  A number of matches, then per
+ * mismatch the pattern byte (neighbouring mismatches separated by "0"), per deletion run '^' and its pattern bytes; an
+ * insertion emits nothing and does not reset the count, but separates two deletion runs ("^AC0^GT"); the count at the end.
+ * quicked_batch_md_bytes / quicked_batch_md: pool and offsets laid out like the CIGAR getters' (NUL-terminated strings,
+ * md_off[i] -1: none). */
+enum { QUICKED_TAG_STATS = 1, QUICKED_TAG_MD = 2, QUICKED_TAG_NO_CIGAR = 4 };
+typedef struct {            /* 32 bytes; all -1 for a pair without an alignment */
+    int32_t matches, mismatches, ins_bases, del_bases, ins_runs, del_runs, longest_match, columns;
+} quicked_pair_stats_t;
+quicked_status_t quicked_batch_configure_tags(quicked_batch_t* batch, int tags);
+quicked_status_t quicked_batch_pair_stats(quicked_batch_t* batch, quicked_pair_stats_t* stats_out /* n */);
+int64_t          quicked_batch_md_bytes(quicked_batch_t* batch);
+quicked_status_t quicked_batch_md(quicked_batch_t* batch, char* md_pool, int64_t* md_off);   /* md_off -1: none */
+
 /* The same validator for CIGAR strings from anywhere ("<len><op>", op in MXID, '=' read as M): string i is
  * cigar_pool + cigar_off[i], NUL-terminated, against the batch's resident pair i; cigar_off[i] < 0 -> -1.
  * What `align_benchmark -c correct` does per pair on the host (benchmark_check.c), at batch scale. */

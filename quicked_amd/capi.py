@@ -59,7 +59,10 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_wire_words", "quicked_wire_pack", "quicked_batch_create_packed",
            "quicked_batch_reload", "quicked_batch_reload_packed", "quicked_batch_fetch", "quicked_pool_stats", "quicked_batch_cigar_view",
            "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats",
-           "quicked_batch_run_bounded"]
+           "quicked_batch_run_bounded",
+           "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
+
+TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
 
 _LIB = None
 
@@ -113,6 +116,12 @@ def lib():
     L.quicked_batch_configure.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.quicked_batch_check_results.argtypes = [C.c_void_p, C.c_void_p]
     L.quicked_batch_validate.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.quicked_batch_configure_tags.argtypes = [C.c_void_p, C.c_int]
+    L.quicked_batch_pair_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.quicked_batch_md_bytes.restype = C.c_int64
+    L.quicked_batch_md_bytes.argtypes = [C.c_void_p]
+    L.quicked_batch_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_debug_tag_launches.argtypes = [C.c_void_p]
     L.quicked_wire_words.restype = C.c_int64
     L.quicked_wire_words.argtypes = [C.c_int32, C.c_int]
     L.quicked_wire_pack.argtypes = [C.c_char_p, C.c_int32, C.c_int, C.c_void_p]
@@ -146,6 +155,13 @@ def reload_env():
     have it parsed again.  No-op while the library is not loaded (its first use parses the environment as it is then)."""
     if _LIB is not None and hasattr(_LIB, "quicked_debug_reload_env"):
         _LIB.quicked_debug_reload_env()
+
+
+def tag_launches():
+    """count passes of the alignment-tag kernels launched by this process so far -> (lane form, wave form); a test hook"""
+    v = np.zeros(2, dtype=np.int64)
+    lib().quicked_debug_tag_launches(v.ctypes.data)
+    return int(v[0]), int(v[1])
 
 
 def pool_trim():
@@ -350,6 +366,33 @@ class ResidentBatch:
     def configure(self, cigar_style=0, check=False):
         """cigar_style 0 = reference RLE "MXID", 1 = SAM "=XID", 2 = SAM "MID"; check = device-side validator"""
         return self._lib.quicked_batch_configure(self._h, cigar_style, 1 if check else 0)
+
+    def configure_tags(self, stats=False, md=False, cigar=True):
+        """quicked_batch_configure_tags for the sync runs to come: stats = a row of pair_stats() per pair, md = the SAM MD:Z
+        strings, cigar=False = align but format and download no CIGAR strings.  -> the status (QUICKED_UNIMPLEMENTED: md on a
+        packed batch)"""
+        return self._lib.quicked_batch_configure_tags(
+            self._h, (TAG_STATS if stats else 0) | (TAG_MD if md else 0) | (0 if cigar else TAG_NO_CIGAR))
+
+    def pair_stats(self):
+        """-> (n, 8) int32: matches, mismatches, ins_bases, del_bases, ins_runs, del_runs, longest_match, columns per pair (all
+        -1: no alignment).  QuickedException after a run that produced none"""
+        out = np.zeros((self.n, 8), dtype=np.int32)
+        st = self._lib.quicked_batch_pair_stats(self._h, out.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return out
+
+    def md(self):
+        """-> one MD:Z string (or None) per pair; the pattern is SAM's reference.  QuickedException after a run that produced none"""
+        nb = self._lib.quicked_batch_md_bytes(self._h)
+        pool = np.zeros(max(nb, 1), dtype=np.uint8)
+        off = np.zeros(self.n, dtype=np.int64)
+        st = self._lib.quicked_batch_md(self._h, pool.ctypes.data, off.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        raw = pool.tobytes()
+        return [None if o < 0 else raw[o:raw.index(b"\0", o)].decode("latin-1") for o in off]
 
     def validate(self, cigars):
         """device-side cigar_check_alignment of one CIGAR string (or None) per pair -> int32 verdicts"""

@@ -91,9 +91,14 @@ struct quicked_batch {
         std::vector<int64_t> cigar_off;
         PinnedBuf cigar_pool;
         std::vector<int32_t> check_ok;            // 1 valid, 0 not, -1 no alignment
+        // alignment tags (quicked_batch_configure_tags): [n] where the run produced them, else empty; all -1 / -1 for a pair
+        // without an alignment.  The MD strings arrive like the CIGARs: one DMA into pinned memory
+        std::vector<quicked_pair_stats_t> stats;
+        std::vector<int64_t> md_off;
+        PinnedBuf md_pool;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -102,6 +107,12 @@ struct quicked_batch {
     bool packed = false;                          // created from wire words: planes are the resident input, no ASCII, no k_pack
     int cigar_style = 0;                          // SegFormatArgs::style of the runs to come (quicked_batch_configure)
     bool check = false;                           // validate every CIGAR on the device (k_check_segs)
+    int tags = 0;                                 // QUICKED_TAG_* of the runs to come (quicked_batch_configure_tags)
+    // ... of the run in progress: `tags` for a sync != 0 run that aligns, else 0 (run_batch) -- what format_segments and the
+    // host-driven flows of that run read, whatever the caller configures meanwhile
+    int run_tags = 0;
+    // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
+    bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)
     // per-pair share of the counters [n][8], kept only by the object that stands in for the pairs of SEVERAL batch objects
     // in a merged early finish (qe::merged_finish): every batch gets exactly the counts of its own pairs back
@@ -194,5 +205,7 @@ void finisher_retire();
 // device-side cigar_check_alignment of caller-provided strings against the batch's resident pairs (quicked_batch_validate)
 quicked_status_t batch_validate(quicked_batch* B, Context& C, const char* cigar_pool, int64_t pool_bytes, const int64_t* cigar_off, int32_t* ok_out);
 void early_finish_stats(int64_t stats_out[4]);
+// count passes of the alignment-tag kernels launched so far: form 0 = one lane per alignment, 1 = one wave (test hook)
+int64_t tag_launches(int form);
 
 }  // namespace qe

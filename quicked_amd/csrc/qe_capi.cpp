@@ -192,6 +192,9 @@ QE_API quicked_status_t quicked_batch_run(quicked_batch_t* batch, const quicked_
     struct Arg { const quicked_params_t* p; int sync; } arg{params, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
+        // alignment tags come with the results of a sync != 0 run: a queued run that aligns cannot carry them (as queued
+        // bounded CIGAR runs: nothing is queued)
+        if (!x->sync && x->p && !x->p->only_score && B->tags) return QUICKED_UNIMPLEMENTED;
         return run_batch(*B, *x->p, x->sync != 0);
     }, &arg);
 }
@@ -281,6 +284,32 @@ QE_API quicked_status_t quicked_batch_configure(quicked_batch_t* batch, int ciga
     return QUICKED_OK;
 }
 
+QE_API quicked_status_t quicked_batch_configure_tags(quicked_batch_t* batch, int tags) {
+    if (!batch || (tags & ~(QUICKED_TAG_STATS | QUICKED_TAG_MD | QUICKED_TAG_NO_CIGAR))) return QUICKED_ERROR;
+    if ((tags & QUICKED_TAG_MD) && batch->packed) return QUICKED_UNIMPLEMENTED;      // MD names raw pattern bytes; a packed batch has none
+    batch->tags = tags;
+    return QUICKED_OK;
+}
+
+QE_API quicked_status_t quicked_batch_pair_stats(quicked_batch_t* batch, quicked_pair_stats_t* stats_out) {
+    if (!batch || !stats_out || batch->n == 0 || batch->res[batch->vis].stats.size() != (size_t)batch->n) return QUICKED_ERROR;
+    memcpy(stats_out, batch->res[batch->vis].stats.data(), (size_t)batch->n * sizeof(quicked_pair_stats_t));
+    return QUICKED_OK;
+}
+
+QE_API int64_t quicked_batch_md_bytes(quicked_batch_t* batch) {
+    if (!batch || batch->res[batch->vis].md_off.size() != (size_t)batch->n) return 0;
+    return (int64_t)batch->res[batch->vis].md_pool.size;
+}
+
+QE_API quicked_status_t quicked_batch_md(quicked_batch_t* batch, char* md_pool, int64_t* md_off) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].md_off.size() != (size_t)batch->n) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (md_pool && R.md_pool.size) memcpy(md_pool, R.md_pool.p, R.md_pool.size);
+    if (md_off) memcpy(md_off, R.md_off.data(), (size_t)batch->n * sizeof(int64_t));
+    return QUICKED_OK;
+}
+
 QE_API quicked_status_t quicked_batch_check_results(quicked_batch_t* batch, int32_t* ok_out) {
     if (!batch || batch->res[batch->vis].check_ok.size() != (size_t)batch->n) return QUICKED_ERROR;
     memcpy(ok_out, batch->res[batch->vis].check_ok.data(), (size_t)batch->n * sizeof(int32_t));
@@ -328,6 +357,14 @@ QE_API quicked_status_t quicked_pool_trim(void) {
         fprintf(stderr, "[quicked_hip] HIP error %d (%s) at %s, qe_driver.hip:%d\n", (int)e.e, hipGetErrorString(e.e), e.what, e.line);
         return QUICKED_ERROR;
     }
+}
+
+// Test hook, not in the public header: count passes of the alignment-tag kernels launched by this process so far,
+// [0] in the lane form, [1] in the wave form (QE_TAGS_WAVE: tests prove that the form they force is the one that runs)
+QE_API quicked_status_t quicked_debug_tag_launches(int64_t out[2]) {
+    if (!out) return QUICKED_ERROR;
+    out[0] = qe::tag_launches(0); out[1] = qe::tag_launches(1);
+    return QUICKED_OK;
 }
 
 // Test hook, not in the public header: parses the QE_* switches again (qe_pool.h: switches_reload).  The in-process test

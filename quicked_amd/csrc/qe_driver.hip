@@ -33,6 +33,7 @@
 #include "qe_pool.h"
 #include "qe_batch.h"
 #include "qe_bounded.h"
+#include "qe_tags.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
 // without a GPU names tests/native/hip_stub/qe_kernels_stub.h here -- tests/test_host_sanitizers.py; never set in the product)
 #ifndef QE_KERNELS_HEADER
@@ -242,7 +243,7 @@ static void quicked_classic(quicked_batch& B, Context& C, const quicked_params_t
                             const KnownStage1* known_s1 = nullptr) {
     double tr_last = now_ms();
     const bool sse = !p.force_scalar;
-    const bool want_cigar = !p.only_score;
+    const bool want_cigar = B.want_strings(p.only_score);
     // the bound stages need their results on the host to regroup; the driver is synchronous here
     std::vector<int32_t> bound(L.pair.size(), 0);
     if (p.algo == QUICKED) {
@@ -579,7 +580,11 @@ static void bounded_noncanon(quicked_batch& B, Context& C, const std::vector<u32
         if (st == QUICKED_WIP || st == QUICKED_FAIL_NON_CONVERGENCE) st = QUICKED_OK;
         int32_t& sc = B.wr->score[(size_t)pr];
         const bool within = st >= 0 && sc >= 0 && sc <= pair_bound[(size_t)pr];
-        if (!within) { sc = -1; B.wr->check_ok[(size_t)pr] = -1; }
+        if (!within) {
+            sc = -1; B.wr->check_ok[(size_t)pr] = -1;
+            if (!B.wr->stats.empty()) B.wr->stats[(size_t)pr] = quicked_pair_stats_t{-1, -1, -1, -1, -1, -1, -1, -1};
+            if (!B.wr->md_off.empty()) B.wr->md_off[(size_t)pr] = -1;
+        }
         if (!within || !want_cigar) B.wr->cigar_off[(size_t)pr] = -1;
     }
 }
@@ -789,6 +794,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         if (B.ev_done_set[par]) HIP_CHECK(B.done_wait_on(C.sw(), par));
     }
     B.only_score_run = p.only_score;
+    B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -833,7 +839,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         HIP_CHECK(hipStreamWaitEvent(C.sa(), C.ev_pack, 0));
     };
     const bool sse = !p.force_scalar;
-    const bool want_cigar = !p.only_score;
+    const bool want_cigar = B.want_strings(p.only_score);      // strings; whether the run aligns at all is !p.only_score
     const size_t matrix_budget = C.pool_budget;      // run_align subtracts what the stage needs besides the matrices
     quicked_status_t ret = QUICKED_WIP;
     QE_TRACE_POINT("setup+pack launch");
@@ -872,17 +878,17 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
                 if (pr < 0) continue;
                 B.wr->score[pr] = sc[t]; B.wr->status[pr] = QUICKED_OK;
                 if (!flags.empty() && (flags[(size_t)pr] & FLAG_NONCANON)) { noncanon = true; continue; }      // bounded_noncanon
-                if (want_cigar && sc[t] >= 0) LA.push(pr, 0, B.p_len[pr], 0, B.t_len[pr], sc[t], B.t_len[pr]);
+                if (!p.only_score && sc[t] >= 0) LA.push(pr, 0, B.p_len[pr], 0, B.t_len[pr], sc[t], B.t_len[pr]);
             }
             if (!LA.pair.empty()) {
                 AlignStats AS;
-                run_align(B, C, LA, true, true, matrix_budget, split_threshold(), QUICKED_OK, &B.d_score, &AS, nullptr, true);
+                run_align(B, C, LA, true, want_cigar, matrix_budget, split_threshold(), QUICKED_OK, &B.d_score, &AS, nullptr, true);
                 C.phase_a();
                 B.counters[1] = (int64_t)AS.fill_adv; B.counters[3] = (int64_t)AS.tb_steps;
                 // (a split that does not converge is not an error where the distance is known: run_quicked, quicked.c:290-291)
                 for (int32_t pr : LA.pair) if (pr >= 0 && B.wr->status[pr] == QUICKED_FAIL_NON_CONVERGENCE) B.wr->status[pr] = QUICKED_OK;
             }
-            if (noncanon) { bounded_noncanon(B, C, flags, pair_bound, want_cigar, matrix_budget, par); C.phase_a(); }
+            if (noncanon) { bounded_noncanon(B, C, flags, pair_bound, !p.only_score, matrix_budget, par); C.phase_a(); }
         }
         ret = QUICKED_OK;
     } else

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include "qe_types.h"
 #include "qe_bounded.h"
+#include "qe_tags.h"
 
 namespace qe {
 
@@ -4587,6 +4588,167 @@ __global__ __launch_bounds__(64) void k_check_segs(SegCheckArgs C) {
     }
     C.o_ok[i] = K.verdict();
 }
+
+// ===========================================================================
+// Alignment tags (quicked_batch_configure_tags; definitions and the string's bound in qe_tags.h): per-pair statistics
+// and the MD string from the traceback's runs.  WRITE = false counts -- statistics and every string's length, which
+// k_scan_offsets turns into offsets --, WRITE = true writes the strings.  Statistics alone are one pass.
+// ===========================================================================
+#define QE_HAVE_K_TAGS 1
+struct TagRuns {                   // what tag_walk_segments reads a leaf's runs through
+    const SegFormatArgs& A; RunView rv;
+    __device__ __forceinline__ void open(int t) { rv = run_view(A, t); }
+    __device__ __forceinline__ u32 at(int k) const { return rv.at(k); }
+};
+// the count pass's verdict on one alignment (lane form: its lane; wave form: lane 0)
+__device__ __forceinline__ void tags_store_counts(const SegTagArgs& T, int i, bool bad, const TagStats& s, int64_t md_len, int m) {
+    tag_store_counts(T.want_stats ? T.o_stats + i : nullptr, T.want_md ? T.o_md_len + i : nullptr, T.o_md_bad, bad, s, md_len, m);
+}
+
+// Lane form: one lane per alignment walks its segments front to back, as k_check_segs does
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_tags_segs(SegTagArgs T) {
+    const SegFormatArgs& A = T.F;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= A.npairs) return;
+    const int pair = T.root_pair[i];
+    const int m = T.P.p_len[pair];
+    TagWalker<WRITE> W;
+    W.want_md = T.want_md != 0;
+    if (WRITE) {
+        char* out = T.md_pool + T.md_off[i];
+        if (T.o_md_len[i] <= 0) { out[0] = '\0'; return; }
+        W.sink = TagSink{out, T.o_md_len[i], T.P.asc_p + T.P.asc_p_off[pair], m};
+    }
+    TagRuns R{A, RunView{nullptr, 0}};
+    const bool ok = tag_walk_segments(W, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
+    const int64_t md_len = W.finish();
+    if (!WRITE) tags_store_counts(T, i, !ok, W.s, md_len, m);
+}
+template __global__ void k_tags_segs<false>(SegTagArgs);
+template __global__ void k_tags_segs<true>(SegTagArgs);
+
+// Wave form: one wave per alignment, 64 consecutive runs per step, lane l run 64 j + l (k_format_segs_wave's walk).  A step
+// needs, over its runs as they lie -- unmerged: what merging changes is decided by the run to the left --
+//   v      exclusive prefix sum of the pattern-consuming lengths (M, X, D) + the steps before: where my run starts in P;
+//   acc    for an X / D run the M lengths since the previous X / D, I skipped: a segmented scan whose segments X and D
+//          open; the open segment is carried from step to step, and what is open at the end is the closing number;
+//   group  the length of the maximal run mine belongs to, up to and including mine (segments open where the operation
+//          changes; the open one is carried): longest_match is the maximum over M lanes, so a group that spans steps
+//          counts once, at its full length; an I / D run counts as a run where its left neighbour is another operation;
+//   chars  prefix sum of the characters every lane writes: X "<acc>B" + "0B" per further base, D "<acc>^" + its bytes,
+//          or only its bytes where the run to its left is a D too (one caret per maximal run).
+// Statistics are per-lane partial sums, reduced once at the end.
+// Like k_format_segs_wave this relies on the traceback never leaving a zero-length run inside a leaf: the lane walker
+// drops such a run, here it would stand between its neighbours (zero-length LITERAL segments are skipped by SegCursor).
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_tags_segs_wave(SegTagArgs T) {
+    const SegFormatArgs& A = T.F;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= A.npairs) return;
+    const int pair = T.root_pair[i];
+    const int m = T.P.p_len[pair];
+    const bool want_md = T.want_md != 0;
+    TagSink sink{nullptr, 0, nullptr, 0};
+    if (WRITE) {
+        char* out = T.md_pool + T.md_off[i];
+        if (T.o_md_len[i] <= 0) { if (lane == 0) out[0] = '\0'; return; }
+        sink = TagSink{out, T.o_md_len[i], T.P.asc_p + T.P.asc_p_off[pair], m};
+    }
+    const int64_t s0 = A.seg_off[i], s1 = A.seg_off[i + 1];
+    int64_t total_runs = 0; bool bad = false;
+    for (int64_t sg = s0 + lane; sg < s1; sg += 64) {
+        if (A.seg_kind[sg] == 1) total_runs += A.seg_b[sg] > 0 ? 1 : 0;
+        else { const int nr = A.nruns[A.seg_a[sg]]; if (nr < 0) bad = true; total_runs += max(nr, 0); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) total_runs += __shfl_xor(total_runs, o);
+    TagStats s{0, 0, 0, 0, 0, 0, 0, 0};
+    if (__any(bad)) {
+        if (!WRITE && lane == 0) tags_store_counts(T, i, true, s, 0, m);
+        return;
+    }
+    SegCursor C; C.A = &A; C.s1 = s1; C.seg = s0; C.first = 0; C.load();
+    int64_t written = 0, v_base = 0;     // MD characters / pattern bases of the steps before (the same in every lane)
+    int carry_op = -1, carry_len = 0;    // the last run of the previous step and the length of its group so far
+    int carry_acc = 0;                   // M lengths since the last X / D of the steps before
+    for (int64_t base = 0; base < total_runs; base += 64) {
+        int op = -1, x = 0;
+        const bool valid = (base + lane < total_runs) && C.get(base + lane, op, x);
+        if (!valid) { op = -1; x = 0; }
+        const int len = x;
+        const int left = __shfl_up(op, 1);
+        const int op_prev = (lane == 0) ? carry_op : left;
+        const int last = (int)min((int64_t)63, total_runs - 1 - base);
+        if (!WRITE && T.want_stats) {
+            // group: segmented inclusive scan of the lengths
+            bool flag = valid && op != op_prev;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(x, d);
+                const int f = __shfl_up((int)flag, d);
+                if (lane >= d && !flag) { x += y; flag = f != 0; }
+            }
+            if (valid && !flag) x += carry_len;
+            carry_len = __shfl(x, last);
+            if (valid) {
+                s.columns += len;
+                if (op == (int)OP_M) { s.matches += len; s.longest_match = max(s.longest_match, x); }
+                else if (op == (int)OP_X) s.mismatches += len;
+                else if (op == (int)OP_I) { s.ins_bases += len; if (op != op_prev) ++s.ins_runs; }
+                else { s.del_bases += len; if (op != op_prev) ++s.del_runs; }
+            }
+        }
+        if (want_md) {
+            const bool event = valid && (op == (int)OP_X || op == (int)OP_D);
+            // acc: M lengths since the last event, inclusive of my own run (an event's own share is 0)
+            int a = (valid && op == (int)OP_M) ? len : 0;
+            bool flag = event;
+            // v: pattern bases up to and including my run
+            int pv = (valid && op != (int)OP_I) ? len : 0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(a, d);
+                const int f = __shfl_up((int)flag, d);
+                const int w = __shfl_up(pv, d);
+                if (lane >= d) { pv += w; if (!flag) { a += y; flag = f != 0; } }
+            }
+            if (!flag) a += carry_acc;
+            const int a_left = __shfl_up(a, 1);
+            const int acc = (lane == 0) ? carry_acc : a_left;            // what precedes my run
+            const bool opens = !(op == (int)OP_D && op_prev == (int)OP_D);
+            int chars = 0;
+            if (event) chars = (int)((op == (int)OP_X) ? tag_md_chars_x(acc, len) : (opens ? tag_md_chars_d(acc, len) : (int64_t)len));
+            int off = chars;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(off, d); if (lane >= d) off += y; }
+            if (WRITE && event) {
+                const int64_t q = written + (off - chars), v = v_base + (pv - len);
+                if (op == (int)OP_X) sink.run_x(q, acc, v, len); else sink.run_d(q, acc, v, len, opens);
+            }
+            written += __shfl(off, 63);
+            v_base += __shfl(pv, 63);
+            carry_acc = __shfl(a, last);
+        }
+        carry_op = __shfl(op, last);
+    }
+    if (WRITE) {
+        if (lane == 0) { sink.number(written, carry_acc); sink.out[sink.cap] = '\0'; }
+        return;
+    }
+    if (T.want_stats) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            s.matches += __shfl_xor(s.matches, o); s.mismatches += __shfl_xor(s.mismatches, o);
+            s.ins_bases += __shfl_xor(s.ins_bases, o); s.del_bases += __shfl_xor(s.del_bases, o);
+            s.ins_runs += __shfl_xor(s.ins_runs, o); s.del_runs += __shfl_xor(s.del_runs, o);
+            s.columns += __shfl_xor(s.columns, o); s.longest_match = max(s.longest_match, __shfl_xor(s.longest_match, o));
+        }
+    }
+    if (lane == 0) tags_store_counts(T, i, false, s, want_md ? written + tag_digits((u32)carry_acc) : 0, m);
+}
+template __global__ void k_tags_segs_wave<false>(SegTagArgs);
+template __global__ void k_tags_segs_wave<true>(SegTagArgs);
 
 // The same walk over caller-supplied CIGAR strings ("<len><op>" with op in MXID, or '=' for M): pair i's string
 // starts at pool + off[i] and is NUL-terminated; off[i] < 0 = no string (verdict -1)

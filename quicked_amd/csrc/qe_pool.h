@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, ScoreMasked, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, ScoreMasked, TagsWave, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -110,6 +110,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::ScoreNarrow, "QE_SCORE_NARROW", -1},          // BandEd score-only runs: -1 a first pass at half the cutoff where it pays (narrow_wanted), 0 never (the reference's band, cell for cell), 1 wherever a task's band is narrower there (tests), -2 as -1 without the policy's probes (diagnosis)
     {Sw::NarrowFit, "QE_NARROW_FIT", -1},              // ... their first pass: -1 the fewest slots that prove the distances the class's last runs saw (narrow_fit_q), 0 always half the cutoff, k > 0 fitted to k / 1024 of every cutoff whatever ran before (tests)
     {Sw::ScoreMasked, "QE_SCORE_MASKED", 1},           // k_banded<false>'s multi-slot passes: 1 every lane with the slots of the pass inside its band (pass_plan), 0 with all of them or none (the rule before it, pass for pass)
+    {Sw::TagsWave, "QE_TAGS_WAVE", -1},                // alignment tags (quicked_batch_configure_tags): -1 the wave form where the CIGAR formatter takes its own (tags_wave_wanted), 0 / 1 the lane / wave form everywhere (tests)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {

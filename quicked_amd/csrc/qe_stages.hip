@@ -630,7 +630,14 @@ struct AlignOut {                             // device, per root
     int32_t* ok = nullptr;                    // validator verdicts (null unless the batch asks for them)
     size_t nroots = 0;
     size_t pool_bytes = 0;                    // what `pool` was sized for (the host-side bound of the strings)
+    // alignment tags (null unless the run asks for them): statistics; MD lengths, offsets, total, overflow flag and pool
+    TagStats* stats = nullptr;
+    int32_t *md_len = nullptr, *md_bad = nullptr;
+    int64_t *md_off = nullptr, *md_total = nullptr;
+    char* md_pool = nullptr;
+    size_t md_pool_bytes = 0;                 // sum of tag_md_bound over the roots
 };
+static_assert(sizeof(TagStats) == sizeof(quicked_pair_stats_t) && sizeof(TagStats) == 32, "TagStats is quicked_pair_stats_t");
 
 // Results of a sync == 0 run, still on the device: what quicked_batch_fetch() copies once the run is over.  The device
 // pointers are those of the batch's result arena (stash_results): valid until the batch's next run, reload or destroy.
@@ -949,9 +956,63 @@ static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList
 static bool wave_formatter_wanted(const quicked_batch& B, const SegList& SL, bool want_strings) {
     const size_t nr = SL.root_pair.size(), nseg = SL.kind.size();
     size_t pool_bytes = 0;
-    if (want_strings) for (size_t b : SL.bound) pool_bytes += b;
+    // QUICKED_TAG_NO_CIGAR: the run lays its runs out, and picks the tag kernels' form, as the CIGAR run of the same pairs would
+    if (want_strings || (B.run_tags & QUICKED_TAG_NO_CIGAR)) for (size_t b : SL.bound) pool_bytes += b;
     const int wave_env = sw(Sw::FormatWave);      // tests force either form
     return B.cigar_style != 2 && nr > 0 && (wave_env >= 0 ? wave_env != 0 : (nseg > 0 && pool_bytes / nr >= 512));
+}
+
+#ifndef QE_HAVE_K_TAGS
+// a kernels header without the tag kernels (the host-only build's stand-ins): the walker of qe_tags.h on the host, both forms
+struct HostTagRuns {
+    const SegFormatArgs& A; const u32* base = nullptr; int64_t stride = 1;
+    void open(int t) {
+        const int g = t >> 6, lane = t & 63;
+        if (A.runs_by_task) { base = A.runs + A.g_runs_off[g] + (int64_t)lane * A.g_runs_cap[g]; stride = 1; }
+        else { base = A.runs + A.g_runs_off[g] + lane; stride = 64; }
+    }
+    u32 at(int k) const { return base[(int64_t)k * stride]; }
+};
+template <bool WRITE> static void k_tags_segs(SegTagArgs T) {
+    const SegFormatArgs& A = T.F;
+    for (int i = 0; i < A.npairs; ++i) {
+        const int pair = T.root_pair[i];
+        const int m = T.P.p_len[pair];
+        TagWalker<WRITE> W;
+        W.want_md = T.want_md != 0;
+        if (WRITE) {
+            char* out = T.md_pool + T.md_off[i];
+            if (T.o_md_len[i] <= 0) { out[0] = '\0'; continue; }
+            W.sink = TagSink{out, T.o_md_len[i], T.P.asc_p + T.P.asc_p_off[pair], m};
+        }
+        HostTagRuns R{A};
+        const bool ok = tag_walk_segments(W, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
+        const int64_t md_len = W.finish();
+        if (!WRITE) tag_store_counts(T.want_stats ? T.o_stats + i : nullptr, T.want_md ? T.o_md_len + i : nullptr, T.o_md_bad, !ok, W.s, md_len, m);
+    }
+}
+template <bool WRITE> static void k_tags_segs_wave(SegTagArgs T) { k_tags_segs<WRITE>(T); }
+#endif
+
+// Which form of the tag kernels a stage takes: the wave form where the CIGAR formatter takes its wave form (runs laid out by
+// task: 256-byte rows), else the lane form; QE_TAGS_WAVE = 0 / 1 forces one (tests).  Both read either run layout.
+static std::atomic<int64_t> g_tag_launches[2];      // count passes launched, process-wide: [0] lane form, [1] wave form (tests)
+int64_t tag_launches(int form) { return g_tag_launches[form ? 1 : 0].load(std::memory_order_relaxed); }
+static bool tags_wave_wanted(bool format_wave) {
+    const int force = sw(Sw::TagsWave);
+    return force >= 0 ? force != 0 : format_wave;
+}
+
+// what format_segments takes from the pool for the tags of these roots: statistics, MD lengths and offsets, the MD pool
+static size_t tag_scratch_bytes(const quicked_batch& B, const SegList& SL) {
+    size_t bytes = 0;
+    const size_t nr = SL.root_pair.size();
+    if (B.run_tags & QUICKED_TAG_STATS) bytes += (nr + 1) * sizeof(TagStats) + 256;
+    if (B.run_tags & QUICKED_TAG_MD) {
+        bytes += (nr + 1) * 12 + 1024;
+        for (int32_t pr : SL.root_pair) bytes += (size_t)tag_md_bound(B.p_len[(size_t)pr]);
+    }
+    return bytes;
 }
 
 static AlignOut format_segments(const quicked_batch& B, Context& C, const SegList& SL, const u32* runs, const int64_t* g_runs_off,
@@ -995,6 +1056,35 @@ static AlignOut format_segments(const quicked_batch& B, Context& C, const SegLis
         if (wave) hipLaunchKernelGGL(k_format_segs_wave<true>, dim3((unsigned)nr), dim3(64), 0, C.stream, f);
         else hipLaunchKernelGGL(k_format_segs<true>, dim3(blocks), dim3(64), 0, C.stream, f);
     }
+    const bool want_stats = (B.run_tags & QUICKED_TAG_STATS) != 0, want_md = (B.run_tags & QUICKED_TAG_MD) != 0;
+    if ((want_stats || want_md) && nr > 0) {
+        // alignment tags: the count pass leaves the statistics and every MD string's length, the scan its offset, the write
+        // pass the strings.  The MD pool is taken before the lengths are known: tag_md_bound per root (qe_tags.h)
+        SegTagArgs tg;
+        tg.F = f; tg.P = pair_view(B, false); tg.root_pair = d_rootpair;
+        tg.want_stats = want_stats ? 1 : 0; tg.want_md = want_md ? 1 : 0;
+        tg.o_stats = nullptr; tg.o_md_len = nullptr; tg.o_md_bad = nullptr; tg.md_off = nullptr; tg.md_pool = nullptr;
+        if (want_stats) tg.o_stats = A.stats = C.scratch_p->take<TagStats>(nr + 1);
+        if (want_md) {
+            for (int32_t pr : SL.root_pair) A.md_pool_bytes += (size_t)tag_md_bound(B.p_len[(size_t)pr]);
+            tg.o_md_len = A.md_len = C.scratch_p->take<int32_t>(nr + 1);
+            tg.md_off = A.md_off = C.scratch_p->take<int64_t>(nr + 1);
+            A.md_total = C.scratch_p->take<int64_t>(1);
+            tg.o_md_bad = A.md_bad = C.scratch_p->take<int32_t>(4);
+            A.md_pool_bytes += 16;
+            tg.md_pool = A.md_pool = C.scratch_p->take<char>(A.md_pool_bytes);
+            HIP_CHECK(hipMemsetAsync(A.md_bad, 0, sizeof(int32_t), C.stream));
+        }
+        const bool tw = tags_wave_wanted(wave);
+        g_tag_launches[tw ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+        if (tw) hipLaunchKernelGGL(k_tags_segs_wave<false>, dim3((unsigned)nr), dim3(64), 0, C.stream, tg);
+        else hipLaunchKernelGGL(k_tags_segs<false>, dim3(blocks), dim3(64), 0, C.stream, tg);
+        if (want_md) {
+            hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, A.md_len, d_rootpair, A.md_off, A.md_total, (int)nr);
+            if (tw) hipLaunchKernelGGL(k_tags_segs_wave<true>, dim3((unsigned)nr), dim3(64), 0, C.stream, tg);
+            else hipLaunchKernelGGL(k_tags_segs<true>, dim3(blocks), dim3(64), 0, C.stream, tg);
+        }
+    }
     return A;
 }
 
@@ -1003,10 +1093,21 @@ static void fetch_alignments(quicked_batch& B, Context& C, const SegList& SL, co
                              int32_t ok_status, const std::vector<int32_t>* root_status) {
     std::vector<int32_t> len, edits, nops; std::vector<int64_t> off;
     std::vector<int32_t> okv;
+    std::vector<quicked_pair_stats_t> tstats; std::vector<int32_t> md_len; std::vector<int64_t> md_off;      // alignment tags
+    int32_t md_bad = 0;
     const size_t nr = A.nroots;
     const bool strings = want_strings && A.pool != nullptr && A.pool_bytes > 0;
-    const size_t small_bytes = 6 * (((nr * 8) + 63) & ~(size_t)63) + (strings ? A.pool_bytes + 64 : 0);
+    const size_t tag_bytes = (A.stats ? ((nr * 32 + 63) & ~(size_t)63) : 0) + (A.md_len ? 2 * ((nr * 8 + 63) & ~(size_t)63) + 64 + A.md_pool_bytes + 64 : 0);
+    const size_t small_bytes = 6 * (((nr * 8) + 63) & ~(size_t)63) + (strings ? A.pool_bytes + 64 : 0) + tag_bytes;
     const size_t base = B.wr->cigar_pool.size;
+    const size_t md_base = B.wr->md_pool.size;
+    // the MD strings of this stage: their lengths give the total (offsets are a scan of length + 1, as the CIGARs')
+    auto md_total_of = [&]() {
+        int64_t total = 0;
+        for (size_t i = 0; i < nr; ++i) total = std::max<int64_t>(total, md_off[i] + md_len[i] + 1);
+        if (md_bad || (size_t)total > A.md_pool_bytes) throw HipError{hipErrorUnknown, "MD strings beyond their pool's bound", __LINE__};
+        return total;
+    };
     if (small_bytes <= ((size_t)256 << 10)) {
         // few alignments (a single quicked_align call): the per-root arrays and the string pool up to its bound arrive in the
         // context's pinned block through ONE copy launch and ONE synchronisation (five copies, the strings' own round trip
@@ -1015,12 +1116,15 @@ static void fetch_alignments(quicked_batch& B, Context& C, const SegList& SL, co
         size_t top = 0;
         auto get = [&](const void* src, size_t bytes) { uint8_t* p = st + top; copy_kernel(p, src, bytes, C.stream); top += (bytes + 63) & ~(size_t)63; return p; };
         const uint8_t *h_len, *h_edits, *h_nops, *h_off = nullptr, *h_ok = nullptr, *h_pool = nullptr;
+        const uint8_t *h_stats = nullptr, *h_mdlen = nullptr, *h_mdoff = nullptr, *h_mdbad = nullptr, *h_mdpool = nullptr;
         {
             CopyBatch cb(C.stream);
             h_len = get(A.len, nr * 4); h_edits = get(A.edits, nr * 4); h_nops = get(A.nops, nr * 4);
             if (want_strings) h_off = get(A.str_off, nr * 8);
             if (A.ok) h_ok = get(A.ok, nr * 4);
             if (strings) h_pool = get(A.pool, A.pool_bytes);
+            if (A.stats) h_stats = get(A.stats, nr * 32);
+            if (A.md_len) { h_mdlen = get(A.md_len, nr * 4); h_mdoff = get(A.md_off, nr * 8); h_mdbad = get(A.md_bad, 4); h_mdpool = get(A.md_pool, A.md_pool_bytes); }
         }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(C.stream));
@@ -1036,11 +1140,34 @@ static void fetch_alignments(quicked_batch& B, Context& C, const SegList& SL, co
             memcpy(B.wr->cigar_pool.p + base, h_pool, (size_t)total);
             B.wr->cigar_pool.size = base + (size_t)total;
         }
+        if (h_stats) tstats.assign((const quicked_pair_stats_t*)h_stats, (const quicked_pair_stats_t*)h_stats + nr);
+        if (h_mdlen) {
+            md_len.assign((const int32_t*)h_mdlen, (const int32_t*)h_mdlen + nr); md_off.assign((const int64_t*)h_mdoff, (const int64_t*)h_mdoff + nr);
+            md_bad = *(const int32_t*)h_mdbad;
+            const int64_t md_total = md_total_of();
+            if (md_total) {
+                B.wr->md_pool.reserve(md_base + (size_t)md_total);
+                memcpy(B.wr->md_pool.p + md_base, h_mdpool, (size_t)md_total);
+                B.wr->md_pool.size = md_base + (size_t)md_total;
+            }
+        }
     } else {
         d2h(len, A.len, A.nroots, C.stream); d2h(edits, A.edits, A.nroots, C.stream); d2h(nops, A.nops, A.nroots, C.stream);
         if (want_strings) d2h(off, A.str_off, A.nroots, C.stream);
         if (A.ok) d2h(okv, A.ok, A.nroots, C.stream);
+        std::vector<int32_t> bad1;
+        if (A.stats) d2h(tstats, (const quicked_pair_stats_t*)A.stats, A.nroots, C.stream);
+        if (A.md_len) { d2h(md_len, A.md_len, A.nroots, C.stream); d2h(md_off, A.md_off, A.nroots, C.stream); d2h(bad1, A.md_bad, 1, C.stream); }
         HIP_CHECK(hipStreamSynchronize(C.stream));
+        if (A.md_len) {
+            md_bad = bad1[0];
+            const int64_t md_total = md_total_of();
+            if (md_total) {
+                B.wr->md_pool.reserve(md_base + (size_t)md_total);
+                HIP_CHECK(hipMemcpyAsync(B.wr->md_pool.p + md_base, A.md_pool, (size_t)md_total, hipMemcpyDeviceToHost, C.stream));
+                B.wr->md_pool.size = md_base + (size_t)md_total;      // (the stream is synchronised below, or with the CIGARs' copy)
+            }
+        }
         int64_t total = 0;
         if (want_strings) for (size_t i = 0; i < A.nroots; ++i) total = std::max<int64_t>(total, off[i] + len[i] + 1);
         if (total) {
@@ -1048,7 +1175,7 @@ static void fetch_alignments(quicked_batch& B, Context& C, const SegList& SL, co
             HIP_CHECK(hipMemcpyAsync(B.wr->cigar_pool.p + base, A.pool, (size_t)total, hipMemcpyDeviceToHost, C.stream));
             HIP_CHECK(hipStreamSynchronize(C.stream));
             B.wr->cigar_pool.size = base + (size_t)total;
-        }
+        } else if (A.md_len) HIP_CHECK(hipStreamSynchronize(C.stream));
     }
     for (size_t i = 0; i < A.nroots; ++i) {
         const int pr = SL.root_pair[i];
@@ -1059,6 +1186,8 @@ static void fetch_alignments(quicked_batch& B, Context& C, const SegList& SL, co
         B.note_pair(pr, 4, nops[i]);
         if (A.ok) B.wr->check_ok[pr] = okv[i];
         if (want_strings && len[i] > 0) B.wr->cigar_off[pr] = (int64_t)base + off[i];      // NUL-terminated in the pool
+        if (A.stats && !B.wr->stats.empty()) B.wr->stats[pr] = tstats[i];
+        if (A.md_len && !B.wr->md_off.empty()) B.wr->md_off[pr] = md_len[i] > 0 ? (int64_t)md_base + md_off[i] : -1;
     }
 }
 
@@ -1164,6 +1293,11 @@ static void reset_host_results(quicked_batch& B) {
     B.wr->cigar_off.assign((size_t)B.n, -1);
     B.wr->cigar_pool.size = 0;
     B.wr->check_ok.assign((size_t)B.n, -1);
+    // alignment tags: arrays only where this run produces them (the getters refuse the others)
+    static const quicked_pair_stats_t no_stats = {-1, -1, -1, -1, -1, -1, -1, -1};
+    if (B.run_tags & QUICKED_TAG_STATS) B.wr->stats.assign((size_t)B.n, no_stats); else B.wr->stats.clear();
+    if (B.run_tags & QUICKED_TAG_MD) B.wr->md_off.assign((size_t)B.n, -1); else B.wr->md_off.clear();
+    B.wr->md_pool.size = 0;
     B.wr->deferred_pairs = 0;
 }
 
@@ -1301,6 +1435,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
     // what the stage takes from the pool besides the matrices: run buffers, string pool, per-task arrays, segment lists
     size_t fixed_bytes = lay.runs_u32 * 4 + (size_t)nt * 160 + SL.kind.size() * 16 + ((size_t)4 << 20);
     if (want_cigar) for (size_t b : SL.bound) fixed_bytes += b;
+    fixed_bytes += tag_scratch_bytes(B, SL);
     B.last_fixed_bytes = fixed_bytes + lay.ws_bytes;
     B.last_groups = ng;
     // partition the groups so that each sub-batch's matrices (and workspaces) fit what is left of the pool's budget

@@ -367,4 +367,19 @@ struct SegCheckArgs {
     int32_t* o_ok;               // 1 valid, 0 not
 };
 
+// Per-pair statistics and MD strings of every entry's alignment (qe_tags.h; quicked_batch_configure_tags).  The count pass
+// leaves o_stats / o_md_len (string length without the terminator; 0 where the pair has no alignment), the write pass
+// fills md_pool at md_off: F.o_* / F.pool / F.str_off are not touched
+struct TagStats;
+struct SegTagArgs {
+    SegFormatArgs F;
+    PairView P;
+    const int32_t* root_pair;
+    int32_t want_stats, want_md;
+    TagStats* o_stats;           // [npairs], all -1 where the pair has no alignment
+    int32_t* o_md_len;
+    int32_t* o_md_bad;           // one flag: set when a string would not fit tag_md_bound of its pattern
+    const int64_t* md_off;  char* md_pool;
+};
+
 }  // namespace qe
