@@ -198,7 +198,12 @@ quicked_status_t quicked_batch_md(quicked_batch_t* batch, char* md_pool, int64_t
 
 /* The same validator for CIGAR strings from anywhere ("<len><op>", op in MXID, '=' read as M): string i is
  * cigar_pool + cigar_off[i], NUL-terminated, against the batch's resident pair i; cigar_off[i] < 0 -> -1.
- * What `align_benchmark -c correct` does per pair on the host (benchmark_check.c), at batch scale. */
+ * What `align_benchmark -c correct` does per pair on the host (benchmark_check.c), at batch scale.
+ * A length is decimal, at least 1 and at most 2147483647 (leading zeros allowed); a longer number, a zero, digits without an
+ * operation, an operation without digits and any other byte make the string invalid (0), as does the first operation that
+ * would leave either sequence -- whatever its length: no string makes the walk read outside its pair, and no sum of lengths
+ * wraps back into it.  The empty string is the alignment of two empty sequences.  An offset >= pool_bytes: QUICKED_ERROR,
+ * ok_out untouched. */
 quicked_status_t quicked_batch_validate(quicked_batch_t* batch, const char* cigar_pool, int64_t pool_bytes,
                                         const int64_t* cigar_off, int32_t* ok_out);
 

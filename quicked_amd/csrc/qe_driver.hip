@@ -1737,6 +1737,7 @@ quicked_status_t fetch_results(quicked_batch& B) { return fetch_pending(B); }
 void early_finish_stats(int64_t stats_out[4]) { for (int q = 0; q < 4; ++q) stats_out[q] = g_fin_stats[q].load(); }
 
 quicked_status_t batch_validate(quicked_batch* B, Context& C, const char* cigar_pool, int64_t pool_bytes, const int64_t* cigar_off, int32_t* ok_out) {
+    for (int64_t i = 0; i < B->n; ++i) if (cigar_off[i] >= pool_bytes) return QUICKED_ERROR;      // before anything is queued
     C.sync_all();
     C.phase_u();
     const DevicePool::Mark mk = C.pool_w.mark();
@@ -1746,7 +1747,6 @@ quicked_status_t batch_validate(quicked_batch* B, Context& C, const char* cigar_
     if (pool_bytes > 0) HIP_CHECK(hipMemcpyAsync(d_pool, cigar_pool, (size_t)pool_bytes, hipMemcpyHostToDevice, C.stream));
     HIP_CHECK(hipMemsetAsync(d_pool + pool_bytes, 0, 16, C.stream));      // a missing terminator cannot run off the pool
     HIP_CHECK(hipMemcpyAsync(d_off, cigar_off, (size_t)B->n * sizeof(int64_t), hipMemcpyHostToDevice, C.stream));
-    for (int64_t i = 0; i < B->n; ++i) if (cigar_off[i] >= pool_bytes) { C.pool_w.release(mk); return QUICKED_ERROR; }
     const int blocks = (int)((B->n + 63) / 64);
     hipLaunchKernelGGL(k_check_strings, dim3(blocks), dim3(64), 0, C.stream, pair_view(*B, false), (int)B->n,
                        (const char*)d_pool, (const int64_t*)d_off, d_ok);

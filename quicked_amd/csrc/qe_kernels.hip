@@ -31,6 +31,7 @@
 #include "qe_types.h"
 #include "qe_bounded.h"
 #include "qe_tags.h"
+#include "qe_check.h"
 
 namespace qe {
 
@@ -4544,48 +4545,28 @@ template __global__ void k_format_segs_wave<true>(SegFormatArgs);
 // ===========================================================================
 // Validator (cigar_check_alignment, cigar.c:363-434): one lane per alignment walks its operations front
 // to back over the RAW bytes of the pair: M needs equal bytes, X different ones, I consumes text, D
-// pattern; both sequences must be consumed exactly.
+// pattern; both sequences must be consumed exactly.  The walk, the string parser and their rules are
+// qe_check.h, the source the CPU suite compiles too; the kernels only point it at their lane's pair.
 // ===========================================================================
-struct AlignCheck {
-    const uint8_t* ap; const uint8_t* at; int m, n, v = 0, h = 0; bool ok = true;
-    __device__ __forceinline__ void apply(int op, int cnt) {
-        if (!ok || cnt <= 0) return;
-        if (op == (int)OP_I) { h += cnt; return; }
-        if (op == (int)OP_D) { v += cnt; return; }
-        if (v + cnt > m || h + cnt > n) { ok = false; return; }
-        int k = 0;
-        if (op == (int)OP_M) {
-            for (; k + 8 <= cnt; k += 8) {
-                u64 x, y; __builtin_memcpy(&x, ap + v + k, 8); __builtin_memcpy(&y, at + h + k, 8);
-                if (x != y) { ok = false; return; }
-            }
-            for (; k < cnt; ++k) if (ap[v + k] != at[h + k]) { ok = false; return; }
-        } else {
-            for (; k < cnt; ++k) if (ap[v + k] == at[h + k]) { ok = false; return; }
-        }
-        v += cnt; h += cnt;
-    }
-    __device__ __forceinline__ int verdict() const { return (ok && v == m && h == n) ? 1 : 0; }
+struct SegRuns {                   // what check_walk_segments / tag_walk_segments read a leaf's runs through
+    const SegFormatArgs& A; RunView rv;
+    __device__ __forceinline__ void open(int t) { rv = run_view(A, t); }
+    __device__ __forceinline__ u32 at(int k) const { return rv.at(k); }
 };
+__device__ __forceinline__ AlignCheck check_of_pair(const PairView& P, int pair) {
+    AlignCheck K;
+    K.ap = P.asc_p + P.asc_p_off[pair]; K.at = P.asc_t + P.asc_t_off[pair];
+    K.m = P.p_len[pair]; K.n = P.t_len[pair];
+    return K;
+}
 
 __global__ __launch_bounds__(64) void k_check_segs(SegCheckArgs C) {
     const SegFormatArgs& A = C.F;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A.npairs) return;
-    const int pair = C.root_pair[i];
-    AlignCheck K;
-    K.ap = C.P.asc_p + C.P.asc_p_off[pair]; K.at = C.P.asc_t + C.P.asc_t_off[pair];
-    K.m = C.P.p_len[pair]; K.n = C.P.t_len[pair];
-    for (int64_t sidx = A.seg_off[i]; sidx < A.seg_off[i + 1]; ++sidx) {
-        if (A.seg_kind[sidx] == 1) { K.apply(A.seg_a[sidx], A.seg_b[sidx]); continue; }
-        const int t = A.seg_a[sidx];
-        const RunView runs = run_view(A, t);
-        if (A.nruns[t] < 0) K.ok = false;
-        for (int k = A.nruns[t] - 1; k >= 0; --k) {
-            const u32 r = runs.at(k);
-            K.apply((int)(r & 3), (int)(r >> 2));
-        }
-    }
+    AlignCheck K = check_of_pair(C.P, C.root_pair[i]);
+    SegRuns R{A, RunView{nullptr, 0}};
+    check_walk_segments(K, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
     C.o_ok[i] = K.verdict();
 }
 
@@ -4595,11 +4576,6 @@ __global__ __launch_bounds__(64) void k_check_segs(SegCheckArgs C) {
 // k_scan_offsets turns into offsets --, WRITE = true writes the strings.  Statistics alone are one pass.
 // ===========================================================================
 #define QE_HAVE_K_TAGS 1
-struct TagRuns {                   // what tag_walk_segments reads a leaf's runs through
-    const SegFormatArgs& A; RunView rv;
-    __device__ __forceinline__ void open(int t) { rv = run_view(A, t); }
-    __device__ __forceinline__ u32 at(int k) const { return rv.at(k); }
-};
 // the count pass's verdict on one alignment (lane form: its lane; wave form: lane 0)
 __device__ __forceinline__ void tags_store_counts(const SegTagArgs& T, int i, bool bad, const TagStats& s, int64_t md_len, int m) {
     tag_store_counts(T.want_stats ? T.o_stats + i : nullptr, T.want_md ? T.o_md_len + i : nullptr, T.o_md_bad, bad, s, md_len, m);
@@ -4620,7 +4596,7 @@ __global__ __launch_bounds__(64) void k_tags_segs(SegTagArgs T) {
         if (T.o_md_len[i] <= 0) { out[0] = '\0'; return; }
         W.sink = TagSink{out, T.o_md_len[i], T.P.asc_p + T.P.asc_p_off[pair], m};
     }
-    TagRuns R{A, RunView{nullptr, 0}};
+    SegRuns R{A, RunView{nullptr, 0}};
     const bool ok = tag_walk_segments(W, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
     const int64_t md_len = W.finish();
     if (!WRITE) tags_store_counts(T, i, !ok, W.s, md_len, m);
@@ -4750,29 +4726,14 @@ __global__ __launch_bounds__(64) void k_tags_segs_wave(SegTagArgs T) {
 template __global__ void k_tags_segs_wave<false>(SegTagArgs);
 template __global__ void k_tags_segs_wave<true>(SegTagArgs);
 
-// The same walk over caller-supplied CIGAR strings ("<len><op>" with op in MXID, or '=' for M): pair i's string
-// starts at pool + off[i] and is NUL-terminated; off[i] < 0 = no string (verdict -1)
+// The same walk over caller-supplied CIGAR strings (the syntax: qe_check.h): pair i's string starts at pool + off[i] and
+// is NUL-terminated; off[i] < 0 = no string (verdict -1)
 __global__ __launch_bounds__(64) void k_check_strings(PairView P, int npairs, const char* pool, const int64_t* off, int32_t* o_ok) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= npairs) return;
     if (off[i] < 0) { o_ok[i] = -1; return; }
-    AlignCheck K;
-    K.ap = P.asc_p + P.asc_p_off[i]; K.at = P.asc_t + P.asc_t_off[i];
-    K.m = P.p_len[i]; K.n = P.t_len[i];
-    const char* q = pool + off[i];
-    int64_t num = 0; bool have = false;
-    for (;; ++q) {
-        const char c = *q;
-        if (c == 0) break;
-        if (c >= '0' && c <= '9') { num = num * 10 + (c - '0'); have = true; if (num > 0x7fffffff) { K.ok = false; break; } continue; }
-        int op = -1;
-        if (c == 'M' || c == '=') op = (int)OP_M; else if (c == 'X') op = (int)OP_X;
-        else if (c == 'I') op = (int)OP_I; else if (c == 'D') op = (int)OP_D;
-        if (op < 0 || !have || num == 0) { K.ok = false; break; }
-        K.apply(op, (int)num);
-        num = 0; have = false;
-    }
-    if (have) K.ok = false;                 // digits without an operation
+    AlignCheck K = check_of_pair(P, i);
+    check_walk_string(K, pool + off[i]);
     o_ok[i] = K.verdict();
 }
 

@@ -1,11 +1,12 @@
 // Host stand-ins for the kernels of quicked_amd/csrc/qe_kernels.hip, for the sanitizer build of the library's HOST layer
 // (see hip/hip_runtime.h next to this file).  The kernels the host logic depends on for its control flow are real code here
-// (in-stream copies, the offsets scan, the stage-1 rule, the cut-off hand-over); the alignment kernels leave plausible
+// (in-stream copies, the offsets scan, the stage-1 rule, the cut-off hand-over, the CIGAR validator); the alignment kernels leave plausible
 // zeros -- a bound of `QE_STUB_BOUND` and, for every `QE_STUB_SKIP_EVERY`-th task, the "goes on to stage 2" flag, so that
 // the fast flow's overflow path, the early-finish threads and the merged flows all get work.  TEST INFRASTRUCTURE.
 #pragma once
 #include <algorithm>
 #include "qe_types.h"
+#include "qe_check.h"
 
 namespace qe {
 
@@ -105,8 +106,40 @@ template <bool WRITE> static void k_format_segs(SegFormatArgs A) {
     }
 }
 template <bool WRITE> static void k_format_segs_wave(SegFormatArgs A) { k_format_segs<WRITE>(A); }
-static void k_check_segs(SegCheckArgs C) { for (int i = 0; i < C.F.npairs; ++i) C.o_ok[i] = 1; }
-static void k_check_strings(PairView, int npairs, const char*, const int64_t*, int32_t* o_ok) { for (int i = 0; i < npairs; ++i) o_ok[i] = 1; }
+// The validator: the walk of qe_check.h, the kernels' own source, one alignment after the other -- real verdicts (of the
+// stand-in alignments above: no runs, so 0 for every pair that has bases)
+struct StubRuns {                  // a leaf's runs in either layout (run_view, qe_kernels.hip)
+    const SegFormatArgs& A; const u32* base = nullptr; int64_t stride = 1;
+    void open(int t) {
+        const int g = t >> 6, lane = t & 63;
+        if (A.runs_by_task) { base = A.runs + A.g_runs_off[g] + (int64_t)lane * A.g_runs_cap[g]; stride = 1; }
+        else { base = A.runs + A.g_runs_off[g] + lane; stride = 64; }
+    }
+    u32 at(int k) const { return base[(int64_t)k * stride]; }
+};
+static AlignCheck stub_check_of_pair(const PairView& P, int pair) {
+    AlignCheck K;
+    K.ap = P.asc_p + P.asc_p_off[pair]; K.at = P.asc_t + P.asc_t_off[pair];
+    K.m = P.p_len[pair]; K.n = P.t_len[pair];
+    return K;
+}
+static void k_check_segs(SegCheckArgs C) {
+    const SegFormatArgs& A = C.F;
+    for (int i = 0; i < A.npairs; ++i) {
+        AlignCheck K = stub_check_of_pair(C.P, C.root_pair[i]);
+        StubRuns R{A};
+        check_walk_segments(K, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
+        C.o_ok[i] = K.verdict();
+    }
+}
+static void k_check_strings(PairView P, int npairs, const char* pool, const int64_t* off, int32_t* o_ok) {
+    for (int i = 0; i < npairs; ++i) {
+        if (off[i] < 0) { o_ok[i] = -1; continue; }
+        AlignCheck K = stub_check_of_pair(P, i);
+        check_walk_string(K, pool + off[i]);
+        o_ok[i] = K.verdict();
+    }
+}
 static void k_pack(PackArgs A) { if (A.flags) for (int i = 0; i < A.nseq; ++i) A.flags[i] |= 0u; }
 static void k_unpack_wire(WireArgs) {}
 static void k_reverse_planes(RevArgs) {}

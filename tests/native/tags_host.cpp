@@ -3,7 +3,8 @@
 // empty operation sequence -- statistics of zeros, MD "0" -- which the host stand-ins of the tag kernels (qe_stages.hip:
 // the walker of qe_tags.h) produce; what is checked is the host side around them: the pools and offsets of both branches
 // of fetch_alignments (few alignments: one copy launch; many: the arrays and one D2H of the MD pool), the getters' rules,
-// NO_CIGAR, and that tags 0 leaves no tag data.  Built and run by tests/test_host_tags.py with -fsanitize=address,undefined.
+// NO_CIGAR, and that tags 0 leaves no tag data; and the validator's entry points (validator_scenario).  Built and run by tests/test_host_tags.py with -fsanitize=address,undefined.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -95,8 +96,52 @@ static void scenario(int n, int len, int algo) {
     quicked_batch_destroy(b);
 }
 
+// The validator's host stand-ins run the walk of qe_check.h (tests/native/hip_stub/qe_kernels_stub.h), so the host-only build
+// gives real verdicts: quicked_batch_validate end to end -- pool and offsets up, verdicts down -- and the in-run form on the
+// stub's alignments, which have no runs and so consume nothing.
+static void validator_scenario() {
+    const char* pat[] = {"ACGTACG", "ACGT", "ACGT", "ACGTACG", "ACG", "ACGTACG", "ACGTACGTAC"};
+    const char* txt[] = {"ACGTACG", "ACGA", "ACGA", "ACGTACG", "ACGG", "ACGTACG", "ACGTACGTAC"};
+    const char* str[] = {"7M", "3M1X", "4M", nullptr, "3M1I", "2147483647I2147483647I2I7M", "0000000010="};
+    const int32_t want[] = {1, 1, 0, -1, 1, 0, 1};
+    const int n = 7;
+    Pairs P;
+    P.n = n;
+    std::string pool;
+    std::vector<int64_t> off;
+    for (int i = 0; i < n; ++i) {
+        P.po.push_back((int64_t)P.pp.size()); P.to.push_back((int64_t)P.tp.size());
+        P.pp += pat[i]; P.tp += txt[i];
+        P.pl.push_back((int32_t)strlen(pat[i])); P.tl.push_back((int32_t)strlen(txt[i]));
+        if (!str[i]) { off.push_back(-1); continue; }
+        off.push_back((int64_t)pool.size());
+        pool.append(str[i]); pool.push_back('\0');
+    }
+    quicked_batch_t* b = quicked_batch_create(P.n, P.pp.data(), P.po.data(), P.pl.data(), P.tp.data(), P.to.data(), P.tl.data());
+    CHECK(b);
+    std::vector<int32_t> ok((size_t)n, 7);
+    CHECK(quicked_batch_validate(b, pool.data(), (int64_t)pool.size(), off.data(), ok.data()) == QUICKED_OK);
+    for (int i = 0; i < n; ++i) CHECK(ok[(size_t)i] == want[i]);
+    // the last terminator left out; an offset at the end of the pool: an error that writes nothing
+    CHECK(quicked_batch_validate(b, pool.data(), (int64_t)pool.size() - 1, off.data(), ok.data()) == QUICKED_OK);
+    for (int i = 0; i < n; ++i) CHECK(ok[(size_t)i] == want[i]);
+    std::fill(ok.begin(), ok.end(), 7);
+    off[2] = (int64_t)pool.size();
+    CHECK(quicked_batch_validate(b, pool.data(), (int64_t)pool.size(), off.data(), ok.data()) == QUICKED_ERROR);
+    for (int i = 0; i < n; ++i) CHECK(ok[(size_t)i] == 7);
+    // in-run: an alignment without operations is valid for no pair that has bases
+    quicked_params_t p = quicked_default_params();
+    p.algo = BANDED;
+    CHECK(quicked_batch_configure(b, 0, 1) == QUICKED_OK);
+    CHECK(quicked_batch_run(b, &p, 1) >= 0);
+    CHECK(quicked_batch_check_results(b, ok.data()) == QUICKED_OK);
+    for (int i = 0; i < n; ++i) CHECK(ok[(size_t)i] == 0);
+    quicked_batch_destroy(b);
+}
+
 int main() {
     CHECK(quicked_batch_configure_tags(nullptr, 1) == QUICKED_ERROR);
+    validator_scenario();
     for (int algo : {(int)QUICKED, (int)BANDED, (int)WINDOWED, (int)HIRSCHBERG}) {
         scenario(5, 300, algo);             // few alignments: everything in one copy launch
         scenario(9000, 120, algo);          // many: the per-root arrays, then one D2H of the MD pool

@@ -1,7 +1,8 @@
 """Alignment tags on the host: format_segments / fetch_alignments with the tag arrays and the MD pool, the getters' rules and
 NO_CIGAR, built with g++ against the fake HIP runtime of tests/native/hip_stub (as tests/test_host_sanitizers.py builds the
 host layer; the tag kernels' host stand-ins of qe_stages.hip run the walker of qe_tags.h) under AddressSanitizer + UBSan,
-driven by tests/native/tags_host.cpp through the C-ABI.  No GPU."""
+driven by tests/native/tags_host.cpp through the C-ABI; the same program drives the validator's entry points, whose host stand-ins
+run the walk of qe_check.h.  No GPU."""
 import os
 import shutil
 import subprocess
