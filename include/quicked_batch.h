@@ -120,6 +120,43 @@ quicked_status_t quicked_batch_run(quicked_batch_t* batch, const quicked_params_
  * itself (its alignment's edit count), on the host's schedule: when a sync != 0 run ends, or in the fetch. */
 quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const int32_t* max_dist, int32_t max_dist_all,
                                            int only_score, int sync);
+/* Approximate pattern search: "where in this text does the pattern fit best, and at what cost?" -- edlib's SHW (prefix) and HW
+ * (infix) modes.  D is the edit-distance matrix of pair i's pattern (rows, m) against its text (columns, n) under the library's
+ * own equality (case folded, every non-ACGT byte one symbol: two symbols are equal when both are non-ACGT or when their codes
+ * agree).  QUICKED_SEARCH_INFIX has a top row of zeros (the pattern may start anywhere in the text),
+ * QUICKED_SEARCH_PREFIX has D[0][j] = j (it starts at the text's start).  The result of pair i:
+ *   score      d = min over e in 1 .. n of D[m][e]
+ *   text_end   the smallest such e; exclusive: the located stretch is text[text_start, text_end)
+ *   text_start 0 for PREFIX; for INFIX the smallest s < text_end for which the global distance of the pattern against
+ *              text[s, text_end) equals d -- the longest stretch
+ * which is edlib's editDistance, endLocations[0] + 1 and startLocations[0] with EDLIB_TASK_LOC; where edlib reports the end
+ * location -1 (d == m: "the pattern before the text") the rule above is the definition.
+ * Bounds as in quicked_batch_run_bounded: pair i's bound is max_dist[i] (n values, read during the call) or, where max_dist is
+ * NULL, max_dist_all; it is clamped to m, which no search distance exceeds, so INT32_MAX means "no bound".  d > bound: the
+ * pair is "beyond" -- score -1 with the status QUICKED_OK, both locations -1, no CIGAR.  Empty sequences keep
+ * QUICKED_EMPTY_SEQUENCE (locations -1); a NULL batch, an unknown mode or a negative bound: QUICKED_ERROR, nothing is launched.
+ * ASCII and packed batches alike.
+ * only_score != 0 with sync == 0 queues the run like quicked_batch_run does; quicked_batch_fetch brings scores and locations.
+ * only_score == 0 needs sync != 0 (sync == 0: QUICKED_UNIMPLEMENTED, nothing is queued, as a queued bounded CIGAR run): every
+ * pair within its bound gets the CIGAR of the global alignment of the pattern against its located stretch, with exactly d
+ * edits, in the style of quicked_batch_configure (a status other than QUICKED_OK on a located pair means its alignment failed:
+ * the score and the locations stand, the CIGAR does not).  The alignment tags of quicked_batch_configure_tags apply unchanged -- they
+ * read the alignment and the whole pattern -- with one difference in the identities of quicked_pair_stats_t:
+ *   matches + mismatches + ins_bases == text_end - text_start   (the stretch, not text_len).
+ * The in-run validator walks the text from its origin: a search run on a batch configured with check != 0 returns
+ * QUICKED_UNIMPLEMENTED and queues nothing.  Pairs with lower-case / IUPAC bytes are scored and located like every other
+ * pair, but in a CIGAR run they get no alignment (cigar_off -1, statistics of all -1, md_off -1): the traceback compares raw
+ * bytes, so the edit count of their CIGAR would not be d.
+ * Two kernel forms, one lane per pair: the workspace form for any pattern length (the library's choice), and a form that
+ * keeps the whole state of a pattern of up to 256 bases in registers; QE_SEARCH_FORM=0 the workspace form always, 1 the
+ * register form wherever it applies.
+ * quicked_batch_locations: text_start / text_end (n values each, either may be NULL) of the last sync != 0 search run or of
+ * the fetch of a queued one; QUICKED_ERROR after any run that was not a search run, as the tag getters. */
+typedef enum { QUICKED_SEARCH_PREFIX = 1, QUICKED_SEARCH_INFIX = 2 } quicked_search_mode_t;
+quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mode,
+                                          const int32_t* max_dist, int32_t max_dist_all,
+                                          int only_score, int sync);
+quicked_status_t quicked_batch_locations(quicked_batch_t* batch, int32_t* text_start, int32_t* text_end); /* n each */
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read
@@ -208,7 +245,7 @@ quicked_status_t quicked_batch_validate(quicked_batch_t* batch, const char* ciga
                                         const int64_t* cigar_off, int32_t* ok_out);
 
 /* counters of the last run, for the measurement harness:
- *   [0] block-advances of score-only BandEd passes   [1] of fills
+ *   [0] block-advances of score-only BandEd passes (a search run: the block steps of its search passes)   [1] of fills
  *   [2] WindowEd block steps   [3] traceback steps   [4] CIGAR ops
  *   [5] last kernel-only time in ns (HIP events on the batch's stream)
  *   [6] pairs that went past stage 1   [7] pairs that went past stage 2
@@ -246,7 +283,7 @@ quicked_status_t quicked_pool_trim(void);
  * fill) over the runs of this thread since the previous call, and how many
  * launches that was; synchronises the batch's stream. */
 quicked_status_t quicked_batch_kernel_time(quicked_batch_t* batch, double* ms_sum, int64_t* launches);
-/* The same by kind of launch: [0] score-only BandEd passes (a BANDED run, QuickEd's stage 3), [1] fills, [2] the half passes of
+/* The same by kind of launch: [0] score-only BandEd passes (a BANDED run, QuickEd's stage 3; the passes of a search run), [1] fills, [2] the half passes of
  * Hirschberg's split levels (bpm_hirschberg.c:85-100; the dominant launches of long reads), [3] diagonal-word launches of bounded
  * runs (quicked_batch_run_bounded; 0 in every other run). */
 quicked_status_t quicked_batch_kernel_times(quicked_batch_t* batch, double ms_sum[4], int64_t launches[4]);

@@ -59,10 +59,11 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_wire_words", "quicked_wire_pack", "quicked_batch_create_packed",
            "quicked_batch_reload", "quicked_batch_reload_packed", "quicked_batch_fetch", "quicked_pool_stats", "quicked_batch_cigar_view",
            "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats",
-           "quicked_batch_run_bounded",
+           "quicked_batch_run_bounded", "quicked_batch_run_search", "quicked_batch_locations",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
+SEARCH_PREFIX, SEARCH_INFIX = 1, 2
 
 _LIB = None
 
@@ -104,6 +105,10 @@ def lib():
     L.quicked_batch_run.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int]
     L.quicked_batch_run_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int]
     L.quicked_batch_run_bounded.restype = C.c_int
+    L.quicked_batch_run_search.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_int, C.c_int]
+    L.quicked_batch_run_search.restype = C.c_int
+    L.quicked_batch_locations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_locations.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -340,6 +345,29 @@ class ResidentBatch:
         if md.shape != (self.n,):
             raise ValueError("max_dist: one bound per pair")
         return self._lib.quicked_batch_run_bounded(self._h, md.ctypes.data, 0, 1 if only_score else 0, 1 if sync else 0)
+
+    def run_search(self, mode, max_dist=None, only_score=True, sync=True):
+        """quicked_batch_run_search: where the pattern fits the text best (SEARCH_PREFIX: from the text's start, SEARCH_INFIX:
+        anywhere) and at what cost.  max_dist: None = no bound, one int for every pair, or an array of n bounds.
+        only_score=False (sync only): a CIGAR of the pattern against text[start:end] for every pair within its bound."""
+        if max_dist is None:
+            max_dist = 2**31 - 1
+        if np.ndim(max_dist) == 0:
+            return self._lib.quicked_batch_run_search(self._h, int(mode), None, int(max_dist), 1 if only_score else 0, 1 if sync else 0)
+        md = np.ascontiguousarray(max_dist, dtype=np.int32)
+        if md.shape != (self.n,):
+            raise ValueError("max_dist: one bound per pair")
+        return self._lib.quicked_batch_run_search(self._h, int(mode), md.ctypes.data, 0, 1 if only_score else 0, 1 if sync else 0)
+
+    def locations(self):
+        """-> (text_start, text_end) int32 arrays of the last search run: the located stretch is text[start:end]; -1 / -1 for a
+        pair beyond its bound or with an empty sequence.  QuickedException after a run that was not a search run"""
+        ts = np.zeros(self.n, dtype=np.int32)
+        te = np.zeros(self.n, dtype=np.int32)
+        st = self._lib.quicked_batch_locations(self._h, ts.ctypes.data, te.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return ts, te
 
     def sync(self):
         return self._lib.quicked_batch_sync(self._h)

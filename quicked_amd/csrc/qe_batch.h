@@ -96,9 +96,12 @@ struct quicked_batch {
         std::vector<quicked_pair_stats_t> stats;
         std::vector<int64_t> md_off;
         PinnedBuf md_pool;
+        // search runs (quicked_batch_run_search): [n] after such a run, else empty; -1 / -1 for a pair that is beyond its bound
+        // or has an empty sequence
+        std::vector<int32_t> text_start, text_end;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -111,6 +114,7 @@ struct quicked_batch {
     // ... of the run in progress: `tags` for a sync != 0 run that aligns, else 0 (run_batch) -- what format_segments and the
     // host-driven flows of that run read, whatever the caller configures meanwhile
     int run_tags = 0;
+    bool search_run = false;                      // the run in progress is a search run: its results carry locations (reset_host_results)
     // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
     bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)
@@ -188,7 +192,9 @@ inline bool trace_on() { return sw_set(Sw::Trace); }
 // bd != nullptr: a bounded run (quicked_batch_run_bounded): pair i's bound is bd->max_dist[i], or bd->max_dist_all where that is
 // null; p is the default BANDED parameter block with the caller's only_score
 struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
-quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr);
+// sr != nullptr: a search run (quicked_batch_run_search) in `mode` (QUICKED_SEARCH_*), bounds as in a bounded run; p as there
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; };
+quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr, const SearchRun* sr = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);
 // (re)loads a batch object with n pairs: host-side layout, arena (kept when it is large enough), H2D

@@ -215,6 +215,30 @@ QE_API quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const 
     }, &arg);
 }
 
+// Pattern search: the arguments are checked before anything touches the device
+QE_API quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mode, const int32_t* max_dist, int32_t max_dist_all,
+                                                 int only_score, int sync) {
+    if (!batch || (mode != QUICKED_SEARCH_PREFIX && mode != QUICKED_SEARCH_INFIX) || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    struct Arg { SearchRun sr; int only_score, sync; } arg{{mode, max_dist, max_dist_all}, only_score, sync};
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        if (x->sr.max_dist) for (int64_t i = 0; i < B->n; ++i) if (x->sr.max_dist[i] < 0) return QUICKED_ERROR;
+        if (B->check) return QUICKED_UNIMPLEMENTED;                         // the in-run validator walks the text from its origin
+        if (!x->only_score && !x->sync) return QUICKED_UNIMPLEMENTED;      // CIGARs need the locations on the host first
+        quicked_params_t p = quicked_default_params();
+        p.algo = BANDED;
+        p.only_score = x->only_score != 0;
+        return run_batch(*B, p, x->sync != 0, nullptr, &x->sr);
+    }, &arg);
+}
+
+QE_API quicked_status_t quicked_batch_locations(quicked_batch_t* batch, int32_t* text_start, int32_t* text_end) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].text_end.size() != (size_t)batch->n) return QUICKED_ERROR;
+    if (text_start) memcpy(text_start, batch->res[batch->vis].text_start.data(), (size_t)batch->n * sizeof(int32_t));
+    if (text_end) memcpy(text_end, batch->res[batch->vis].text_end.data(), (size_t)batch->n * sizeof(int32_t));
+    return QUICKED_OK;
+}
+
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {
     return guard(batch, [](quicked_batch* B, void*) {
         tl_device = B->device;

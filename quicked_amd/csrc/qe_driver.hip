@@ -33,6 +33,7 @@
 #include "qe_pool.h"
 #include "qe_batch.h"
 #include "qe_bounded.h"
+#include "qe_search.h"
 #include "qe_tags.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
 // without a GPU names tests/native/hip_stub/qe_kernels_stub.h here -- tests/test_host_sanitizers.py; never set in the product)
@@ -607,6 +608,7 @@ static void stash_results(quicked_batch& B, Context& C, PendingFetch& F) {
     const size_t nt = F.task_pair.size(), nr = F.AO.nroots, nl = F.leaf_pair.size(), nq = F.L.pair.size();
     stash_add(items, F.d_score, nt * 4); stash_add(items, F.d_adv, nt * 4); stash_add(items, F.d_steps, nt * 4); stash_add(items, F.d_abort, nt * 4);
     stash_add(items, F.d_narrow, QE_NARROW_STAT * sizeof(unsigned long long));
+    stash_add(items, F.d_start, nt * 4); stash_add(items, F.d_end, nt * 4);
     if (F.kind == 2) {
         stash_add(items, F.AO.len, nr * 4); stash_add(items, F.AO.edits, nr * 4); stash_add(items, F.AO.nops, nr * 4);
         stash_add(items, F.AO.ok, nr * 4); stash_add(items, F.AO.str_off, nr * 8);
@@ -663,7 +665,7 @@ static int rotation_depth(int64_t n, int floor_sets = 5) {
 
 static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 
-quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd) {
+quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd, const SearchRun* sr) {
     double tr_last = now_ms();
     tl_device = B.device;
     Context& C = ctx();
@@ -707,10 +709,14 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
             const int m = B.p_len[(size_t)i], n = B.t_len[(size_t)i];
             if (m == 0 || n == 0) continue;
             // (a bounded run aligns with cutoff = the distance it found, which is within the pair's bound)
-            const HGeom G = host_geometry(m, n, bd ? bounded_effective(std::max(0, bounded_bound(*bd, (int)i)), m, n) : max_cutoff(p.bandwidth, m, n));
+            // (a search run aligns the pattern against its located stretch -- at most m + d bases -- with cutoff = d <= min(bound, m):
+            // planned from the pattern lengths)
+            const int se = sr ? search_effective(std::max(0, search_bound(*sr, (int)i)), m) : 0;
+            const HGeom G = sr ? host_geometry(m, std::min(n, m + se), se)
+                               : host_geometry(m, n, bd ? bounded_effective(std::max(0, bounded_bound(*bd, (int)i)), m, n) : max_cutoff(p.bandwidth, m, n));
             const uint64_t full = (uint64_t)(QE_CPC + 1) * (uint64_t)(n / 64 + 3) * (uint64_t)G.ebb * 16;
             need_mat += (size_t)std::min<uint64_t>(full, (uint64_t)18 << 20);             // per pair; splits cap a leaf at 16 MiB of matrix
-            need_fixed += (size_t)((p.algo == QUICKED || bd) ? std::min<int64_t>((int64_t)m + n + 2, (int64_t)2 * G.cutoff + 8) : (int64_t)m + n + 2) * 15 + 512;
+            need_fixed += (size_t)((p.algo == QUICKED || bd || sr) ? std::min<int64_t>((int64_t)m + n + 2, (int64_t)2 * G.cutoff + 8) : (int64_t)m + n + 2) * 15 + 512;
         }
         need_groups = (int)((B.n + 63) / 64);
     }
@@ -795,6 +801,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     }
     B.only_score_run = p.only_score;
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
+    B.search_run = sr != nullptr;
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -845,12 +852,56 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     QE_TRACE_POINT("setup+pack launch");
     std::vector<int32_t> beyond;
     TaskList L, Ld, Lg;
-    if (bd) bounded_pairs(B, *bd, beyond, Ld, Lg); else L = all_pairs(B, p);
+    SearchLists SLs;
+    if (sr) search_pairs(B, *sr, SLs); else if (bd) bounded_pairs(B, *bd, beyond, Ld, Lg); else L = all_pairs(B, p);
     QE_TRACE_POINT("task list");
-    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty()) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
+    bool no_search_task = true;
+    for (const TaskList& l : SLs.L) no_search_task = no_search_task && l.pair.empty();
+    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
     StageResult R;
 
-    if (bd) {
+    if (sr) {
+        // Search run: the forward pass and -- INFIX -- the start pass leave {d, text_start, text_end} per task on the device;
+        // with CIGARs wanted every pair within its bound is then aligned against its located stretch with cutoff = d -- exact,
+        // so the run buffers are tight (the path bounded CIGAR runs take).  Pairs with lower-case / IUPAC bytes are scored and
+        // located like the others but get no alignment: the traceback compares raw bytes, its edit count would not be d
+        enter_a();
+        const SearchOut SO = run_search(B, C, SLs, sr->mode);
+        B.d_score = SO.d_score;
+        if (pf) {
+            pf->kind = 1; pf->task_pair = SO.task_pair; pf->d_score = SO.d_score; pf->d_adv = SO.d_adv; pf->counter_slot = 0;
+            pf->ok_status = QUICKED_OK; pf->search = true; pf->d_start = SO.d_start; pf->d_end = SO.d_end;
+        } else {
+            const size_t nt = SO.task_pair.size();
+            std::vector<int32_t> sc, ts, te; std::vector<u32> adv, flags;
+            {
+                FetchBatch fb(C);
+                fb.add(sc, (const int32_t*)SO.d_score, nt); fb.add(ts, (const int32_t*)SO.d_start, nt); fb.add(te, (const int32_t*)SO.d_end, nt);
+                fb.add(adv, (const u32*)SO.d_adv, nt);
+                if (!B.packed && !p.only_score) fb.add(flags, (const u32*)B.d_flags[par], (size_t)B.n);
+                fb.sync();
+            }
+            B.counters[0] = (int64_t)sum_u32(adv);
+            TaskList LA;
+            for (size_t t = 0; t < nt; ++t) {
+                const int pr = SO.task_pair[t];
+                if (pr < 0) continue;
+                B.wr->score[pr] = sc[t]; B.wr->status[pr] = QUICKED_OK;
+                B.wr->text_start[pr] = ts[t]; B.wr->text_end[pr] = te[t];
+                if (p.only_score || sc[t] < 0 || (!flags.empty() && (flags[(size_t)pr] & FLAG_NONCANON))) continue;
+                LA.push(pr, 0, B.p_len[pr], ts[t], te[t] - ts[t], sc[t], te[t] - ts[t]);
+            }
+            if (!LA.pair.empty()) {
+                AlignStats AS;
+                run_align(B, C, LA, true, want_cigar, matrix_budget, split_threshold(), QUICKED_OK, &B.d_score, &AS, nullptr, true);
+                C.phase_a();
+                B.counters[1] = (int64_t)AS.fill_adv; B.counters[3] = (int64_t)AS.tb_steps;
+                // (a split that does not converge keeps QUICKED_FAIL_NON_CONVERGENCE here, unlike in a bounded run: with cutoff = d
+                // the halves must add up to d, so that status would mean the search passes and the aligner disagree -- not to be hidden)
+            }
+        }
+        ret = QUICKED_OK;
+    } else if (bd) {
         // Bounded run: the score pass (diagonal word / general path) gives every task "d, or -1 = beyond"; with CIGARs wanted
         // the pairs found within their bound are then aligned with cutoff = d -- exact, so the run buffers are tight
         enter_a();
@@ -1038,14 +1089,16 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     B.pending_fetch.reset();
     HIP_CHECK(B.done_sync(F.parity));
     C.phase_u();
+    B.search_run = F.search;
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {
         const size_t nt = F.task_pair.size();
-        std::vector<int32_t> sc, ab; std::vector<u32> w; std::vector<unsigned long long> nar;
+        std::vector<int32_t> sc, ab, ts, te; std::vector<u32> w; std::vector<unsigned long long> nar;
         {
             FetchBatch fb(C);
             fb.add(sc, F.d_score, nt);
+            if (F.search) { fb.add(ts, F.d_start, nt); fb.add(te, F.d_end, nt); }
             if (F.d_adv) fb.add(w, F.d_adv, nt); else if (F.d_steps) fb.add(w, F.d_steps, nt);
             if (F.d_abort) fb.add(ab, F.d_abort, nt);
             if (F.d_narrow) fb.add(nar, F.d_narrow, QE_NARROW_STAT);
@@ -1056,6 +1109,7 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
             const int pr = F.task_pair[t];
             if (pr < 0) continue;
             B.wr->score[pr] = sc[t]; B.wr->status[pr] = F.ok_status;
+            if (F.search) { B.wr->text_start[pr] = ts[t]; B.wr->text_end[pr] = te[t]; }
         }
         for (int32_t pr : F.beyond_pair) B.wr->status[pr] = F.ok_status;
         if (!F.pair_bound.empty() && !B.packed) {

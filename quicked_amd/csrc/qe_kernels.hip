@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include "qe_types.h"
 #include "qe_bounded.h"
+#include "qe_search.h"
 #include "qe_tags.h"
 #include "qe_check.h"
 
@@ -1196,6 +1197,89 @@ __global__ __launch_bounds__(256) void k_bounded_threshold(int nt, const int32_t
     o_score[t] = bounded_answer(score[t], bound[t]);
     o_adv[t] = adv[t];
 }
+
+// ===========================================================================
+// Approximate pattern search (qe_search.h; quicked_batch_run_search): Myers' column sweep under a free (INFIX) or counted
+// (PREFIX) top row, one lane per task, whole pairs.  A lane walks its text in chunks of 64 columns; per chunk the live-block
+// rule decides which blocks of 64 pattern rows it computes, top-down, each handing the horizontal deltas of its last row to
+// the block below as two carry words; row m's deltas give the end-position scan its 64 values.
+//   NB > 0, the register form: patterns of up to NB blocks -- {Pv, Mv, S} and the pattern planes of every block stay in
+//   registers for the whole pair (every index a constant after unrolling): no workspace, nothing written but the result.
+//   Memory traffic per chunk: the text's three plane words.
+//   NB == 0, the workspace form: any pattern length; {Pv, Mv, S} per block live in the group's workspace [block][64 lanes]
+//   (a wave's accesses to one block are one contiguous row), the pattern planes of a block are read again every chunk.
+// Lanes of a wave differ in m, n and live blocks; the wave leaves the chunk loop at the end of its longest text, or when
+// every lane has its answer (an exact occurrence: nothing later can be better).
+// The start pass of an INFIX run is the PREFIX form over the reversed planes (SearchArgs::in_score).
+// ===========================================================================
+#define QE_HAVE_K_SEARCH 1
+template <int NB>
+__global__ __launch_bounds__(256) void k_search(SearchArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
+    if (g * 64 >= A.T.ntasks) return;
+    const int pair = (t < A.T.ntasks) ? A.T.pair[t] : -1;
+    bool valid = pair >= 0;
+    int m = 1, n = 0, bound = 0, in_end = 0;
+    int64_t tbit = 0;
+    const u64* pp = A.P.pl_p;
+    const u64* tp = A.P.pl_t;
+    if (valid) {
+        m = A.T.m[t]; n = A.T.n[t]; bound = A.T.cutoff[t];
+        if (A.in_score) {                                      // the start pass: the n = text_end columns that end at text_end, reversed
+            bound = A.in_score[t]; in_end = A.in_end[t];
+            valid = bound >= 0 && in_end >= 1 && in_end <= n;
+            tbit = n - in_end; n = in_end;
+        }
+    }
+    const int nbg = (NB == 0) ? A.g_nb[g] : NB;
+    valid = valid && search_blocks(m) <= nbg;                  // (the host lays the groups out so; never index past the store)
+    if (!__any(valid)) return;
+    SearchLane L;
+    search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, A.flags);
+    if (valid) { pp = A.P.pl_p + A.P.pl_p_off[pair]; tp = A.P.pl_t + A.P.pl_t_off[pair]; }
+    SearchRegStore<(NB > 0 ? NB : 1)> R;
+    SearchWsStore W;
+    if constexpr (NB > 0) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = R.pa[b] = R.pb[b] = R.pn[b] = 0; R.s[b] = 0; }
+        if (valid) { R.load(pp, m); search_store_init<NB>(R, L); }
+    } else {
+        uint8_t* base = A.ws + A.g_ws_off[g];
+        W.pv = (u64*)base + lane; W.mv = (u64*)base + (int64_t)nbg * 64 + lane;
+        W.s = (int32_t*)((u64*)base + (int64_t)2 * nbg * 64) + lane;
+        W.stride = 64; W.pp = pp; W.m = m;
+        if (valid) search_store_init<0>(W, L);
+    }
+    const int my_chunks = valid ? (n + 63) >> 6 : 0;
+    const int wave_chunks = wave_max(my_chunks);
+    for (int c = 0; c < wave_chunks; ++c) {
+        const bool live = c < my_chunks && L.k >= 0;
+        if (!__any(live)) break;
+        if (live) {
+            const int col0 = 64 * c, ncols = min(64, n - col0);
+            u64 T0, T1, TN;
+            search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
+            if constexpr (NB > 0) search_chunk<NB>(R, L, T0, T1, TN, col0, ncols);
+            else search_chunk<0>(W, L, T0, T1, TN, col0, ncols);
+        }
+    }
+    if (pair >= 0) {
+        int32_t score, end;
+        search_answer(L, score, end);
+        if (!valid) { score = -1; end = -1; }
+        if (A.in_score) {
+            if (valid) A.o_start[t] = (score == bound) ? in_end - end : -1;
+        } else {
+            A.o_score[t] = score; A.o_end[t] = end;
+            A.o_start[t] = (score >= 0 && A.mode == SEARCH_PREFIX) ? 0 : -1;
+        }
+        A.o_adv[t] += L.steps;                                 // one block step per block per column, both passes
+    }
+}
+template __global__ void k_search<0>(SearchArgs);
+template __global__ void k_search<1>(SearchArgs);
+template __global__ void k_search<2>(SearchArgs);
+template __global__ void k_search<4>(SearchArgs);
 
 
 // ===========================================================================

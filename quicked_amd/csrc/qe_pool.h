@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, ScoreMasked, TagsWave, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, ScoreMasked, TagsWave, SearchForm, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -111,6 +111,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::NarrowFit, "QE_NARROW_FIT", -1},              // ... their first pass: -1 the fewest slots that prove the distances the class's last runs saw (narrow_fit_q), 0 always half the cutoff, k > 0 fitted to k / 1024 of every cutoff whatever ran before (tests)
     {Sw::ScoreMasked, "QE_SCORE_MASKED", 1},           // k_banded<false>'s multi-slot passes: 1 every lane with the slots of the pass inside its band (pass_plan), 0 with all of them or none (the rule before it, pass for pass)
     {Sw::TagsWave, "QE_TAGS_WAVE", -1},                // alignment tags (quicked_batch_configure_tags): -1 the wave form where the CIGAR formatter takes its own (tags_wave_wanted), 0 / 1 the lane / wave form everywhere (tests)
+    {Sw::SearchForm, "QE_SEARCH_FORM", -1},            // search runs (quicked_batch_run_search): -1 the library's choice (search_reg_form: the workspace form), 0 the workspace form always, 1 the register form wherever it applies (patterns of up to 256 bases)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {

@@ -1,0 +1,250 @@
+// qe_search.h -- approximate pattern search: "where in this text does the pattern fit best, and at what cost?"
+// (quicked_batch_run_search).  Plain C++ with no HIP dependency: k_search<NB> (qe_kernels.hip; NB > 0 the register form, 0 the workspace form) runs it one lane
+// per task, the host stand-ins of the stub build run it on the host, and the CPU suite compiles the very same source with
+// g++ (tests/native/search_cpu.cpp) and checks it against a brute-force DP and edlib's HW / SHW modes.
+//
+// The matrix.  D is the edit-distance matrix of the pattern (rows, m) against the text (columns, n) under the library's
+// equality (two symbols are equal when both are not-ACGT, or neither is and the code bits agree; qe_bounded.h).  INFIX has
+// a top row of zeros -- an occurrence may start in any column --, PREFIX has D[0][j] = j.  The answer is
+//   d = min over e in 1 .. n of D[m][e],   end = the smallest such e   (SEARCH_LARGEST_END: the largest),
+// or "beyond" (-1, -1) when d exceeds the task's bound.  SEARCH_LAST_COLUMN reads column n only: with PREFIX that is the
+// global distance.  No search distance exceeds m (D[m][1] <= m), so the bound is clamped to m.
+//
+// The sweep.  Myers' column sweep in the tree's carry-word convention, over blocks of 64 pattern rows and
+// chunks of 64 text columns: a block over a chunk takes the horizontal deltas of the row above it as two 64-bit words (bit
+// c = column c of the chunk) and leaves those of its last row.  The top block's carry-in is zero for INFIX and all-plus for
+// PREFIX.  The last block takes the RAW, pre-shift deltas at bit (m - 1) & 63 -- row m's -- instead of bit 63's: the rows
+// of that block below row m hold zero planes and garbage values that never reach a row above them (every cell depends on
+// rows at or above its own only, and the carry of the addition runs towards higher rows).
+//
+// The live-block rule, one decision per chunk.  k = the task's current bound, S_b = the computed value of block b's last
+// row in the chunk's start column (column 64 c; column 0 before the first chunk, where S_b = min(64 (b + 1), m)).  The
+// chunk computes blocks 0 .. L + 1, L = the lowest-lying computed block with S_b <= k + 63 (-1: none; block 0 is always
+// computed: a new occurrence can start in any column).  A block that (re)enters starts from "the cell above + 1" in every
+// row -- Pv all ones, S = S_above + its rows --: stale state is never reused.  Why that loses no answer:
+//   * computed values are costs of real paths (a skipped block's cells are never read as cheaper than they are, an
+//     entering block's are a vertical run below a computed cell), so they are >= the true values;
+//   * they are exact wherever the true value is <= k: the cells of a path of cost <= k all have values <= k, and by
+//     induction over the chunks each of them lies in a computed block (last point);
+//   * computed vertical deltas are in {-1, 0, 1}, so a block holding a cell <= k has S_b <= k + 63;
+//   * values never decrease along a diagonal, so a cell <= k within the next 64 columns lies at most 64 rows below a cell
+//     <= k of this column (or starts in row 0 and is in block 0): in block L + 1 at the lowest.
+// At most one block enters per chunk (L + 1 <= the blocks computed so far).  Lowering k to best - 1 once a result
+// best <= k is found keeps all of this -- a later column only matters when it is strictly better -- and makes "the smallest
+// end among the minima" free.  SEARCH_LARGEST_END keeps k = best instead.  SEARCH_ALL_LIVE computes every block of every
+// chunk (the form the rule is tested against).
+//
+// The end-position scan.  Row m's two delta words give its 64 values in the chunk from the value at the chunk's start; they
+// are scanned only when start - popcount(minus word) <= k.
+#pragma once
+#include <stdint.h>
+
+#include "qe_bounded.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define QE_S_HD __host__ __device__ __forceinline__
+#else
+#define QE_S_HD inline
+#endif
+
+namespace qe {
+
+enum : int { SEARCH_PREFIX = 1, SEARCH_INFIX = 2 };                               // quicked_search_mode_t
+enum : int { SEARCH_LARGEST_END = 1, SEARCH_LAST_COLUMN = 2, SEARCH_ALL_LIVE = 4 };
+enum : int { QE_SEARCH_REG_BLOCKS = 4 };                                          // the most blocks the register form holds
+
+QE_S_HD int search_popc(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popcll(x);
+#else
+    return __builtin_popcountll(x);
+#endif
+}
+// the bound a task is decided with: no search distance exceeds the pattern's length
+QE_S_HD int search_effective(int bound, int m) { return bound < m ? bound : m; }
+QE_S_HD int search_blocks(int m) { return (m + 63) >> 6; }
+QE_S_HD int search_rows(int b, int m) { const int r = m - 64 * b; return r < 64 ? r : 64; }      // rows of block b
+// blocks 0 .. L + 1 for "L = the last block of the first `have` with S <= k + 63" (at least the top block, at most nb)
+QE_S_HD int search_want(int L, int nb) { const int w = L + 2 < nb ? L + 2 : nb; return w < 1 ? 1 : w; }
+// blocks that are live before the first chunk: column 0 holds S_b = min(64 (b + 1), m)
+QE_S_HD int search_first_live(int k, int m, int flags) {
+    const int nb = search_blocks(m);
+    if (flags & SEARCH_ALL_LIVE) return nb;
+    int L = -1;
+    for (int b = 0; b < nb; ++b) if ((b + 1 < nb ? 64 * (b + 1) : m) <= k + 63) L = b;
+    return search_want(L, nb);
+}
+
+// 64 text columns starting at bit offset `bit` of a text's planes; words past the one that holds the chunk's last column
+// (bit + ncols - 1) are not read
+QE_S_HD void search_text_chunk(const uint64_t* tp, int64_t bit, int ncols, uint64_t& t0, uint64_t& t1, uint64_t& tn) {
+    const int64_t w = bit >> 6;
+    const int sh = (int)(bit & 63);
+    const uint64_t* q = tp + 3 * w;
+    t0 = q[0] >> sh; t1 = q[1] >> sh; tn = q[2] >> sh;
+    if (sh && ((bit + ncols - 1) >> 6) > w) { t0 |= q[3] << (64 - sh); t1 |= q[4] << (64 - sh); tn |= q[5] << (64 - sh); }
+}
+
+// One block over one chunk: Pv / Mv the block's vertical deltas, (a, b, nn) its pattern planes, (T0, T1, TN) the chunk's text
+// planes, hinP / hinM the horizontal deltas of the row above.  Leaves in oP / oM the raw horizontal deltas of the block's
+// row `lvl` (63: its last row = the carry words of the block below), bits >= ncols zero.
+QE_S_HD void search_block_chunk(uint64_t& Pv, uint64_t& Mv, uint64_t a, uint64_t b, uint64_t nn, uint64_t T0, uint64_t T1, uint64_t TN,
+                                uint64_t hinP, uint64_t hinM, int lvl, int ncols, uint64_t& oP, uint64_t& oM) {
+    uint64_t P = Pv, M = Mv, qP = 0, qM = 0;
+    for (int c = 0; c < ncols; ++c) {
+        const uint64_t m0 = (uint64_t)0 - ((T0 >> c) & 1), m1 = (uint64_t)0 - ((T1 >> c) & 1), mn = (uint64_t)0 - ((TN >> c) & 1);
+        const uint64_t acgt = ~(a ^ m0) & ~(b ^ m1) & ~nn;
+        const uint64_t Eq = (mn & nn) | (~mn & acgt);
+        const uint64_t PHin = (hinP >> c) & 1, MHin = (hinM >> c) & 1;
+        const uint64_t Xv = Eq | M;
+        const uint64_t Eqc = Eq | MHin;
+        const uint64_t Xh = (((Eqc & P) + P) ^ P) | Eqc;
+        uint64_t Ph = M | ~(Xh | P);
+        uint64_t Mh = P & Xh;
+        qP |= ((Ph >> lvl) & 1) << c;
+        qM |= ((Mh >> lvl) & 1) << c;
+        Ph = (Ph << 1) | PHin;
+        Mh = (Mh << 1) | MHin;
+        P = Mh | ~(Xv | Ph);
+        M = Ph & Xv;
+    }
+    Pv = P; Mv = M; oP = qP; oM = qM;
+}
+
+// what a lane carries besides its blocks' {Pv, Mv, S}
+struct SearchLane {
+    int32_t m, n, nb, mode, flags;
+    int32_t k;              // the current bound
+    int32_t live;           // blocks 0 .. live - 1 hold computed state
+    int32_t best, end;      // -1, -1: nothing within the bound yet
+    uint32_t steps;         // block steps (one per block per column)
+};
+
+QE_S_HD void search_lane_init(SearchLane& L, int m, int n, int mode, int bound, int flags) {
+    L.m = m; L.n = n; L.nb = search_blocks(m); L.mode = mode; L.flags = flags;
+    L.k = search_effective(bound, m);
+    L.live = search_first_live(L.k, m, flags);
+    L.best = -1; L.end = -1; L.steps = 0;
+}
+
+// row m's values in the chunk that starts at column col0 (0-based; its first column is end position col0 + 1)
+QE_S_HD void search_scan(SearchLane& L, int32_t start, uint64_t oP, uint64_t oM, int col0, int ncols) {
+    if (start - search_popc(oM) > L.k) return;
+    int32_t v = start;
+    for (int c = 0; c < ncols; ++c) {
+        v += (int32_t)((oP >> c) & 1) - (int32_t)((oM >> c) & 1);
+        if (v > L.k) continue;
+        if ((L.flags & SEARCH_LAST_COLUMN) && col0 + c + 1 != L.n) continue;
+        L.best = v; L.end = col0 + c + 1;
+        L.k = (L.flags & SEARCH_LARGEST_END) ? v : v - 1;
+    }
+}
+
+// The state of a lane's blocks.  NBT > 0: at most NBT blocks, every index a compile-time constant after unrolling (the
+// register form: arrays that stay in registers); NBT == 0: any number (the workspace form).  A store has
+//   uint64_t& P(int b), & M(int b);  int32_t& S(int b);  void planes(int b, uint64_t& a, uint64_t& b, uint64_t& nn)
+//
+// One chunk: text columns [col0, col0 + ncols) of the task, planes (T0, T1, TN).
+template <int NBT, class Store>
+QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols) {
+    constexpr int UF = NBT ? NBT : 1;                         // the register form unrolls over its blocks; the workspace form does not
+    (void)UF;
+    const int nbl = NBT ? NBT : L.nb;
+    // ---- the live-block rule
+    int want = L.nb;
+    if (!(L.flags & SEARCH_ALL_LIVE)) {
+        int low = -1;
+#if defined(__HIPCC__)
+#pragma unroll UF
+#endif
+        for (int b = 0; b < nbl; ++b) if (b < L.live && st.S(b) <= L.k + 63) low = b;
+        want = search_want(low, L.nb);
+    }
+#if defined(__HIPCC__)
+#pragma unroll UF
+#endif
+    for (int b = 1; b < nbl; ++b)
+        if (b == L.live && want > L.live) {                      // enters: the cell above + 1 in every row
+            st.P(b) = ~(uint64_t)0; st.M(b) = 0;
+            st.S(b) = st.S(b - 1) + search_rows(b, L.m);
+        }
+    L.live = want;
+    // ---- the live blocks, top-down
+    uint64_t hP = (L.mode == SEARCH_PREFIX) ? ~(uint64_t)0 : 0, hM = 0;
+#if defined(__HIPCC__)
+#pragma unroll UF
+#endif
+    for (int b = 0; b < nbl; ++b) {
+        if (b >= L.live) continue;
+        uint64_t pa, pb, pn, oP, oM;
+        st.planes(b, pa, pb, pn);
+        const bool last = b == L.nb - 1;
+        search_block_chunk(st.P(b), st.M(b), pa, pb, pn, T0, T1, TN, hP, hM, last ? ((L.m - 1) & 63) : 63, ncols, oP, oM);
+        const int32_t start = st.S(b);
+        st.S(b) = start + search_popc(oP) - search_popc(oM);
+        if (last) search_scan(L, start, oP, oM, col0, ncols);
+        hP = oP; hM = oM;
+        L.steps += (uint32_t)ncols;
+    }
+}
+
+// before the first chunk: the live blocks hold column 0
+template <int NBT, class Store>
+QE_S_HD void search_store_init(Store& st, const SearchLane& L) {
+    constexpr int UF = NBT ? NBT : 1;
+    (void)UF;
+    const int nbl = NBT ? NBT : L.nb;
+#if defined(__HIPCC__)
+#pragma unroll UF
+#endif
+    for (int b = 0; b < nbl; ++b) {
+        if (b >= L.live) continue;
+        st.P(b) = ~(uint64_t)0; st.M(b) = 0;
+        st.S(b) = b + 1 < L.nb ? 64 * (b + 1) : L.m;
+    }
+}
+
+// the answer of a finished lane: {d, end}, or {-1, -1} = beyond the bound
+QE_S_HD void search_answer(const SearchLane& L, int32_t& score, int32_t& end) { score = L.best; end = L.best < 0 ? -1 : L.end; }
+
+// The workspace form's store: Pv / Mv / S of block b at stride `stride` elements (64 on the device: [block][lane]), the
+// pattern planes read from memory every chunk
+struct SearchWsStore {
+    uint64_t* pv; uint64_t* mv; int32_t* s; int64_t stride;
+    const uint64_t* pp; int32_t m;
+    QE_S_HD uint64_t& P(int b) { return pv[(int64_t)b * stride]; }
+    QE_S_HD uint64_t& M(int b) { return mv[(int64_t)b * stride]; }
+    QE_S_HD int32_t& S(int b) { return s[(int64_t)b * stride]; }
+    QE_S_HD void planes(int b, uint64_t& a, uint64_t& bb, uint64_t& nn) { bounded_pattern_rows(pp, m, 64 * b, a, bb, nn); }
+};
+// The register form's: everything of up to NB blocks in arrays
+template <int NB>
+struct SearchRegStore {
+    uint64_t pv[NB], mv[NB], pa[NB], pb[NB], pn[NB]; int32_t s[NB];
+    QE_S_HD uint64_t& P(int b) { return pv[b]; }
+    QE_S_HD uint64_t& M(int b) { return mv[b]; }
+    QE_S_HD int32_t& S(int b) { return s[b]; }
+    QE_S_HD void planes(int b, uint64_t& a, uint64_t& bb, uint64_t& nn) { a = pa[b]; bb = pb[b]; nn = pn[b]; }
+    QE_S_HD void load(const uint64_t* pp, int m) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int b = 0; b < NB; ++b) bounded_pattern_rows(pp, m, 64 * b, pa[b], pb[b], pn[b]);
+    }
+};
+
+// One task, lane by lane as the kernels do it: pattern planes pp (m bases, words [0, 3 ceil(m / 64))), the text's planes tp
+// read from bit offset tbit for n columns.  A lane whose bound has dropped below zero has its answer (an exact occurrence
+// at the smallest end) and stops.
+template <int NBT, class Store>
+QE_S_HD void search_run(Store& st, SearchLane& L, const uint64_t* tp, int64_t tbit) {
+    search_store_init<NBT>(st, L);
+    for (int col0 = 0; col0 < L.n && L.k >= 0; col0 += 64) {
+        const int ncols = L.n - col0 < 64 ? L.n - col0 : 64;
+        uint64_t T0, T1, TN;
+        search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
+        search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols);
+    }
+}
+
+}  // namespace qe

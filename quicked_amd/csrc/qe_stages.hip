@@ -663,6 +663,8 @@ struct PendingFetch {
     int parity = 0;                           // the plane set / ev_done slot of the run
     std::vector<int32_t> beyond_pair;         // bounded runs: pairs that are beyond their bound by their lengths alone (no task): score -1, ok_status
     std::vector<int32_t> pair_bound;          // bounded runs: every pair's bound (the fetch thresholds the pairs it hands to the QuickEd flow)
+    bool search = false;                      // a search run (kind 1): locations per task next to the scores
+    const int32_t* d_start = nullptr; const int32_t* d_end = nullptr;
 };
 
 // One wavefront per alignment (k_banded_wave) is for few, long alignments: up to ~1000 tasks every task gets a wave of its
@@ -944,6 +946,153 @@ static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList
         hipLaunchKernelGGL(k_bounded_threshold, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, C.stream, (int)ng, G.d_score, G.d_adv,
                            (const int32_t*)d_bound, O.d_score + nd, O.d_adv + nd);
         HIP_CHECK(hipGetLastError());
+    }
+    return O;
+}
+
+// ---------------------------------------------------------------------------
+// Search runs (quicked_batch_run_search): per task {d, text_start, text_end}, or {-1, -1, -1} = beyond.
+// ---------------------------------------------------------------------------
+#ifndef QE_HAVE_K_SEARCH
+// a kernels header without it (the host-only build's stand-ins): the same source on the host, task by task, in the
+// layout and with the arguments of the device form
+template <int NB>
+static void k_search(SearchArgs A) {
+    for (int t = 0; t < A.T.ntasks; ++t) {
+        const int pair = A.T.pair[t];
+        if (pair < 0) continue;
+        const int g = t >> 6, lane = t & 63, m = A.T.m[t];
+        int n = A.T.n[t], bound = A.T.cutoff[t], in_end = 0;
+        int64_t tbit = 0;
+        bool valid = true;
+        if (A.in_score) {
+            bound = A.in_score[t]; in_end = A.in_end[t];
+            valid = bound >= 0 && in_end >= 1 && in_end <= n;
+            tbit = n - in_end; n = in_end;
+        }
+        const int nbg = NB == 0 ? A.g_nb[g] : NB;
+        valid = valid && search_blocks(m) <= nbg;
+        SearchLane L;
+        search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, A.flags);
+        const u64* pp = A.P.pl_p + A.P.pl_p_off[pair];
+        const u64* tp = A.P.pl_t + A.P.pl_t_off[pair];
+        if (valid) {
+            if constexpr (NB > 0) {
+                SearchRegStore<(NB > 0 ? NB : 1)> R;
+                for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+                R.load(pp, m);
+                search_run<NB>(R, L, tp, tbit);
+            } else {
+                u64* base = (u64*)(A.ws + A.g_ws_off[g]);
+                SearchWsStore W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
+                search_run<0>(W, L, tp, tbit);
+            }
+        }
+        int32_t score, end;
+        search_answer(L, score, end);
+        if (!valid) { score = -1; end = -1; }
+        if (A.in_score) {
+            if (valid) A.o_start[t] = (score == bound) ? in_end - end : -1;
+        } else {
+            A.o_score[t] = score; A.o_end[t] = end;
+            A.o_start[t] = (score >= 0 && A.mode == SEARCH_PREFIX) ? 0 : -1;
+        }
+        A.o_adv[t] += L.steps;
+    }
+}
+#endif
+
+// Which form takes a pattern of nb blocks: the register form's instantiation (1, 2 or 4 blocks), or 0 = the workspace form.
+// QE_SEARCH_FORM = 0: the workspace form always; 1: the register form wherever it applies (up to QE_SEARCH_REG_BLOCKS
+// blocks = 256 bases).  Unset, the library's choice, by the rule of DESIGN.md 4.9 -- the register form only where its median
+// beats the workspace form's by more than the larger of the two spreads -- is the workspace form at every block count: the
+// register form's kernels are the faster ones (1 M pairs in 400-base texts, both passes, workspace / registers: 3.1 / 2.1 ms
+// at 64 bases, 4.1 / 3.4 at 128, 3.9 / 3.6 at 150, 6.1 / 5.5 at 256), but a queued run of that size takes 14 - 20 ms, most of it
+// the host's task lists and uploads, and there the register form was level (150 bases: 16.1 against 16.3 ms, spread 1.1) or
+// behind (64 / 128 / 256 bases: 19.9 / 17.1 / 19.5 against 15.7 / 15.4 / 14.8 ms).  DESIGN.md 4.12, profiles/search.md.
+static int search_reg_form(int nb) {
+    if (sw(Sw::SearchForm) != 1 || nb > QE_SEARCH_REG_BLOCKS) return 0;
+    return nb <= 1 ? 1 : (nb == 2 ? 2 : 4);
+}
+static_assert((int)QUICKED_SEARCH_PREFIX == (int)SEARCH_PREFIX && (int)QUICKED_SEARCH_INFIX == (int)SEARCH_INFIX, "quicked_search_mode_t is qe_search.h's mode");
+
+// The lists of a search run: one per kernel form, so that a wave's lanes are of a kind ([0] the workspace form, [1] / [2] /
+// [3] the register form of 1 / 2 / 4 blocks); a task's index in the run's outputs is its list's offset plus its index
+// there.  Within a list the tasks keep the batch's order (sorted by length).
+struct SearchLists { TaskList L[4]; };
+static int search_bound(const SearchRun& sr, int pr) { return sr.max_dist ? sr.max_dist[pr] : sr.max_dist_all; }
+static void search_pairs(const quicked_batch& B, const SearchRun& sr, SearchLists& S) {
+    for (int64_t i = 0; i < B.n; ++i) {
+        const int pr = B.order[(size_t)i];
+        const int m = B.p_len[pr], n = B.t_len[pr];
+        if (m == 0 || n == 0) continue;                             // QUICKED_EMPTY_SEQUENCE, as in every run
+        const int f = search_reg_form(search_blocks(m));
+        S.L[f == 0 ? 0 : (f == 1 ? 1 : (f == 2 ? 2 : 3))].push(pr, 0, m, 0, n, search_effective(search_bound(sr, pr), m), n);
+    }
+    for (TaskList& l : S.L) l.pad();
+}
+
+// Forward pass over whole pairs, then -- INFIX -- the start pass: the PREFIX form over the reversed planes on the stretch
+// that ends at text_end, bound d, the largest end; it reads the forward pass's results on the device and runs only the
+// tasks within their bound (no host round trip).  Leaves per task of `task_pair` score / start / end and the block steps
+// of both passes on the device.  Both passes are timed as kind 0 (quicked_batch_kernel_times).
+struct SearchOut { std::vector<int32_t> task_pair; int32_t *d_score = nullptr, *d_start = nullptr, *d_end = nullptr; u32* d_adv = nullptr; };
+static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, int mode) {
+    SearchOut O;
+    size_t off[5] = {0, 0, 0, 0, 0};
+    for (int f = 0; f < 4; ++f) {
+        O.task_pair.insert(O.task_pair.end(), S.L[f].pair.begin(), S.L[f].pair.end());
+        off[f + 1] = O.task_pair.size();
+    }
+    const size_t nt = O.task_pair.size();
+    if (nt == 0) return O;
+    int32_t* blk = C.scratch_p->take<int32_t>(4 * nt);
+    O.d_score = blk; O.d_start = blk + nt; O.d_end = blk + 2 * nt; O.d_adv = (u32*)(blk + 3 * nt);
+    HIP_CHECK(hipMemsetAsync(blk, 0xFF, 3 * nt * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nt * sizeof(u32), C.stream));
+    // the workspace form's groups: Pv | Mv | S of the group's tallest pattern
+    const TaskList& Lw = S.L[0];
+    const int ngw = Lw.ngroups();
+    std::vector<int64_t> ws_off((size_t)ngw);
+    std::vector<int32_t> g_nb((size_t)ngw);
+    size_t ws_bytes = 0;
+    for (int g = 0; g < ngw; ++g) {
+        int nb = 1;
+        for (int l = 0; l < 64; ++l) if (Lw.pair[(size_t)g * 64 + l] >= 0) nb = std::max(nb, search_blocks(Lw.m[(size_t)g * 64 + l]));
+        g_nb[g] = nb; ws_off[g] = (int64_t)ws_bytes;
+        ws_bytes += ((size_t)nb * 64 * (8 + 8 + 4) + 255) & ~(size_t)255;
+    }
+    uint8_t* ws = nullptr; int64_t* d_ws_off = nullptr; int32_t* d_nb = nullptr;
+    if (ngw) {
+        ws = C.scratch_p->take<uint8_t>(ws_bytes + 256);
+        d_ws_off = C.scratch_p->take<int64_t>((size_t)ngw); d_nb = C.scratch_p->take<int32_t>((size_t)ngw);
+        CopyBatch cb(C.stream);
+        h2d(d_ws_off, ws_off, C.stream); h2d(d_nb, g_nb, C.stream);
+    }
+    DevTasks T[4];
+    for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
+    auto pass = [&](bool start_pass) {
+        auto* ke = C.kernel_events(0);
+        if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+        for (int f = 0; f < 4; ++f) {
+            if (S.L[f].pair.empty()) continue;
+            SearchArgs a{};
+            a.P = pair_view(B, start_pass); a.T = T[f].v;
+            a.mode = start_pass ? SEARCH_PREFIX : mode; a.flags = start_pass ? SEARCH_LARGEST_END : 0;
+            a.in_score = start_pass ? O.d_score + off[f] : nullptr; a.in_end = start_pass ? O.d_end + off[f] : nullptr;
+            a.o_score = O.d_score + off[f]; a.o_end = O.d_end + off[f]; a.o_start = O.d_start + off[f]; a.o_adv = O.d_adv + off[f];
+            const size_t ng = (size_t)S.L[f].ngroups();
+            if (f == 0) { a.ws = ws; a.g_ws_off = d_ws_off; a.g_nb = d_nb; launch_groups(C, k_search<0>, a, ng, 4, 0); }
+            else if (f == 1) launch_groups(C, k_search<1>, a, ng, 4, 0);
+            else if (f == 2) launch_groups(C, k_search<2>, a, ng, 4, 0);
+            else launch_groups(C, k_search<4>, a, ng, 4, 0);
+        }
+        if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    };
+    pass(false);
+    if (mode == SEARCH_INFIX) {
+        if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+        pass(true);
     }
     return O;
 }
@@ -1298,6 +1447,8 @@ static void reset_host_results(quicked_batch& B) {
     if (B.run_tags & QUICKED_TAG_STATS) B.wr->stats.assign((size_t)B.n, no_stats); else B.wr->stats.clear();
     if (B.run_tags & QUICKED_TAG_MD) B.wr->md_off.assign((size_t)B.n, -1); else B.wr->md_off.clear();
     B.wr->md_pool.size = 0;
+    if (B.search_run) { B.wr->text_start.assign((size_t)B.n, -1); B.wr->text_end.assign((size_t)B.n, -1); }
+    else { B.wr->text_start.clear(); B.wr->text_end.clear(); }
     B.wr->deferred_pairs = 0;
 }
 

@@ -102,6 +102,23 @@ struct BoundedArgs {
     u32* o_adv;              // text columns walked (one block step each)
 };
 
+// Approximate pattern search (k_search<NB>, qe_search.h): whole pairs (p0 = t0 = 0, T.m / T.n = the pair's lengths), T.cutoff =
+// the pair's bound.  The forward pass (in_score == null) leaves o_score / o_end = {d, text_end} or {-1, -1} = beyond, and
+// o_start = 0 for a PREFIX task within its bound, else -1.  The start pass of an INFIX run (in_score / in_end = the forward
+// pass's outputs, P = the REVERSED planes, mode = SEARCH_PREFIX, flags = SEARCH_LARGEST_END) runs the tasks with
+// in_score >= 0, bound in_score, over the in_end columns that end at text_end, and leaves o_start.  Both add their block
+// steps to o_adv.
+struct SearchArgs {
+    PairView P;
+    TaskView T;
+    int32_t mode, flags;                     // SEARCH_PREFIX / SEARCH_INFIX; SEARCH_* flags
+    const int32_t* in_score;  const int32_t* in_end;
+    // the workspace form (k_search<0>), per group: Pv[nb][64] u64 | Mv[nb][64] u64 | S[nb][64] i32, nb = g_nb[group] >= the
+    // blocks of every pattern of the group; null for the register forms
+    uint8_t* ws;  const int64_t* g_ws_off;  const int32_t* g_nb;
+    int32_t* o_score;  int32_t* o_end;  int32_t* o_start;  u32* o_adv;
+};
+
 // BandEd score-only, G lanes per alignment (cooperative form of k_banded<false>)
 struct CoopArgs {
     PairView P;
