@@ -903,7 +903,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
     if (A.only_if != nullptr && pair >= 0 && A.only_if[t] == 0) pair = -1;
     const bool valid = pair >= 0;
     if (!__any(valid)) return;
-    int m = 1, n = 1, p0 = 0, t0 = 0, cut_in = 0, tfin = 0;
+    int m = 1, n = 1, p0 = 0, t0 = 0, cut_in = 0, tfin = 0, prune = 0x7fffffff;
     const u64* pp = A.P.pl_p;
     const u64* tp = A.P.pl_t;
     u32 fl = 0;
@@ -911,12 +911,15 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
         m = A.T.m[t]; n = A.T.n[t]; p0 = A.T.p0[t]; t0 = A.T.t0[t];
         cut_in = A.T.cutoff[t];
         tfin = FILL ? n : A.T.tfin[t];
+        if (!FILL && A.prune != nullptr) prune = A.prune[t];
         pp = A.P.pl_p + A.P.pl_p_off[pair];
         tp = A.P.pl_t + A.P.pl_t_off[pair];
         fl = A.P.flags[pair];
     }
     const bool hasN = (fl & FLAG_HAS_N) != 0;
     const Geom G = band_geometry(m, n, cut_in);
+    const int thr = prune < cut_in ? prune : G.cutoff;             // what the band-edge rules compare against: a threshold counts only below the
+                                                                   // task's cutoff (BandedArgs::prune); without one the geometry's clamped cutoff, as ever
     const int nw = (m + 63) >> 6;
     // the score-only kernels use their own narrower band (bpm_banded.c:801-803) -- unless the launch asks for the fill's
     const bool fgeom = FILL || A.fill_geom != 0;
@@ -1102,7 +1105,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             // every-64-columns bookkeeping (bpm_banded.c:889-922 / 264-301)
             const bool c1 = (first + 2 < last) && (G.fin > 64 * (first + 1));
             bool cut_lo = false;
-            if (c1) cut_lo = S[(int64_t)(first + pos_v + 1) * 64] + (G.fin - 64 * (first + 1)) > G.cutoff;
+            if (c1) cut_lo = S[(int64_t)(first + pos_v + 1) * 64] + (G.fin - 64 * (first + 1)) > thr;
             if (cut_lo && pos_h >= G.prolog) first++;
             else if (!cut_lo && pos_h < G.prolog) first--;
             Pv[(int64_t)last * 64] = QE_ONES;
@@ -1113,7 +1116,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             max_row_init = max(max_row_init, pos + 1);
             const bool c2 = (first + 2 < last) && (64 * (last - 1) > G.fin);
             bool cut_hi = false;
-            if (c2) cut_hi = S[(int64_t)(last + pos_v - 1) * 64] + (64 * (last - 1) - G.fin) > G.cutoff;
+            if (c2) cut_hi = S[(int64_t)(last + pos_v - 1) * 64] + (64 * (last - 1) - G.fin) > thr;
             if (cut_hi || (pos_v + last >= stop_row)) last--;
             pos_v++;
             pos_h++;
@@ -4232,6 +4235,7 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
             if (t >= nt) return;
             A.q_pair[t] = -1;
             A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_cutoff(A.T.m[t], A.T.n[t], A.T.cutoff[t]) : A.T.cutoff[t];
+            if (A.prune1 != nullptr) A.prune1[t] = A.cut1[t];
             return;
         }
         // the fit: this wave is the group t >> 6 of k_banded; its lanes take one slot count (the wave takes part as a whole)
@@ -4241,7 +4245,9 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
         for (int o = 32; o > 0; o >>= 1) sg = max(sg, __shfl_xor(sg, o));
         if (t >= nt) return;
         A.q_pair[t] = -1;
-        A.cut1[t] = live ? narrow_fit_lane(m, n, cut, A.q, sg) : A.T.cutoff[t];
+        const int c1 = live ? narrow_fit_lane(m, n, cut, A.q, sg) : A.T.cutoff[t];
+        A.cut1[t] = c1;
+        if (A.prune1 != nullptr) A.prune1[t] = live ? narrow_prune(m, n, cut, c1, A.qp) : c1;
         return;
     }
     if (A.phase == 1) {
@@ -4250,7 +4256,7 @@ __global__ __launch_bounds__(256) void k_narrow(NarrowArgs A) {
         if (live) {
             const int c1 = A.cut1[t];
             halved = c1 != A.T.cutoff[t];
-            miss = halved && !narrow_accepts(A.T.m[t], A.T.n[t], c1, A.T.cutoff[t], A.score[t]);
+            miss = halved && !narrow_accepts_pruned(A.T.m[t], A.T.n[t], c1, A.T.cutoff[t], A.prune1 != nullptr ? A.prune1[t] : c1, A.score[t]);
         }
         const unsigned long long a1 = wave_sum_u64(halved ? (unsigned long long)A.adv[t] : 0ull);
         const u64 mask = __ballot(miss), hmask = __ballot(halved);

@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, ScoreMasked, TagsWave, SearchForm, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, TagsWave, SearchForm, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -109,6 +109,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::BoundedDiag, "QE_BOUNDED_DIAG", -1},          // bounded runs: -1 the library's choice, 0 never (general path), 1 wherever k_bounded_diag's precondition holds
     {Sw::ScoreNarrow, "QE_SCORE_NARROW", -1},          // BandEd score-only runs: -1 a first pass at half the cutoff where it pays (narrow_wanted), 0 never (the reference's band, cell for cell), 1 wherever a task's band is narrower there (tests), -2 as -1 without the policy's probes (diagnosis)
     {Sw::NarrowFit, "QE_NARROW_FIT", -1},              // ... their first pass: -1 the fewest slots that prove the distances the class's last runs saw (narrow_fit_q), 0 always half the cutoff, k > 0 fitted to k / 1024 of every cutoff whatever ran before (tests)
+    {Sw::NarrowPrune, "QE_NARROW_PRUNE", -1},          // ... the band-edge threshold of a fitted first pass: -1 the fitted ratio plus the spread the class's last runs showed, once two have reported (narrow_prune_q), 0 never (the fit's cells exactly), k > 0 k / 1024 of every cutoff for every fitted list, also under a forced fit (tests)
     {Sw::ScoreMasked, "QE_SCORE_MASKED", 1},           // k_banded<false>'s multi-slot passes: 1 every lane with the slots of the pass inside its band (pass_plan), 0 with all of them or none (the rule before it, pass for pass)
     {Sw::TagsWave, "QE_TAGS_WAVE", -1},                // alignment tags (quicked_batch_configure_tags): -1 the wave form where the CIGAR formatter takes its own (tags_wave_wanted), 0 / 1 the lane / wave form everywhere (tests)
     {Sw::SearchForm, "QE_SEARCH_FORM", -1},            // search runs (quicked_batch_run_search): -1 the library's choice (search_reg_form: the workspace form), 0 the workspace form always, 1 the register form wherever it applies (patterns of up to 256 bases)

@@ -344,6 +344,26 @@ static int narrow_fit_q(Context& C, int cls, bool policy) {
     for (auto& v : C.narrow_q[cls]) q = std::max(q, v.load());
     return q;
 }
+// The pruning threshold of a fitted first pass (qe_types.h: narrow_prune): the ratio qp = q + w, w = what the maxima in the
+// ring varied by (q less its smallest reported ratio).  On repeated data w = 0 and the band edges prune at r_hat itself; on
+// fresh batches of one distribution the threshold sits above r_hat by the spread the class has shown; after a shift the old
+// entries make w large and the threshold is the fitted cutoff, i.e. none.  Only with two reported runs in the ring: one
+// report says nothing about the spread.  QE_NARROW_PRUNE = 0: never, k > 0: qp = k for every fitted list, also under a
+// forced QE_NARROW_FIT (tests); a forced fit alone has no threshold.
+static int narrow_prune_q(Context& C, int cls, bool policy) {
+    const int f = sw(Sw::NarrowPrune);
+    if (f >= 0) return f;
+    if (!policy || sw(Sw::NarrowFit) >= 0) return 0;
+    int q = 0, lo = 0, reports = 0;
+    for (auto& a : C.narrow_q[cls]) {
+        const int v = a.load();
+        if (v <= 0) continue;
+        ++reports;
+        q = std::max(q, v);
+        lo = lo ? std::min(lo, v) : v;
+    }
+    return reports >= 2 ? q + (q - lo) : 0;
+}
 static void narrow_report(Context* C, int cls, const std::vector<unsigned long long>& st, bool probe) {
     static_assert(sizeof(C->narrow_q[0]) / sizeof(C->narrow_q[0][0]) == QE_NARROW_FIT_RUNS, "the ring holds the window");
     if (!C || st.size() < QE_NARROW_STAT) return;
@@ -369,13 +389,14 @@ static void k_narrow(NarrowArgs A) {
             for (int t = g; t < std::min(nt, g + 64); ++t) {
                 A.q_pair[t] = -1;
                 A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_fit_lane(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.q, sg) : A.T.cutoff[t];
+                if (A.prune1) A.prune1[t] = (A.T.pair[t] >= 0) ? narrow_prune(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.cut1[t], A.qp) : A.cut1[t];
             }
         }
     } else if (A.phase == 1) {
         for (int t = 0; t < nt; ++t) {
             if (A.T.pair[t] < 0 || A.cut1[t] == A.T.cutoff[t]) continue;
             A.stat[1] += A.adv[t]; ++A.stat[3];
-            if (narrow_accepts(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.score[t])) {
+            if (narrow_accepts_pruned(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.prune1 ? A.prune1[t] : A.cut1[t], A.score[t])) {
                 A.stat[4] = std::max(A.stat[4], (unsigned long long)std::max(0, narrow_ratio(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.score[t])));
                 continue;
             }
@@ -460,7 +481,7 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
     return S;
 }
 
-static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q) {
+static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q, int qp) {
     ScoreLaunch S;
     S.nt = L.pair.size();
     const size_t nt = S.nt;
@@ -469,13 +490,14 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     S.O = take_out(C, nt);
     ScoreLaunch S2 = S;                              // the packed list of the misses, its outputs; the same workspace
     S2.O = take_out(C, nt);
-    int32_t* blk = C.scratch_p->take<int32_t>(9 * nt);
+    int32_t* blk = C.scratch_p->take<int32_t>(10 * nt);
     S.narrow = C.scratch_p->take<unsigned long long>(QE_NARROW_STAT);
     NarrowArgs x{};
     x.T = S.T.v; x.cut1 = blk; x.score = S.O.score; x.adv = S.O.adv;
     x.q_pair = blk + nt; x.q_p0 = blk + 2 * nt; x.q_m = blk + 3 * nt; x.q_t0 = blk + 4 * nt; x.q_n = blk + 5 * nt;
     x.q_cutoff = blk + 6 * nt; x.q_tfin = blk + 7 * nt; x.q_src = blk + 8 * nt;
     x.q_score = S2.O.score; x.q_adv = S2.O.adv; x.stat = S.narrow; x.q = q;
+    x.qp = q > 0 ? qp : 0; x.prune1 = blk + 9 * nt;      // the first launch's pruning thresholds, beside cut1
     S2.T.v.pair = x.q_pair; S2.T.v.p0 = x.q_p0; S2.T.v.m = x.q_m; S2.T.v.t0 = x.q_t0; S2.T.v.n = x.q_n;
     S2.T.v.cutoff = x.q_cutoff; S2.T.v.tfin = x.q_tfin;
     const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
@@ -485,6 +507,7 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
     BandedArgs a = score_args(B, S, reversed);
     a.T.cutoff = x.cut1;
+    if (x.qp > 0) a.prune = x.prune1;                // (without a ratio prune1 = cut1: today's launch)
     a.lane_rel = sw(Sw::LaneRel);
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
     x.phase = 1;
@@ -809,7 +832,7 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
         narrow = policy && take == 1;
         probe = policy && take == 2;
     }
-    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay, narrow_fit_q(C, np.cls, policy)) :
+    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay, narrow_fit_q(C, np.cls, policy), narrow_prune_q(C, np.cls, policy)) :
                           probe ? launch_banded_probe(B, C, L, reversed, 1) :
                           lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
                           wave ? launch_banded_wave(B, C, L, reversed, 1)

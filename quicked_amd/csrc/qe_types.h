@@ -91,6 +91,9 @@ struct BandedArgs {
     int32_t fill_geom = 0;        // k_banded<false>: the FILL's band geometry (a6's ebb, stop rule nw - 1: bpm_banded.c:121-135, 295) instead of
                                   // the score-only kernel's narrower one (801-803, 917): the cells, hence the end value, of the fill -- QuickEd with
                                   // only_score takes its score from such a pass instead of filling, tracing back and counting edits
+    const int32_t* prune = nullptr;   // k_banded<false>: per task, beside T.cutoff: where prune[t] < T.cutoff[t] the band-edge rules compare against it
+                                  // instead of the geometry's cutoff -- the fitted first launch of a two-pass run (narrow_prune); null, or a value
+                                  // that is not below the task's cutoff: the geometry's (clamped) cutoff, as every other launch
 };
 
 // Bounded edit distance, diagonal-word form (k_bounded_diag, qe_bounded.h): whole pairs (p0 = t0 = 0), T.cutoff = the pair's
@@ -288,6 +291,22 @@ QE_T_HD int narrow_fit_lane(int m, int n, int cutoff_in, int q, int s_g) {
     const int c = narrow_fit_cutoff(m, n, cutoff_in, s_g);
     return (c > 0 && narrow_accepts(m, n, c, cutoff_in, narrow_rhat(q, cutoff_in))) ? c : half;
 }
+// The pruning threshold: the fitted cutoff is the roomiest its slot count holds, and every unit of that room
+// is rows the band-edge rules of k_banded keep (they compare against the cutoff).  A lane that took the fitted cutoff prunes
+// at min(c1, r_hat of the ratio qp) instead -- the geometry stays c1's -- and a first result above the threshold proves
+// nothing: the rules drop a slot only when no path within the threshold passes through what is no longer computed.
+// c1 = the lane's first-pass cutoff (narrow_fit_lane): it is the fit's exactly when it differs from narrow_cutoff (the fitted
+// band has fewer slots than the band at half the cutoff); qp = the prune ratio in 1/1024ths of the cutoff, 0: none.
+// A fitted band of three slots (the least there is) keeps its cutoff: its edges cannot move.
+QE_T_HD int narrow_prune(int m, int n, int cutoff_in, int c1, int qp) {
+    if (qp <= 0 || c1 == cutoff_in || c1 == narrow_cutoff(m, n, cutoff_in)) return c1;
+    if (narrow_slots(m, n, c1) <= 3) return c1;      // first + 2 < last never holds in such a band: no rule fires, a threshold could only add misses
+    const int r = narrow_rhat(qp, cutoff_in);
+    return r < c1 ? r : c1;
+}
+QE_T_HD bool narrow_accepts_pruned(int m, int n, int c1, int cutoff_in, int p, int r) {
+    return narrow_accepts(m, n, c1, cutoff_in, r) && r <= p;
+}
 // what a run reports of a task with a lowered cutoff and the final score r: ceil(1024 r / cutoff) where the pass at
 // narrow_cutoff would have accepted r (the ratio the next fit is made from), else -1
 QE_T_HD int narrow_ratio(int m, int n, int cutoff_in, int r) {
@@ -327,11 +346,16 @@ QE_T_HD int pass_plan(int i, int K, int lo, int hi, int r, int nw, bool plain, b
 // pass did advance for the misses) and adds the sample pass's block-columns to the tasks' own (work really done).
 // With q > 0 (the fit, see above) phase 0 works per group of 64 tasks = one wave of k_banded: s_g = the largest narrow_fit_slots
 // of the group's live lanes that have one, cut1 = narrow_fit_lane(.., q, s_g); q = 0 is narrow_cutoff for every task.
+// With a prune ratio qp > 0 the lanes that took the fit get prune1 = narrow_prune(..) <= cut1, the band-edge threshold of
+// the first launch, and phase 1 takes a first result only up to it; the misses this adds are accepted by narrow_cutoff's
+// pass, so phase 2 counts them in stat[5] and reports their ratios like every miss owed to the fit.
 enum : int { QE_NARROW_STAT = 6 };               // words of NarrowArgs::stat
 struct NarrowArgs {
     int32_t phase, stride, q;
     TaskView T;
     int32_t* cut1;
+    int32_t qp = 0;  int32_t* prune1 = nullptr;  // the fit's pruning threshold: phase 0 writes narrow_prune(.., cut1, qp) beside cut1, phase 1
+                                                 // accepts with narrow_accepts_pruned (null: no thresholds; phase 3 has none)
     int32_t* score;  u32* adv;                   // the list's outputs (first pass; phase 2 merges the second into them)
     int32_t *q_pair, *q_p0, *q_m, *q_t0, *q_n, *q_cutoff, *q_tfin, *q_src;
     const int32_t* q_score;  const u32* q_adv;   // the second pass's outputs, by packed index
