@@ -157,6 +157,44 @@ quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mode,
                                           const int32_t* max_dist, int32_t max_dist_all,
                                           int only_score, int sync);
 quicked_status_t quicked_batch_locations(quicked_batch_t* batch, int32_t* text_start, int32_t* text_end); /* n each */
+/* Every occurrence within the bound, not only the best: "where does the pattern occur in this text within k edits?" -- a primer
+ * in a window of a genome, an adapter that occurs twice in a chimeric read, a barcode in a read with a tandem repeat.
+ * D, the modes, the equality, the per-pair bound (max_dist / max_dist_all, clamped to m) and the treatment of empty sequences
+ * are those of quicked_batch_run_search.  Let R[e] = D[m][e] for e = 1 .. n and k the pair's effective bound; column 0 counts as
+ * higher than every value.  Position e is an occurrence when
+ *   R[e] <= k,
+ *   R[e] < R[e-1]  (which holds for e = 1 by the convention above), and
+ *   the first e' > e with R[e'] != R[e], if there is one, has R[e'] > R[e]:
+ * e is the first column of a valley of row m; a valley's plateau counts once, and a plateau that reaches the end of the text
+ * counts.  The occurrence's score is R[e], its text_end is e (exclusive, as above); text_start is 0 for PREFIX, for INFIX the
+ * smallest s for which the global distance of the pattern against text[s, e) is score -- the rule of the best search.  A
+ * pair's occurrences are ordered by text_end.  Two consequences: the set depends on min(R[e], k + 1) only; and the smallest
+ * score among a pair's occurrences, with the first occurrence that has it, is exactly {score, text_start, text_end} of
+ * quicked_batch_run_search for the same bound (d == m included).  For upper-case ACGT input with d != m the occurrences of
+ * score d are edlib's endLocations + 1 with every member whose predecessor is also in the list removed, and its startLocations
+ * of those.
+ * Results: quicked_batch_hit_counts gives found[i], the number of occurrences of pair i -- exact whatever the cap -- and
+ * stored[i] = min(found[i], max_hits): the stored occurrences are the first ones by text_end, hits[hit_off[i] .. hit_off[i+1])
+ * of quicked_batch_hits (hit_off has n + 1 entries; quicked_batch_hit_total = hit_off[n] sizes the array).  quicked_batch_scores
+ * after such a run gives the smallest score among ALL found occurrences, stored or not, so "is pair i within k?" stays exact
+ * under any cap; a pair without an occurrence gets -1 with QUICKED_OK.  Empty sequences keep QUICKED_EMPTY_SEQUENCE and have no
+ * occurrences.  quicked_batch_locations, the CIGAR getters and the tag getters return what they return after any run that
+ * produced none of their data; the three getters here return QUICKED_ERROR (the total: -1) after any run that was not an
+ * all-occurrences run.
+ * max_hits must be in 1 .. 4096 and (the number of pairs without an empty sequence) x max_hits at most 2^26; otherwise, and for
+ * a NULL batch, an unknown mode or a negative bound: QUICKED_ERROR, nothing is launched.  sync == 0: QUICKED_UNIMPLEMENTED,
+ * nothing is queued (the start pass is sized from a total that the host reads between the two passes); so is a batch configured
+ * with check != 0, as for quicked_batch_run_search.  The tags of quicked_batch_configure_tags are ignored: these runs produce
+ * no alignments.  ASCII and packed batches alike; N, lower-case and IUPAC bytes under the library's equality.  Counters [0] and
+ * kernel_times slot [0] count the passes, as for a search run.  Both kernel forms of quicked_batch_run_search (QE_SEARCH_FORM);
+ * the forward pass cannot lower its bound or stop at an exact occurrence, so it walks every text to its end. */
+typedef struct { int32_t text_start, text_end, score; } quicked_hit_t;          /* 12 bytes */
+quicked_status_t quicked_batch_run_search_all(quicked_batch_t* batch, int mode,
+                                              const int32_t* max_dist, int32_t max_dist_all,
+                                              int32_t max_hits, int sync);
+quicked_status_t quicked_batch_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored); /* n each, either may be NULL */
+int64_t          quicked_batch_hit_total(quicked_batch_t* batch);               /* sum of stored; -1 after any other run */
+quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t* hits, int64_t* hit_off /* n + 1 */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

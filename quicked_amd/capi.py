@@ -60,9 +60,11 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_reload", "quicked_batch_reload_packed", "quicked_batch_fetch", "quicked_pool_stats", "quicked_batch_cigar_view",
            "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats",
            "quicked_batch_run_bounded", "quicked_batch_run_search", "quicked_batch_locations",
+           "quicked_batch_run_search_all", "quicked_batch_hit_counts", "quicked_batch_hit_total", "quicked_batch_hits",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
+HIT_DTYPE = np.dtype([("text_start", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_hit_t
 SEARCH_PREFIX, SEARCH_INFIX = 1, 2
 
 _LIB = None
@@ -109,6 +111,14 @@ def lib():
     L.quicked_batch_run_search.restype = C.c_int
     L.quicked_batch_locations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_locations.restype = C.c_int
+    L.quicked_batch_run_search_all.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int]
+    L.quicked_batch_run_search_all.restype = C.c_int
+    L.quicked_batch_hit_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_hit_counts.restype = C.c_int
+    L.quicked_batch_hit_total.argtypes = [C.c_void_p]
+    L.quicked_batch_hit_total.restype = C.c_int64
+    L.quicked_batch_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_hits.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -358,6 +368,35 @@ class ResidentBatch:
         if md.shape != (self.n,):
             raise ValueError("max_dist: one bound per pair")
         return self._lib.quicked_batch_run_search(self._h, int(mode), md.ctypes.data, 0, 1 if only_score else 0, 1 if sync else 0)
+
+    def run_search_all(self, mode, max_dist=None, max_hits=16, sync=True):
+        """quicked_batch_run_search_all: every occurrence of the pattern within the bound (the first columns of the valleys of
+        row m), at most max_hits (1 .. 4096) stored per pair.  max_dist as in run_search.  Sync runs only."""
+        if max_dist is None:
+            max_dist = 2**31 - 1
+        if np.ndim(max_dist) == 0:
+            return self._lib.quicked_batch_run_search_all(self._h, int(mode), None, int(max_dist), int(max_hits), 1 if sync else 0)
+        md = np.ascontiguousarray(max_dist, dtype=np.int32)
+        if md.shape != (self.n,):
+            raise ValueError("max_dist: one bound per pair")
+        return self._lib.quicked_batch_run_search_all(self._h, int(mode), md.ctypes.data, 0, int(max_hits), 1 if sync else 0)
+
+    def hits(self):
+        """-> (found, hit_off, hits) of the last all-occurrences run: found[i] occurrences of pair i (exact whatever the cap),
+        the stored ones hits[hit_off[i]:hit_off[i + 1]], a structured array of HIT_DTYPE ordered by text_end.
+        QuickedException after any other run"""
+        total = self._lib.quicked_batch_hit_total(self._h)
+        if total < 0:
+            raise QuickedException(QUICKED_ERROR)
+        found = np.zeros(self.n, dtype=np.int32)
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        hits = np.zeros(total, dtype=HIT_DTYPE)
+        st = self._lib.quicked_batch_hit_counts(self._h, found.ctypes.data, None)
+        if st >= 0:
+            st = self._lib.quicked_batch_hits(self._h, hits.ctypes.data, off.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return found, off, hits
 
     def locations(self):
         """-> (text_start, text_end) int32 arrays of the last search run: the located stretch is text[start:end]; -1 / -1 for a

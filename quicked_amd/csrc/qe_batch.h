@@ -99,9 +99,14 @@ struct quicked_batch {
         // search runs (quicked_batch_run_search): [n] after such a run, else empty; -1 / -1 for a pair that is beyond its bound
         // or has an empty sequence
         std::vector<int32_t> text_start, text_end;
+        // all-occurrences runs (quicked_batch_run_search_all): found [n] and hit_off [n + 1] after such a run, else empty; the
+        // stored occurrences of pair i are hits[hit_off[i] .. hit_off[i + 1])
+        std::vector<int32_t> found;
+        std::vector<int64_t> hit_off;
+        std::vector<quicked_hit_t> hits;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -115,6 +120,7 @@ struct quicked_batch {
     // host-driven flows of that run read, whatever the caller configures meanwhile
     int run_tags = 0;
     bool search_run = false;                      // the run in progress is a search run: its results carry locations (reset_host_results)
+    bool hits_run = false;                        // ... an all-occurrences run: its results carry occurrence lists instead
     // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
     bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)
@@ -193,7 +199,8 @@ inline bool trace_on() { return sw_set(Sw::Trace); }
 // null; p is the default BANDED parameter block with the caller's only_score
 struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 // sr != nullptr: a search run (quicked_batch_run_search) in `mode` (QUICKED_SEARCH_*), bounds as in a bounded run; p as there
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; };
+// max_hits > 0: every occurrence within the bound (quicked_batch_run_search_all), at most max_hits stored per pair; fetch only
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; };
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr, const SearchRun* sr = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);

@@ -239,6 +239,51 @@ QE_API quicked_status_t quicked_batch_locations(quicked_batch_t* batch, int32_t*
     return QUICKED_OK;
 }
 
+// Every occurrence within the bound: the arguments are checked before anything touches the device
+static_assert(sizeof(quicked_hit_t) == 12, "quicked_hit_t is three int32 (k_hits_expand writes it as such)");
+QE_API quicked_status_t quicked_batch_run_search_all(quicked_batch_t* batch, int mode, const int32_t* max_dist, int32_t max_dist_all,
+                                                     int32_t max_hits, int sync) {
+    if (!batch || (mode != QUICKED_SEARCH_PREFIX && mode != QUICKED_SEARCH_INFIX) || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
+    struct Arg { SearchRun sr; int sync; } arg{{mode, max_dist, max_dist_all, max_hits}, sync};
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        int64_t tasks = 0;
+        for (int64_t i = 0; i < B->n; ++i) {
+            if (x->sr.max_dist && x->sr.max_dist[i] < 0) return QUICKED_ERROR;
+            tasks += B->p_len[(size_t)i] > 0 && B->t_len[(size_t)i] > 0;
+        }
+        if (tasks * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;      // the room for the stored occurrences
+        if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
+        if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the start pass is sized from a total the host reads
+        quicked_params_t p = quicked_default_params();
+        p.algo = BANDED;
+        p.only_score = true;
+        return run_batch(*B, p, true, nullptr, &x->sr);
+    }, &arg);
+}
+
+QE_API quicked_status_t quicked_batch_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (found) memcpy(found, R.found.data(), (size_t)batch->n * sizeof(int32_t));
+    if (stored) for (int64_t i = 0; i < batch->n; ++i) stored[i] = (int32_t)(R.hit_off[(size_t)i + 1] - R.hit_off[(size_t)i]);
+    return QUICKED_OK;
+}
+
+QE_API int64_t quicked_batch_hit_total(quicked_batch_t* batch) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return -1;
+    return batch->res[batch->vis].hit_off[(size_t)batch->n];
+}
+
+QE_API quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t* hits, int64_t* hit_off) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (hits && !R.hits.empty()) memcpy(hits, R.hits.data(), R.hits.size() * sizeof(quicked_hit_t));
+    if (hit_off) memcpy(hit_off, R.hit_off.data(), ((size_t)batch->n + 1) * sizeof(int64_t));
+    return QUICKED_OK;
+}
+
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {
     return guard(batch, [](quicked_batch* B, void*) {
         tl_device = B->device;

@@ -100,9 +100,12 @@ struct FetchBatch {
     explicit FetchBatch(Context& c) : C(c) {}
     template <typename T> void add(std::vector<T>& dst, const T* src, size_t n) {
         dst.resize(n);
-        if (n == 0) return;
-        items.push_back(Item{dst.data(), src, n * sizeof(T), top});
-        top += (n * sizeof(T) + 63) & ~(size_t)63;
+        add_bytes(dst.data(), src, n * sizeof(T));
+    }
+    void add_bytes(void* dst, const void* src, size_t bytes) {
+        if (bytes == 0) return;
+        items.push_back(Item{dst, src, bytes, top});
+        top += (bytes + 63) & ~(size_t)63;
     }
     void sync() {
         if (top <= ((size_t)256 << 10)) {
@@ -801,7 +804,8 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     }
     B.only_score_run = p.only_score;
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
-    B.search_run = sr != nullptr;
+    B.search_run = sr != nullptr && sr->max_hits == 0;
+    B.hits_run = sr != nullptr && sr->max_hits > 0;
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -860,7 +864,27 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
     StageResult R;
 
-    if (sr) {
+    if (sr && sr->max_hits > 0) {
+        // All-occurrences run (sync only): found / smallest score / offsets per pair and the stored occurrences, already in the
+        // order of the pairs, in one read-back
+        enter_a();
+        const SearchHitsOut HO = run_search_hits(B, C, SLs, sr->mode, sr->max_hits);
+        const size_t n = (size_t)B.n, nh = (size_t)HO.total;
+        std::vector<int32_t> best; std::vector<u32> adv, adv2;
+        B.wr->hits.resize(nh);
+        {
+            FetchBatch fb(C);
+            fb.add(B.wr->found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
+            fb.add(B.wr->hit_off, (const int64_t*)HO.d_off, n + 1);
+            fb.add(adv, (const u32*)HO.d_adv, HO.task_pair.size());
+            if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
+            fb.add_bytes(B.wr->hits.data(), HO.d_hits, nh * sizeof(quicked_hit_t));
+            fb.sync();
+        }
+        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
+        for (const int32_t pr : HO.task_pair) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+        ret = QUICKED_OK;
+    } else if (sr) {
         // Search run: the forward pass and -- INFIX -- the start pass leave {d, text_start, text_end} per task on the device;
         // with CIGARs wanted every pair within its bound is then aligned against its located stretch with cutoff = d -- exact,
         // so the run buffers are tight (the path bounded CIGAR runs take).  Pairs with lower-case / IUPAC bytes are scored and
@@ -1090,6 +1114,7 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     HIP_CHECK(B.done_sync(F.parity));
     C.phase_u();
     B.search_run = F.search;
+    B.hits_run = false;                        // (all-occurrences runs are never queued)
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {

@@ -1284,6 +1284,89 @@ template __global__ void k_search<1>(SearchArgs);
 template __global__ void k_search<2>(SearchArgs);
 template __global__ void k_search<4>(SearchArgs);
 
+// Every occurrence within the bound (quicked_batch_run_search_all): the forward pass above with SearchHitScan in the place of
+// the end-position scan -- the same stores, the same group layout, the bound kept for the whole text, no early exit.  A lane
+// emits an occurrence when row m rises out of a valley (rarely more than a few per text): one 8-byte store into its own
+// stretch of `raw`, never past max_hits entries (SearchHitSink::cap); a lane without a valid task has cap 0 and a null sink.
+#define QE_HAVE_K_SEARCH_HITS 1
+template <int NB>
+__global__ __launch_bounds__(256) void k_search_hits(SearchHitsArgs X) {
+    const SearchArgs& A = X.S;
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
+    if (g * 64 >= A.T.ntasks) return;
+    const int pair = (t < A.T.ntasks) ? A.T.pair[t] : -1;
+    bool valid = pair >= 0;
+    int m = 1, n = 0, bound = 0;
+    const u64* pp = A.P.pl_p;
+    const u64* tp = A.P.pl_t;
+    if (valid) { m = A.T.m[t]; n = A.T.n[t]; bound = A.T.cutoff[t]; }
+    const int nbg = (NB == 0) ? A.g_nb[g] : NB;
+    valid = valid && bound >= 0 && search_blocks(m) <= nbg;     // (the host lays the groups out so; never index past the store)
+    if (!__any(valid)) return;
+    SearchLane L;
+    search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, 0);
+    SearchHitScan H;
+    H.init(L, valid ? reinterpret_cast<SearchHit*>(X.raw) + (int64_t)t * X.max_hits : nullptr, 1, valid ? X.max_hits : 0);
+    if (valid) { pp = A.P.pl_p + A.P.pl_p_off[pair]; tp = A.P.pl_t + A.P.pl_t_off[pair]; }
+    SearchRegStore<(NB > 0 ? NB : 1)> R;
+    SearchWsStore W;
+    if constexpr (NB > 0) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = R.pa[b] = R.pb[b] = R.pn[b] = 0; R.s[b] = 0; }
+        if (valid) { R.load(pp, m); search_store_init<NB>(R, L); }
+    } else {
+        uint8_t* base = A.ws + A.g_ws_off[g];
+        W.pv = (u64*)base + lane; W.mv = (u64*)base + (int64_t)nbg * 64 + lane;
+        W.s = (int32_t*)((u64*)base + (int64_t)2 * nbg * 64) + lane;
+        W.stride = 64; W.pp = pp; W.m = m;
+        if (valid) search_store_init<0>(W, L);
+    }
+    const int my_chunks = valid ? (n + 63) >> 6 : 0;
+    const int wave_chunks = wave_max(my_chunks);
+    for (int c = 0; c < wave_chunks; ++c) {
+        if (c < my_chunks) {
+            const int col0 = 64 * c, ncols = min(64, n - col0);
+            u64 T0, T1, TN;
+            search_text_chunk(tp, col0, ncols, T0, T1, TN);
+            if constexpr (NB > 0) search_chunk<NB>(R, L, T0, T1, TN, col0, ncols, H);
+            else search_chunk<0>(W, L, T0, T1, TN, col0, ncols, H);
+        }
+    }
+    if (valid) {
+        H.finish();
+        X.o_found[pair] = H.found; X.o_best[pair] = H.best; X.o_len[pair] = H.sink.count - 1;
+        A.o_adv[t] += L.steps;
+    }
+}
+template __global__ void k_search_hits<0>(SearchHitsArgs);
+template __global__ void k_search_hits<1>(SearchHitsArgs);
+template __global__ void k_search_hits<2>(SearchHitsArgs);
+template __global__ void k_search_hits<4>(SearchHitsArgs);
+
+// one thread per task of a forward list: its stored occurrences to their places in the run's occurrence list (HitExpandArgs)
+__global__ __launch_bounds__(256) void k_hits_expand(HitExpandArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= A.T.ntasks) return;
+    const int pair = A.T.pair[t];
+    if (pair < 0) return;
+    const int stored = min(A.len[pair] + 1, A.max_hits), m = A.T.m[t], n = A.T.n[t];
+    const int32_t* raw = A.raw + 2 * (int64_t)t * A.max_hits;
+    for (int i = 0; i < stored; ++i) {
+        const int64_t j = A.off[pair] + i;
+        const int32_t end = raw[2 * i], score = raw[2 * i + 1];
+        int32_t task_n, in_end, base;
+        search_hit_task(m, n, end, score, task_n, in_end, base);
+        A.hits[3 * j] = A.infix ? base : 0; A.hits[3 * j + 1] = end; A.hits[3 * j + 2] = score;
+        if (A.infix) { A.o_pair[j] = pair; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = score; A.o_end[j] = in_end; }
+    }
+}
+// the start pass's o_start is relative to the occurrence's window
+__global__ __launch_bounds__(256) void k_hits_finish(int64_t total, const int32_t* __restrict__ o_start, int32_t* __restrict__ hits) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= total) return;
+    hits[3 * j] = o_start[j] < 0 ? -1 : hits[3 * j] + o_start[j];
+}
+
 
 // ===========================================================================
 // BandEd score-only, cooperative form: G adjacent lanes share one alignment.

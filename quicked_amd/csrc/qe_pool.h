@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, TagsWave, SearchForm, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, TagsWave, SearchForm, SearchHitsWsKb, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -113,6 +113,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::ScoreMasked, "QE_SCORE_MASKED", 1},           // k_banded<false>'s multi-slot passes: 1 every lane with the slots of the pass inside its band (pass_plan), 0 with all of them or none (the rule before it, pass for pass)
     {Sw::TagsWave, "QE_TAGS_WAVE", -1},                // alignment tags (quicked_batch_configure_tags): -1 the wave form where the CIGAR formatter takes its own (tags_wave_wanted), 0 / 1 the lane / wave form everywhere (tests)
     {Sw::SearchForm, "QE_SEARCH_FORM", -1},            // search runs (quicked_batch_run_search): -1 the library's choice (search_reg_form: the workspace form), 0 the workspace form always, 1 the register form wherever it applies (patterns of up to 256 bases)
+    {Sw::SearchHitsWsKb, "QE_SEARCH_HITS_WS_KB", 262144},      // all-occurrences runs (quicked_batch_run_search_all): KiB of workspace the start pass's workspace-form launches share; more groups than fit run in slices (tests force slices with a small value)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {

@@ -36,6 +36,14 @@
 //
 // The end-position scan.  Row m's two delta words give its 64 values in the chunk from the value at the chunk's start; they
 // are scanned only when start - popcount(minus word) <= k.
+//
+// Every occurrence (quicked_batch_run_search_all).  R[e] = D[m][e]; position e is an occurrence when R[e] <= k, R[e] <
+// R[e - 1] (column 0 counts as higher than every value) and the first later column with another value, if there is one,
+// has a higher one: the first column of a valley of row m.  SearchHitScan replaces the scan above: k stays the task's
+// bound for the whole text, the lane never stops early, and the valleys go to a small sink in the order of their ends.
+// The set depends on min(R[e], k + 1) only -- a value above k is no occurrence, ends a plateau as a rise whatever it is, and
+// is a column every value <= k lies below -- and the sweep's values are exact wherever the true value is <= k and above k
+// wherever it is not (the rule's first two points), so the scan walks w = min(computed value, k + 1).
 #pragma once
 #include <stdint.h>
 
@@ -145,8 +153,11 @@ QE_S_HD void search_scan(SearchLane& L, int32_t start, uint64_t oP, uint64_t oM,
 //   uint64_t& P(int b), & M(int b);  int32_t& S(int b);  void planes(int b, uint64_t& a, uint64_t& b, uint64_t& nn)
 //
 // One chunk: text columns [col0, col0 + ncols) of the task, planes (T0, T1, TN).
-template <int NBT, class Store>
-QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols) {
+//
+// Scan: what becomes of row m.  row(): the last block was computed, its row-m deltas are (oP, oM) from the value `start`;
+// no_row(): the chunk left the last block out.
+template <int NBT, class Store, class Scan>
+QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols, Scan& scan) {
     constexpr int UF = NBT ? NBT : 1;                         // the register form unrolls over its blocks; the workspace form does not
     (void)UF;
     const int nbl = NBT ? NBT : L.nb;
@@ -182,11 +193,62 @@ QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, ui
         search_block_chunk(st.P(b), st.M(b), pa, pb, pn, T0, T1, TN, hP, hM, last ? ((L.m - 1) & 63) : 63, ncols, oP, oM);
         const int32_t start = st.S(b);
         st.S(b) = start + search_popc(oP) - search_popc(oM);
-        if (last) search_scan(L, start, oP, oM, col0, ncols);
+        if (last) scan.row(L, start, oP, oM, col0, ncols);
         hP = oP; hM = oM;
         L.steps += (uint32_t)ncols;
     }
+    if (L.live < L.nb) scan.no_row(L);
 }
+// the scan of the best search: the default
+struct SearchBestScan {
+    QE_S_HD void row(SearchLane& L, int32_t start, uint64_t oP, uint64_t oM, int col0, int ncols) { search_scan(L, start, oP, oM, col0, ncols); }
+    QE_S_HD void no_row(SearchLane&) {}
+};
+template <int NBT, class Store>
+QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols) {
+    SearchBestScan scan;
+    search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols, scan);
+}
+
+// ---- every occurrence.  Where a lane's occurrences go: {end, score} number i at out[i * stride], the first `cap` of them
+struct SearchHit { int32_t end, score; };
+struct SearchHitSink { SearchHit* out; int64_t stride; int32_t cap, count; };
+// what a lane carries besides SearchLane: w of the previous column, the candidate -- the first column of a plateau that was
+// reached by a descent and has not risen yet (end < 0: none) --, the occurrences so far and the smallest score among them
+struct SearchHitScan {
+    int32_t prev, pend_end, pend_val, found, best;
+    SearchHitSink sink;
+    QE_S_HD void init(const SearchLane& L, SearchHit* out, int64_t stride, int32_t cap) {
+        prev = L.k + 1;                              // column 0: higher than every value that counts
+        pend_end = -1; pend_val = 0; found = 0; best = -1;
+        sink.out = out; sink.stride = stride; sink.cap = cap; sink.count = 0;
+    }
+    QE_S_HD void emit() {                            // the row has risen, or the text is over: the candidate is a valley
+        if (pend_end < 0) return;
+        if (sink.count < sink.cap) { sink.out[(int64_t)sink.count * sink.stride] = SearchHit{pend_end, pend_val}; ++sink.count; }
+        ++found;
+        if (best < 0 || pend_val < best) best = pend_val;
+        pend_end = -1;
+    }
+    QE_S_HD void row(SearchLane& L, int32_t start, uint64_t oP, uint64_t oM, int col0, int ncols) {
+        // The popcount test says that every value of the chunk is above k.  With no candidate pending the chunk changes
+        // nothing but `prev`, and that only to k + 1: values above k need not be exact (min(R, k + 1), above).  With one
+        // pending the chunk's first column is the rise that makes it an occurrence, so the walk below has to see it.
+        if (pend_end < 0 && start - search_popc(oM) > L.k) { prev = L.k + 1; return; }
+        int32_t v = start;
+        for (int c = 0; c < ncols; ++c) {
+            v += (int32_t)((oP >> c) & 1) - (int32_t)((oM >> c) & 1);
+            const int32_t w = v <= L.k ? v : L.k + 1;
+            if (w < prev) { pend_end = col0 + c + 1; pend_val = w; }      // a descent (w <= k: prev <= k + 1); an older candidate was no valley
+            else if (w > prev) emit();
+            prev = w;
+        }
+    }
+    // The last block was not computed: by the rule no cell of it in this chunk is <= k (a cell <= k lies in a computed
+    // block), so row m has risen above k
+    QE_S_HD void no_row(SearchLane& L) { emit(); prev = L.k + 1; }
+    QE_S_HD void finish() { emit(); }                // a plateau that reaches the end of the text counts
+};
 
 // before the first chunk: the live blocks hold column 0
 template <int NBT, class Store>
@@ -245,6 +307,28 @@ QE_S_HD void search_run(Store& st, SearchLane& L, const uint64_t* tp, int64_t tb
         search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
         search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols);
     }
+}
+
+// One task of an all-occurrences run: the bound stays, the lane walks the whole text.  flags: 0 or SEARCH_ALL_LIVE
+template <int NBT, class Store>
+QE_S_HD void search_run_hits(Store& st, SearchLane& L, SearchHitScan& H, const uint64_t* tp, int64_t tbit) {
+    search_store_init<NBT>(st, L);
+    for (int col0 = 0; col0 < L.n; col0 += 64) {
+        const int ncols = L.n - col0 < 64 ? L.n - col0 : 64;
+        uint64_t T0, T1, TN;
+        search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
+        search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols, H);
+    }
+    H.finish();
+}
+// the columns the start pass of an occurrence {end, score} walks: no stretch is longer than m + score
+QE_S_HD int search_hit_window(int m, int end, int score) { return end < m + score ? end : m + score; }
+// ... as a task of the best search's start pass (SearchArgs::in_score = score): it walks the in_end columns that end at
+// column task_n of the reversed text, so task_n = n - end + window puts the window's last column on text_end; the pass leaves
+// text_start - base
+QE_S_HD void search_hit_task(int m, int n, int end, int score, int32_t& task_n, int32_t& in_end, int32_t& base) {
+    const int w = search_hit_window(m, end, score);
+    in_end = w; task_n = n - end + w; base = end - w;
 }
 
 }  // namespace qe

@@ -1025,6 +1025,58 @@ static void k_search(SearchArgs A) {
 }
 #endif
 
+#ifndef QE_HAVE_K_SEARCH_HITS
+// ... and of the all-occurrences kernels (SearchHitsArgs, HitExpandArgs)
+template <int NB>
+static void k_search_hits(SearchHitsArgs X) {
+    const SearchArgs& A = X.S;
+    for (int t = 0; t < A.T.ntasks; ++t) {
+        const int pair = A.T.pair[t];
+        if (pair < 0) continue;
+        const int g = t >> 6, lane = t & 63, m = A.T.m[t], n = A.T.n[t], bound = A.T.cutoff[t];
+        const int nbg = NB == 0 ? A.g_nb[g] : NB;
+        if (bound < 0 || search_blocks(m) > nbg) continue;
+        SearchLane L;
+        search_lane_init(L, m, n, A.mode, bound, 0);
+        SearchHitScan H;
+        H.init(L, reinterpret_cast<SearchHit*>(X.raw) + (int64_t)t * X.max_hits, 1, X.max_hits);
+        const u64* pp = A.P.pl_p + A.P.pl_p_off[pair];
+        const u64* tp = A.P.pl_t + A.P.pl_t_off[pair];
+        if constexpr (NB > 0) {
+            SearchRegStore<(NB > 0 ? NB : 1)> R;
+            for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+            R.load(pp, m);
+            search_run_hits<NB>(R, L, H, tp, 0);
+        } else {
+            u64* base = (u64*)(A.ws + A.g_ws_off[g]);
+            SearchWsStore W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
+            search_run_hits<0>(W, L, H, tp, 0);
+        }
+        X.o_found[pair] = H.found; X.o_best[pair] = H.best; X.o_len[pair] = H.sink.count - 1;
+        A.o_adv[t] += L.steps;
+    }
+}
+static void k_hits_expand(HitExpandArgs A) {
+    for (int t = 0; t < A.T.ntasks; ++t) {
+        const int pair = A.T.pair[t];
+        if (pair < 0) continue;
+        const int stored = std::min(A.len[pair] + 1, A.max_hits), m = A.T.m[t], n = A.T.n[t];
+        const int32_t* raw = A.raw + 2 * (int64_t)t * A.max_hits;
+        for (int i = 0; i < stored; ++i) {
+            const int64_t j = A.off[pair] + i;
+            const int32_t end = raw[2 * i], score = raw[2 * i + 1];
+            int32_t task_n, in_end, base;
+            search_hit_task(m, n, end, score, task_n, in_end, base);
+            A.hits[3 * j] = A.infix ? base : 0; A.hits[3 * j + 1] = end; A.hits[3 * j + 2] = score;
+            if (A.infix) { A.o_pair[j] = pair; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = score; A.o_end[j] = in_end; }
+        }
+    }
+}
+static void k_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) {
+    for (int64_t j = 0; j < total; ++j) hits[3 * j] = o_start[j] < 0 ? -1 : hits[3 * j] + o_start[j];
+}
+#endif
+
 // Which form takes a pattern of nb blocks: the register form's instantiation (1, 2 or 4 blocks), or 0 = the workspace form.
 // QE_SEARCH_FORM = 0: the workspace form always; 1: the register form wherever it applies (up to QE_SEARCH_REG_BLOCKS
 // blocks = 256 bases).  Unset, the library's choice, by the rule of DESIGN.md 4.9 -- the register form only where its median
@@ -1055,6 +1107,30 @@ static void search_pairs(const quicked_batch& B, const SearchRun& sr, SearchList
     for (TaskList& l : S.L) l.pad();
 }
 
+// the workspace form's groups: Pv | Mv | S of the group's tallest pattern
+struct SearchWs { uint8_t* ws = nullptr; int64_t* d_ws_off = nullptr; int32_t* d_nb = nullptr; };
+static size_t search_group_bytes(int nb) { return ((size_t)nb * 64 * (8 + 8 + 4) + 255) & ~(size_t)255; }
+static SearchWs search_workspace(Context& C, const TaskList& Lw) {
+    SearchWs W;
+    const int ngw = Lw.ngroups();
+    std::vector<int64_t> ws_off((size_t)ngw);
+    std::vector<int32_t> g_nb((size_t)ngw);
+    size_t ws_bytes = 0;
+    for (int g = 0; g < ngw; ++g) {
+        int nb = 1;
+        for (int l = 0; l < 64; ++l) if (Lw.pair[(size_t)g * 64 + l] >= 0) nb = std::max(nb, search_blocks(Lw.m[(size_t)g * 64 + l]));
+        g_nb[g] = nb; ws_off[g] = (int64_t)ws_bytes;
+        ws_bytes += search_group_bytes(nb);
+    }
+    if (ngw) {
+        W.ws = C.scratch_p->take<uint8_t>(ws_bytes + 256);
+        W.d_ws_off = C.scratch_p->take<int64_t>((size_t)ngw); W.d_nb = C.scratch_p->take<int32_t>((size_t)ngw);
+        CopyBatch cb(C.stream);
+        h2d(W.d_ws_off, ws_off, C.stream); h2d(W.d_nb, g_nb, C.stream);
+    }
+    return W;
+}
+
 // Forward pass over whole pairs, then -- INFIX -- the start pass: the PREFIX form over the reversed planes on the stretch
 // that ends at text_end, bound d, the largest end; it reads the forward pass's results on the device and runs only the
 // tasks within their bound (no host round trip).  Leaves per task of `task_pair` score / start / end and the block steps
@@ -1073,25 +1149,8 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
     O.d_score = blk; O.d_start = blk + nt; O.d_end = blk + 2 * nt; O.d_adv = (u32*)(blk + 3 * nt);
     HIP_CHECK(hipMemsetAsync(blk, 0xFF, 3 * nt * sizeof(int32_t), C.stream));
     HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nt * sizeof(u32), C.stream));
-    // the workspace form's groups: Pv | Mv | S of the group's tallest pattern
-    const TaskList& Lw = S.L[0];
-    const int ngw = Lw.ngroups();
-    std::vector<int64_t> ws_off((size_t)ngw);
-    std::vector<int32_t> g_nb((size_t)ngw);
-    size_t ws_bytes = 0;
-    for (int g = 0; g < ngw; ++g) {
-        int nb = 1;
-        for (int l = 0; l < 64; ++l) if (Lw.pair[(size_t)g * 64 + l] >= 0) nb = std::max(nb, search_blocks(Lw.m[(size_t)g * 64 + l]));
-        g_nb[g] = nb; ws_off[g] = (int64_t)ws_bytes;
-        ws_bytes += ((size_t)nb * 64 * (8 + 8 + 4) + 255) & ~(size_t)255;
-    }
-    uint8_t* ws = nullptr; int64_t* d_ws_off = nullptr; int32_t* d_nb = nullptr;
-    if (ngw) {
-        ws = C.scratch_p->take<uint8_t>(ws_bytes + 256);
-        d_ws_off = C.scratch_p->take<int64_t>((size_t)ngw); d_nb = C.scratch_p->take<int32_t>((size_t)ngw);
-        CopyBatch cb(C.stream);
-        h2d(d_ws_off, ws_off, C.stream); h2d(d_nb, g_nb, C.stream);
-    }
+    const SearchWs Wk = search_workspace(C, S.L[0]);
+    uint8_t* const ws = Wk.ws; int64_t* const d_ws_off = Wk.d_ws_off; int32_t* const d_nb = Wk.d_nb;
     DevTasks T[4];
     for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
     auto pass = [&](bool start_pass) {
@@ -1117,6 +1176,136 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
         if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
         pass(true);
     }
+    return O;
+}
+
+// Every occurrence within the bound (quicked_batch_run_search_all): the forward pass in its all-occurrences form
+// (k_search_hits: found / best score / stored per pair, up to max_hits {end, score} per task), the offset scan over the stored
+// counts in the order of the pairs, and -- the one thing the host reads in between -- their total, which sizes the rest: the
+// stored occurrences become a task list on the device (k_hits_expand) and, INFIX, the best search's start pass runs one lane
+// per occurrence over its window of min(text_end, m + score) columns.  That list is in the order of the pairs, so its waves
+// mix the kernel forms: every form that has tasks gets a pair array of its own (-1 where an occurrence is another form's) and
+// a launch over the whole list; a wave without a lane of the form leaves at once.  The workspace form's groups are all as
+// tall as the list's tallest pattern, and are run in slices that share one workspace of at most 256 MiB (QE_SEARCH_HITS_WS_KB).
+// Both passes are timed as kind 0; d_adv / d_adv2 hold their block steps per task / per occurrence.
+struct SearchHitsOut {
+    std::vector<int32_t> task_pair;
+    int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
+    int64_t total = 0;
+};
+static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits) {
+    SearchHitsOut O;
+    size_t off[5] = {0, 0, 0, 0, 0};
+    for (int f = 0; f < 4; ++f) {
+        O.task_pair.insert(O.task_pair.end(), S.L[f].pair.begin(), S.L[f].pair.end());
+        off[f + 1] = O.task_pair.size();
+    }
+    const size_t nt = O.task_pair.size(), n = (size_t)B.n;
+    if (nt == 0) return O;
+    int32_t* blk = C.scratch_p->take<int32_t>(3 * n);
+    O.d_found = blk; O.d_best = blk + n;
+    int32_t* d_len = blk + 2 * n;
+    HIP_CHECK(hipMemsetAsync(O.d_found, 0, n * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(O.d_best, 0xFF, 2 * n * sizeof(int32_t), C.stream));
+    O.d_adv = C.scratch_p->take<u32>(nt);
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nt * sizeof(u32), C.stream));
+    int32_t* raw = C.scratch_p->take<int32_t>(2 * nt * (size_t)max_hits);
+    O.d_off = C.scratch_p->take<int64_t>(n + 1);
+    const SearchWs Wk = search_workspace(C, S.L[0]);
+    DevTasks T[4];
+    for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
+    auto* ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    for (int f = 0; f < 4; ++f) {
+        if (S.L[f].pair.empty()) continue;
+        SearchHitsArgs x{};
+        x.S.P = pair_view(B, false); x.S.T = T[f].v; x.S.mode = mode; x.S.o_adv = O.d_adv + off[f];
+        x.max_hits = max_hits; x.raw = raw + 2 * off[f] * (size_t)max_hits;
+        x.o_found = O.d_found; x.o_best = O.d_best; x.o_len = d_len;
+        const size_t ng = (size_t)S.L[f].ngroups();
+        if (f == 0) { x.S.ws = Wk.ws; x.S.g_ws_off = Wk.d_ws_off; x.S.g_nb = Wk.d_nb; launch_groups(C, k_search_hits<0>, x, ng, 4, 0); }
+        else if (f == 1) launch_groups(C, k_search_hits<1>, x, ng, 4, 0);
+        else if (f == 2) launch_groups(C, k_search_hits<2>, x, ng, 4, 0);
+        else launch_groups(C, k_search_hits<4>, x, ng, 4, 0);
+    }
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    // offsets in the order of the pairs (a pair without a task has -1 + 1 = 0 stored; every pair counts: the lengths stand in
+    // for the scan's list of tasks), the total behind them
+    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, (const int32_t*)d_len, (const int32_t*)B.d_p_len, O.d_off, O.d_off + n, (int)n);
+    HIP_CHECK(hipGetLastError());
+    {
+        std::vector<int64_t> tot;
+        FetchBatch fb(C);
+        fb.add(tot, (const int64_t*)(O.d_off + n), 1);
+        fb.sync();
+        O.total = tot[0];
+    }
+    if (O.total <= 0) return O;
+    const size_t nh = (size_t)O.total;
+    const bool infix = mode == SEARCH_INFIX;
+    O.d_hits = C.scratch_p->take<int32_t>(3 * nh);
+    int32_t *o_m = nullptr, *o_n = nullptr, *o_score = nullptr, *o_end = nullptr, *o_start = nullptr, *o_pair[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (infix) {
+        int32_t* q = C.scratch_p->take<int32_t>(5 * nh);
+        o_m = q; o_n = q + nh; o_score = q + 2 * nh; o_end = q + 3 * nh; o_start = q + 4 * nh;
+        HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
+        for (int f = 0; f < 4; ++f) {
+            if (S.L[f].pair.empty()) continue;
+            o_pair[f] = C.scratch_p->take<int32_t>(nh);
+            HIP_CHECK(hipMemsetAsync(o_pair[f], 0xFF, nh * sizeof(int32_t), C.stream));
+        }
+        O.d_adv2 = C.scratch_p->take<u32>(nh);
+        HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
+    }
+    for (int f = 0; f < 4; ++f) {
+        if (S.L[f].pair.empty()) continue;
+        HitExpandArgs e{};
+        e.T = T[f].v; e.max_hits = max_hits; e.infix = infix ? 1 : 0; e.raw = raw + 2 * off[f] * (size_t)max_hits;
+        e.len = d_len; e.off = O.d_off; e.hits = O.d_hits;
+        e.o_pair = o_pair[f]; e.o_m = o_m; e.o_n = o_n; e.o_score = o_score; e.o_end = o_end;
+        hipLaunchKernelGGL(k_hits_expand, dim3((unsigned)((S.L[f].pair.size() + 255) / 256)), dim3(256), 0, C.stream, e);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (!infix) return O;
+    if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    const size_t ngh = (nh + 63) / 64;
+    for (int f = 0; f < 4; ++f) {
+        if (S.L[f].pair.empty()) continue;
+        SearchArgs a{};
+        a.P = pair_view(B, true);
+        a.mode = SEARCH_PREFIX; a.flags = SEARCH_LARGEST_END;
+        size_t slice = ngh;                              // groups per launch
+        if (f == 0) {
+            int nb = 1;
+            for (size_t t = 0; t < S.L[0].pair.size(); ++t) if (S.L[0].pair[t] >= 0) nb = std::max(nb, search_blocks(S.L[0].m[t]));
+            const size_t gb = search_group_bytes(nb);
+            slice = std::max<size_t>(1, std::min(ngh, ((size_t)std::max<long long>(1, sw_ll(Sw::SearchHitsWsKb)) << 10) / gb));
+            std::vector<int64_t> ws_off(slice);
+            std::vector<int32_t> g_nb(slice, nb);
+            for (size_t g = 0; g < slice; ++g) ws_off[g] = (int64_t)(g * gb);
+            a.ws = C.scratch_p->take<uint8_t>(slice * gb + 256);
+            int64_t* d_ws_off = C.scratch_p->take<int64_t>(slice); int32_t* d_nb = C.scratch_p->take<int32_t>(slice);
+            CopyBatch cb(C.stream);
+            h2d(d_ws_off, ws_off, C.stream); h2d(d_nb, g_nb, C.stream);
+            a.g_ws_off = d_ws_off; a.g_nb = d_nb;
+        }
+        for (size_t g0 = 0; g0 < ngh; g0 += slice) {
+            const size_t j0 = g0 * 64, ng = std::min(slice, ngh - g0);
+            a.T = TaskView{};
+            a.T.ntasks = (int32_t)std::min(nh - j0, ng * 64);
+            a.T.pair = o_pair[f] + j0; a.T.m = o_m + j0; a.T.n = o_n + j0; a.T.cutoff = o_score + j0;
+            a.in_score = o_score + j0; a.in_end = o_end + j0; a.o_start = o_start + j0; a.o_adv = O.d_adv2 + j0;
+            if (f == 0) launch_groups(C, k_search<0>, a, ng, 4, 0);
+            else if (f == 1) launch_groups(C, k_search<1>, a, ng, 4, 0);
+            else if (f == 2) launch_groups(C, k_search<2>, a, ng, 4, 0);
+            else launch_groups(C, k_search<4>, a, ng, 4, 0);
+        }
+    }
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    hipLaunchKernelGGL(k_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
+    HIP_CHECK(hipGetLastError());
     return O;
 }
 
@@ -1472,6 +1661,9 @@ static void reset_host_results(quicked_batch& B) {
     B.wr->md_pool.size = 0;
     if (B.search_run) { B.wr->text_start.assign((size_t)B.n, -1); B.wr->text_end.assign((size_t)B.n, -1); }
     else { B.wr->text_start.clear(); B.wr->text_end.clear(); }
+    if (B.hits_run) { B.wr->found.assign((size_t)B.n, 0); B.wr->hit_off.assign((size_t)B.n + 1, 0); }
+    else { B.wr->found.clear(); B.wr->hit_off.clear(); }
+    B.wr->hits.clear();
     B.wr->deferred_pairs = 0;
 }
 

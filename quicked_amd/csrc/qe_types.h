@@ -122,6 +122,30 @@ struct SearchArgs {
     int32_t* o_score;  int32_t* o_end;  int32_t* o_start;  u32* o_adv;
 };
 
+// Every occurrence within the bound (k_search_hits<NB>, qe_search.h: SearchHitScan): the forward pass of k_search with the
+// bound kept -- S.P / S.T / S.mode / S.ws .. S.g_nb / S.o_adv as there, S.flags 0, the other fields of S unused.  Per task t
+// up to max_hits {end, score} at raw[2 (t max_hits + i)], ordered by end; per PAIR o_found = the occurrences, o_best = the
+// smallest score among them (-1: none), o_len = the stored ones - 1 (what k_scan_offsets adds 1 to).  A lane without a task
+// writes nothing.
+struct SearchHitsArgs {
+    SearchArgs S;
+    int32_t max_hits;
+    int32_t* raw;
+    int32_t* o_found;  int32_t* o_best;  int32_t* o_len;
+};
+// The stored occurrences of a task list become one start-pass task each (k_hits_expand), in the order of the pairs: occurrence
+// i of the list's task t is number j = off[pair] + i of the run.  hits[j] = {text_end - window (PREFIX: 0), text_end, score};
+// o_pair[j] / o_m[j] / o_n[j] / o_score[j] / o_end[j] = T.pair / T.m / T.n / in_score / in_end of a start pass over the
+// occurrence's window (search_hit_task; INFIX only: a PREFIX run has no start pass).  k_hits_finish then adds the pass's o_start to text_start (or leaves -1).
+struct HitExpandArgs {
+    TaskView T;                              // the forward pass's list
+    int32_t max_hits, infix;
+    const int32_t* raw;                      // of the list's first task
+    const int32_t* len;  const int64_t* off; // per pair: stored - 1, the offset scan over it
+    int32_t* hits;                           // quicked_hit_t[total] as {text_start, text_end, score}
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;
+};
+
 // BandEd score-only, G lanes per alignment (cooperative form of k_banded<false>)
 struct CoopArgs {
     PairView P;
