@@ -394,9 +394,10 @@ __device__ __forceinline__ void run64_skew_fill(u64 (&P)[K], u64 (&M)[K], const 
 //   sum_c hout_k(c) = sum_c hin_(k+1)(c) = sum_c hout_(k+1)(c) - (v_(k+1) after - v_(k+1) before),
 // v = sum of a block's vertical deltas -- exact for any block state, because every cell of the step satisfies
 // v' - v = h - h_above (the step evaluates the min-recurrence cell by cell).
-template <int K>
+template <int K, bool RING = false>
 // `stride` = elements between consecutive slots / rows of one lane's state (64 in k_banded's layout, the tasks per wave in
-// k_banded_coop's); scores[] is read from Srd and written to Swr (the cooperative kernel double-buffers it by chunk parity)
+// k_banded_coop's); scores[] is read from Srd and written to Swr (the cooperative kernel double-buffers it by chunk parity).
+// RING: scores[] is the ring of k_banded<false, true> (qe_types.h: score_lds_row), not an array of absolute block rows
 __device__ __forceinline__ void slots_pass(int nl, int i, int r, u64* Pv, u64* Mv, const int32_t* Srd, int32_t* Swr, int64_t stride,
                                            const u64* pp, int p0, u64 T0, u64 T1, u64& hinP, u64& hinM, u32& adv) {
     u64 P[K], M[K], a[K], b[K];
@@ -406,7 +407,7 @@ __device__ __forceinline__ void slots_pass(int nl, int i, int r, u64* Pv, u64* M
         P[k] = 0; M[k] = 0; a[k] = 0; b[k] = 0; sc[k] = 0;
         if (k < nl) {
             u64 nn;
-            P[k] = Pv[(int64_t)(i + k) * stride]; M[k] = Mv[(int64_t)(i + k) * stride]; sc[k] = Srd[(int64_t)(r + k) * stride];
+            P[k] = Pv[(int64_t)(i + k) * stride]; M[k] = Mv[(int64_t)(i + k) * stride]; sc[k] = Srd[(int64_t)(RING ? score_lds_row(r + k) : r + k) * stride];
             load_planes(pp, p0 + 64 * (r + k), a[k], b[k], nn);
         }
         v0[k] = __popcll(P[k]) - __popcll(M[k]);
@@ -418,7 +419,7 @@ __device__ __forceinline__ void slots_pass(int nl, int i, int r, u64* Pv, u64* M
 #pragma unroll
         for (int k = K - 1; k >= 0; --k) {
             if (k < nl) {
-                Swr[(int64_t)(r + k) * stride] = sc[k] + d;
+                Swr[(int64_t)(RING ? score_lds_row(r + k) : r + k) * stride] = sc[k] + d;
                 Pv[(int64_t)(i + k - 1) * stride] = P[k]; Mv[(int64_t)(i + k - 1) * stride] = M[k];   // band shift (bpm_banded.c:903-909)
             }
             d -= (__popcll(P[k]) - __popcll(M[k])) - v0[k];
@@ -895,19 +896,24 @@ __device__ __forceinline__ GroupWs group_ws(uint8_t* ws, int64_t off, int ns, in
 #ifndef QE_FILL_K
 #define QE_FILL_K 3          // slots per skewed pass of the fill (1: single-slot passes only)
 #endif
-template <bool FILL>
+// LDS (score-only, the first launch of a two-pass run whose bands fit: launch_banded_narrow): Pv, Mv and scores[] of a wave
+// live in its slice of the workgroup's LDS instead of the group workspace -- scores[] as a ring (qe_types.h: score_lds_*).
+// Same walk, same values; the kernel then has global loads only (the planes), and nothing waits behind a store.
+#define QE_HAVE_K_BANDED_LDS 1
+template <bool FILL, bool LDS = false>
 __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
+    static_assert(!(FILL && LDS), "the fill's state stays in the group workspace");
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
     if (g * 64 >= A.T.ntasks) return;
     int pair = (t < A.T.ntasks) ? A.T.pair[t] : -1;
     if (A.only_if != nullptr && pair >= 0 && A.only_if[t] == 0) pair = -1;
-    const bool valid = pair >= 0;
-    if (!__any(valid)) return;
+    const bool have = pair >= 0;
+    if (!__any(have)) return;
     int m = 1, n = 1, p0 = 0, t0 = 0, cut_in = 0, tfin = 0, prune = 0x7fffffff;
     const u64* pp = A.P.pl_p;
     const u64* tp = A.P.pl_t;
     u32 fl = 0;
-    if (valid) {
+    if (have) {
         m = A.T.m[t]; n = A.T.n[t]; p0 = A.T.p0[t]; t0 = A.T.t0[t];
         cut_in = A.T.cutoff[t];
         tfin = FILL ? n : A.T.tfin[t];
@@ -922,7 +928,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                                                                    // task's cutoff (BandedArgs::prune); without one the geometry's clamped cutoff, as ever
     const int nw = (m + 63) >> 6;
     // the score-only kernels use their own narrower band (bpm_banded.c:801-803) -- unless the launch asks for the fill's
-    const bool fgeom = FILL || A.fill_geom != 0;
+    const bool fgeom = FILL || (!LDS && A.fill_geom != 0);         // (the ring of the LDS form is sized for the stop rule nw)
     const int nsl = fgeom ? G.ebb : ((G.cutoff + 63) >> 6) + 1;
     const int stop_row = fgeom ? nw - 1 : nw;                      // bpm_banded.c:295 / 917
     const int lvl_last = (m - 1) & 63;                             // level_mask of the last block
@@ -930,11 +936,20 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
     int max_row_init = nsl - 1;
     u32 adv = 0;
 
-    const int gns = A.g_nslots[g], gnr = A.g_nrows[g], gnch = A.g_nch[g];
-    const GroupWs W = group_ws(A.ws, A.g_ws_off[g], gns, gnr, gnch);
+    const int gns = LDS ? A.lds_slots : A.g_nslots[g], gnr = LDS ? 0 : A.g_nrows[g], gnch = LDS ? 0 : A.g_nch[g];
+    GroupWs W;
+    if (LDS) {
+        // this wave's slice: Pv[(lds_slots + 1)][64] | Mv[(lds_slots + 1)][64] | scores ring [score_lds_ring()][64]
+        uint8_t* lb = (uint8_t*)qe_dyn_lds + (size_t)QE_WAVE_IN_BLOCK() * (size_t)score_lds_bytes(gns);
+        W.Pv = (u64*)lb; W.Mv = W.Pv + (gns + 1) * 64; W.S = (int32_t*)(W.Mv + (gns + 1) * 64); W.cf = nullptr; W.cl = nullptr;
+        // a band the slice cannot hold (the launch's bound rules it out) is not walked: its task reports -1, "proves nothing"
+        if (nsl > gns) pair = -1;
+    } else W = group_ws(A.ws, A.g_ws_off[g], gns, gnr, gnch);
+    const bool valid = pair >= 0;
     u64* const Pv = W.Pv + 64 + lane;        // slot s lives at Pv[s * 64]; slot -1 is addressable
     u64* const Mv = W.Mv + 64 + lane;
-    int32_t* const S = W.S + lane;           // scores[] indexed by absolute block row (bpm_banded.c:180-197)
+    int32_t* const S = W.S + lane;           // scores[] indexed by absolute block row (bpm_banded.c:180-197), LDS: by srow() of it
+    auto srow = [](int r) { return (int64_t)(LDS ? score_lds_row(r) : r) * 64; };
     // fill: per group  cp[QE_CPC nch][ns][64] = {Pv, Mv} after every QE_CP_COLS-th stored column (in the slot numbering of the
     // chunk that starts at / contains it), then  hw[nch][ns][64] = the carry-in words of every (chunk, slot)
     uint4* const cp = FILL ? A.mat + A.g_mat_off[g] + lane : nullptr;
@@ -946,7 +961,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
         if (valid && s < nsl) {
             Pv[(int64_t)s * 64] = QE_ONES;
             Mv[(int64_t)s * 64] = 0;
-            S[(int64_t)s * 64] = 64 * (s + 1);
+            S[srow(s)] = 64 * (s + 1);
             if (FILL) cp[(int64_t)s * 64] = make_uint4(~0u, ~0u, 0u, 0u);
         }
     }
@@ -983,7 +998,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
         const bool unaligned = __any(psh != 0);
         auto prefetch = [&](int j) {
             const int jc = min(max(j, 0), gns - 1), rc = min(max(j + pos_v, 0), gnr - 1), rp = min(max(j + pos_v, 0), nw);
-            qP = Pv[(int64_t)jc * 64]; qM = Mv[(int64_t)jc * 64]; qS = S[(int64_t)rc * 64];
+            qP = Pv[(int64_t)jc * 64]; qM = Mv[(int64_t)jc * 64]; qS = S[srow(rc)];
             const u64* w = pp + 3 * (int64_t)((p0 >> 6) + rp);
             qa0 = w[0]; qb0 = w[1];
             if (unaligned) { qa1 = w[3]; qb1 = w[4]; }            // Hirschberg children start anywhere in their pair's pattern
@@ -1006,8 +1021,8 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                     return !__any(bad);
                 };
                 if (i == first) { hinP = QE_ONES; hinM = 0; }
-                if (x + 3 <= i1 && planned(4)) { slots_pass<4>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
-                if (x + 1 <= i1 && planned(2)) { slots_pass<2>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
+                if (x + 3 <= i1 && planned(4)) { slots_pass<4, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
+                if (x + 1 <= i1 && planned(2)) { slots_pass<2, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
             }
             if (FILL && QE_FILL_K > 1 && A.fill_multi && x + QE_FILL_K - 1 <= i1) {
                 // K slots in one skewed pass, every lane with the slots inside its own band, unless a lane needs the
@@ -1029,7 +1044,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                         P[q] = 0; M[q] = 0; a[q] = 0; b[q] = 0; sc[q] = 0;
                         if (actk[q]) {
                             u64 nn;
-                            P[q] = Pv[(int64_t)(i + q) * 64]; M[q] = Mv[(int64_t)(i + q) * 64]; sc[q] = S[(int64_t)(r + q) * 64];
+                            P[q] = Pv[(int64_t)(i + q) * 64]; M[q] = Mv[(int64_t)(i + q) * 64]; sc[q] = S[srow(r + q)];
                             load_planes(pp, p0 + 64 * (r + q), a[q], b[q], nn);
                         }
                     }
@@ -1044,7 +1059,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                             const u64 iP = (q == 0) ? hinP : (topk[q] ? QE_ONES : oP[q > 0 ? q - 1 : 0]);
                             const u64 iM = (q == 0) ? hinM : (topk[q] ? (u64)0 : oM[q > 0 ? q - 1 : 0]);
                             hw[((int64_t)k * gns + (i + q)) * 64] = make_uint4(lo32(iP), hi32(iP), lo32(iM), hi32(iM));
-                            S[(int64_t)(r + q) * 64] = sc[q] + __popcll(oP[q]) - __popcll(oM[q]);
+                            S[srow(r + q)] = sc[q] + __popcll(oP[q]) - __popcll(oM[q]);
                             Pv[(int64_t)(i + q - 1) * 64] = P[q]; Mv[(int64_t)(i + q - 1) * 64] = M[q];   // band shift (bpm_banded.c:903-909)
                             adv += 64u;
                         }
@@ -1068,7 +1083,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             } else if (act) {
                 P = Pv[(int64_t)i * 64];
                 M = Mv[(int64_t)i * 64];
-                sc = S[(int64_t)r * 64];
+                sc = S[srow(r)];
                 load_planes(pp, p0 + 64 * r, a, b, nn);
             }
             if (i == first) { hinP = QE_ONES; hinM = 0; }          // PHin = 1 into the band's top block
@@ -1092,7 +1107,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             }
             if (act) {
                 sc += __popcll(sP) - __popcll(sM);
-                S[(int64_t)r * 64] = sc;
+                S[srow(r)] = sc;
                 // in-place band shift: slot i of this chunk is slot i-1 of the next (bpm_banded.c:903-909)
                 const int64_t dst = (ncols == 64) ? (int64_t)(i - 1) * 64 : (int64_t)i * 64;
                 Pv[dst] = P;
@@ -1105,30 +1120,30 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
             // every-64-columns bookkeeping (bpm_banded.c:889-922 / 264-301)
             const bool c1 = (first + 2 < last) && (G.fin > 64 * (first + 1));
             bool cut_lo = false;
-            if (c1) cut_lo = S[(int64_t)(first + pos_v + 1) * 64] + (G.fin - 64 * (first + 1)) > thr;
+            if (c1) cut_lo = S[srow(first + pos_v + 1)] + (G.fin - 64 * (first + 1)) > thr;
             if (cut_lo && pos_h >= G.prolog) first++;
             else if (!cut_lo && pos_h < G.prolog) first--;
             Pv[(int64_t)last * 64] = QE_ONES;
             Mv[(int64_t)last * 64] = 0;
             if (FILL) cp[(int64_t)(QE_CPC * k + QE_CPC) * cps + (int64_t)last * 64] = make_uint4(~0u, ~0u, 0u, 0u);
             const int pos = last + pos_v;
-            S[(int64_t)(pos + 1) * 64] = S[(int64_t)pos * 64] + 64;
+            S[srow(pos + 1)] = S[srow(pos)] + 64;
             max_row_init = max(max_row_init, pos + 1);
             const bool c2 = (first + 2 < last) && (64 * (last - 1) > G.fin);
             bool cut_hi = false;
-            if (c2) cut_hi = S[(int64_t)(last + pos_v - 1) * 64] + (64 * (last - 1) - G.fin) > thr;
+            if (c2) cut_hi = S[srow(last + pos_v - 1)] + (64 * (last - 1) - G.fin) > thr;
             if (cut_hi || (pos_v + last >= stop_row)) last--;
             pos_v++;
             pos_h++;
             if (FILL) { W.cf[(int64_t)pos_h * 64 + lane] = (int16_t)first; W.cl[(int64_t)pos_h * 64 + lane] = (int16_t)last; }
         }
     }
-    if (valid) {
+    if (have) {
         // final score read-out (bpm_banded.c:952-961); -1: band never reached the last block (A.7(3))
         const int row = nw - 1;
         int score = -1;
-        if (row <= max_row_init) {
-            score = S[(int64_t)row * 64];
+        if (valid && row <= max_row_init) {
+            score = S[srow(row)];
             if (m & 63) score -= 64 - (m & 63);
         }
         A.o_score[t] = score;
@@ -1142,6 +1157,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
 
 template __global__ void k_banded<false>(BandedArgs);
 template __global__ void k_banded<true>(BandedArgs);
+template __global__ void k_banded<false, true>(BandedArgs);
 
 // ===========================================================================
 // Bounded edit distance, diagonal-word form (qe_bounded.h): one lane per pair, score only, for tasks whose Ukkonen band

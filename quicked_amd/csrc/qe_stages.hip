@@ -295,7 +295,7 @@ static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskL
 // find pair = -1 and return.  Both launches share one group workspace, laid out for the list's largest geometry at the
 // full cutoff -- the membership of the second launch's groups is decided on the device.
 // ---------------------------------------------------------------------------
-struct NarrowPlan { bool ok = false; int cls = 0; size_t live = 0, narrower = 0; };
+struct NarrowPlan { bool ok = false; int cls = 0; size_t live = 0, narrower = 0; int slots1 = 0; };      // slots1: see score_lds_slots
 // whole-text passes only (a stopped band is exported from ONE pass: Hirschberg half passes keep the single pass)
 static NarrowPlan narrow_plan(const TaskList& L) {
     NarrowPlan P;
@@ -304,7 +304,9 @@ static NarrowPlan narrow_plan(const TaskList& L) {
         if (L.pair[t] < 0) continue;
         if (L.tfin[t] != L.n[t]) return P;
         ++P.live;
-        P.narrower += narrow_cutoff(L.m[t], L.n[t], L.cutoff[t]) != L.cutoff[t];
+        const int c1 = narrow_cutoff(L.m[t], L.n[t], L.cutoff[t]);
+        P.narrower += c1 != L.cutoff[t];
+        P.slots1 = std::max(P.slots1, narrow_slots(L.m[t], L.n[t], c1));
         n_max = std::max(n_max, L.n[t]);
     }
     while ((n_max >> (P.cls + 1)) != 0 && P.cls < 31) ++P.cls;
@@ -481,7 +483,24 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
     return S;
 }
 
-static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q, int qp) {
+// Band state in LDS for the FIRST launch (k_banded<false, true>): the slot count its slices are sized for, or 0
+// = the group workspace as ever.  The bound on a task's first-launch band is its slot count at narrow_cutoff -- the fit only
+// ever takes fewer, a task that keeps its cutoff walks exactly that; narrow_plan takes the largest over the list in the scan it
+// makes anyway (NarrowPlan::slots1) -- and the list takes the form when that fits the budget of qe_types.h.  At the cap a
+// workgroup's four slices are 72 KB: two workgroups still share a CU (launch_groups).  QE_SCORE_LDS = 0: never, 1: whatever
+// the list's size (by default a list of a group per SIMD, as the two passes themselves: smaller launches were not measured).
+static int score_lds_slots(const Context& C, const TaskList& L, int bound) {
+#ifndef QE_HAVE_K_BANDED_LDS
+    (void)C; (void)L; (void)bound;
+    return 0;                                        // a kernels header without the form (the host-only build's stand-ins)
+#else
+    const int mode = sw(Sw::ScoreLds);
+    if (mode == 0 || (mode != 1 && (size_t)L.ngroups() < (size_t)chip(C.device).simds)) return 0;
+    return score_lds_fits(bound) ? bound : 0;
+#endif
+}
+
+static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q, int qp, int slots1) {
     ScoreLaunch S;
     S.nt = L.pair.size();
     const size_t nt = S.nt;
@@ -509,6 +528,12 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     a.T.cutoff = x.cut1;
     if (x.qp > 0) a.prune = x.prune1;                // (without a ratio prune1 = cut1: today's launch)
     a.lane_rel = sw(Sw::LaneRel);
+    a.lds_slots = score_lds_slots(C, L, slots1);
+    if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots)\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots);
+#ifdef QE_HAVE_K_BANDED_LDS
+    if (a.lds_slots) launch_groups(C, k_banded<false, true>, a, L.ngroups(), 8, (size_t)score_lds_bytes(a.lds_slots));
+    else
+#endif
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
     x.phase = 1;
     hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
@@ -832,7 +857,7 @@ static void run_banded_score(quicked_batch& B, Context& C, const TaskList& L, bo
         narrow = policy && take == 1;
         probe = policy && take == 2;
     }
-    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay, narrow_fit_q(C, np.cls, policy), narrow_prune_q(C, np.cls, policy)) :
+    const ScoreLaunch S = narrow ? launch_banded_narrow(B, C, L, reversed, 1, ulay, narrow_fit_q(C, np.cls, policy), narrow_prune_q(C, np.cls, policy), np.slots1) :
                           probe ? launch_banded_probe(B, C, L, reversed, 1) :
                           lg ? launch_banded_sys(B, C, L, reversed, lg, 1) :
                           wave ? launch_banded_wave(B, C, L, reversed, 1)

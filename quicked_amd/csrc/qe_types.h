@@ -94,6 +94,8 @@ struct BandedArgs {
     const int32_t* prune = nullptr;   // k_banded<false>: per task, beside T.cutoff: where prune[t] < T.cutoff[t] the band-edge rules compare against it
                                   // instead of the geometry's cutoff -- the fitted first launch of a two-pass run (narrow_prune); null, or a value
                                   // that is not below the task's cutoff: the geometry's (clamped) cutoff, as every other launch
+    int32_t lds_slots = 0;        // k_banded<false, true> only: the band slots every wave's slice of the LDS holds (score_lds_bytes(lds_slots)
+                                  // per wave); the group workspace is not touched
 };
 
 // Bounded edit distance, diagonal-word form (k_bounded_diag, qe_bounded.h): whole pairs (p0 = t0 = 0), T.cutoff = the pair's
@@ -358,6 +360,21 @@ QE_T_HD int pass_plan(int i, int K, int lo, int hi, int r, int nw, bool plain, b
     fallback = nl > 0 && (a0 != i || !plain || r + nl - 1 >= nw - 1);
     return nl;
 }
+
+// Band state in LDS (k_banded<false, true>; DESIGN.md 4.1, "Band state in LDS"): the budget, one definition for the launch
+// and the kernel.  A wave's slice holds Pv[s + 1][64] u64 | Mv[s + 1][64] u64 (slot -1 included) for bands of up to s slots
+// and scores[] as a ring of score_lds_ring() block rows x 64 lanes, row r at index r & (ring - 1).
+// The ring's invariant: with the score-only geometry (stop rule nw) a chunk reads and writes the rows
+// first + pos_v .. last + pos_v + 1 only -- at most slots + 1 consecutive rows, first + pos_v and last + pos_v never decrease
+// from chunk to chunk -- and no row above nw + 1 is ever written (last-- once pos_v + last reaches nw).  So with
+// slots + 1 <= ring - 2 no two rows of a chunk share an index, and row nw - 1 shares one only with rows nw - 1 -+ ring:
+// the lower one left the window before nw - 1 entered it, the upper one does not exist.  The read-out finds row nw - 1
+// as it was last written.
+QE_T_HD int score_lds_ring() { return 16; }
+QE_T_HD int score_lds_cap() { return score_lds_ring() - 3; }        // 13 slots: a window of 14 rows
+QE_T_HD bool score_lds_fits(int slots) { return slots >= 1 && slots <= score_lds_cap(); }
+QE_T_HD int score_lds_row(int r) { return r & (score_lds_ring() - 1); }
+QE_T_HD int score_lds_bytes(int slots) { return 2 * (slots + 1) * 64 * 8 + score_lds_ring() * 64 * 4; }      // per wave: 18 KB at the cap
 
 // k_narrow, one thread per task of the list T (whole-text passes: tfin = n).  phase 0: cut1 = narrow_cutoff of every task,
 // the packed list emptied, the statistics zeroed.  phase 1, after the first pass: a task whose cutoff was halved and whose
