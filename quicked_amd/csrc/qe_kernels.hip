@@ -429,6 +429,110 @@ __device__ __forceinline__ void slots_pass(int nl, int i, int r, u64* Pv, u64* M
     hinP = houtP; hinM = houtM;
 }
 
+// A TALL pass (k_banded<false, true>; DESIGN.md 4.1, "Tall passes"): K = 5 .. 10 adjacent slots over 64 columns, the whole
+// walk of a fitted wave's chunk.  run64_skew unrolls its 32 + K - 1 pass steps and keeps all 32 mask pairs (K = 6: 256 VGPRs
+// and scratch, 6 KB of code per slot), so this body is a ROLLED loop over column pairs, the masks and slot 0's carry-ins
+// taken from their words at a running bit index.  Inside an iteration the two columns run one slot apart -- slot k of
+// column c beside slot k - 1 of column c + 1, which do not depend on one another -- which is the skew's independent work
+// without its triangular ends and without a window of masks.  Per cell the arithmetic of run64_multi / run64_skew
+// (block_step_core, the lowest slot block_step_collect), hence the same bits.
+template <int K>
+__device__ __forceinline__ void run64_tall(u64 (&P)[K], u64 (&M)[K], const u64 (&a)[K], const u64 (&b)[K],
+                                           u64 T0, u64 T1, u64 hinP, u64 hinM, u64& houtP, u64& houtM) {
+    u32 alo[K], ahi[K], blo[K], bhi[K], Plo[K], Phi[K], Mlo[K], Mhi[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        alo[k] = lo32(a[k]); ahi[k] = hi32(a[k]); blo[k] = lo32(b[k]); bhi[k] = hi32(b[k]);
+        Plo[k] = lo32(P[k]); Phi[k] = hi32(P[k]); Mlo[k] = lo32(M[k]); Mhi[k] = hi32(M[k]);
+    }
+    u32 oPlo = 0, oPhi = 0, oMlo = 0, oMhi = 0;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+        const u32 t0 = half ? hi32(T0) : lo32(T0), t1 = half ? hi32(T1) : lo32(T1);
+        const u32 hp = half ? hi32(hinP) : lo32(hinP), hm = half ? hi32(hinM) : lo32(hinM);
+        u32 gP = 0, gM = 0;
+#pragma unroll 1
+        for (int c = 0; c < 32; c += 2) {
+            u32 m0[2], m1[2], cP[2], cM[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                m0[j] = (u32)__builtin_amdgcn_sbfe((int)t0, (u32)(c + j), 1u);
+                m1[j] = (u32)__builtin_amdgcn_sbfe((int)t1, (u32)(c + j), 1u);
+                cP[j] = __builtin_amdgcn_ubfe(hp, (u32)(c + j), 1u);
+                cM[j] = __builtin_amdgcn_ubfe(hm, (u32)(c + j), 1u);
+            }
+#pragma unroll
+            for (int s = 0; s <= K; ++s) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {            // column c + j at slot s - j; the lowest slot collects c before c + 1
+                    const int k = s - j;
+                    if (k < 0 || k >= K) continue;
+                    const u32 elo = bitop3<0x90>(~(alo[k] ^ m0[j]), blo[k], m1[j]), ehi = bitop3<0x90>(~(ahi[k] ^ m0[j]), bhi[k], m1[j]);
+                    if (k + 1 < K) {
+                        u32 phhi, mhhi;
+                        block_step_core(elo, ehi, Plo[k], Phi[k], Mlo[k], Mhi[k], cP[j], cM[j], phhi, mhhi);
+                        cP[j] = phhi >> 31; cM[j] = mhhi >> 31;
+                    } else {
+                        block_step_collect(elo, ehi, Plo[k], Phi[k], Mlo[k], Mhi[k], cP[j], cM[j], gP, gM);
+                    }
+                }
+            }
+        }
+        const u32 rP = __builtin_bitreverse32(gP), rM = __builtin_bitreverse32(gM);
+        if (half) { oPhi = rP; oMhi = rM; } else { oPlo = rP; oMlo = rM; }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) { P[k] = mk64(Plo[k], Phi[k]); M[k] = mk64(Mlo[k], Mhi[k]); }
+    houtP = mk64(oPlo, oPhi);
+    houtM = mk64(oMlo, oMhi);
+}
+
+// slots_pass around a tall pass, k_banded<false, true>'s layout (64 lanes per row, scores[] the ring): every read of the
+// pass -- Pv, Mv, scores[] and the pattern planes of all live slots -- is issued before the first block step; the planes as
+// raw words, shifted afterwards (`unaligned`, wave-uniform: some lane's pattern starts inside a word), so that no load
+// waits inside a branch.  Stores and the scores chain as in slots_pass.
+template <int K>
+__device__ __forceinline__ void slots_pass_tall(int nl, int i, int r, u64* Pv, u64* Mv, int32_t* S, const u64* pp, int p0, bool unaligned,
+                                                u64 T0, u64 T1, u64& hinP, u64& hinM, u32& adv) {
+    u64 P[K], M[K], a[K], b[K], a1[K], b1[K];
+    int sc[K], v0[K];
+    const int psh = p0 & 63;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        P[k] = 0; M[k] = 0; a[k] = 0; b[k] = 0; a1[k] = 0; b1[k] = 0; sc[k] = 0;
+        if (k < nl) {
+            P[k] = Pv[(int64_t)(i + k) * 64]; M[k] = Mv[(int64_t)(i + k) * 64]; sc[k] = S[(int64_t)score_lds_row(r + k) * 64];
+            const u64* w = pp + 3 * (int64_t)((p0 >> 6) + r + k);
+            a[k] = w[0]; b[k] = w[1];
+            if (unaligned) { a1[k] = w[3]; b1[k] = w[4]; }
+        }
+    }
+    if (unaligned) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            a[k] = (a[k] >> psh) | ((a1[k] << 1) << (63 - psh));
+            b[k] = (b[k] >> psh) | ((b1[k] << 1) << (63 - psh));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) v0[k] = __popcll(P[k]) - __popcll(M[k]);
+    u64 houtP, houtM;
+    run64_tall<K>(P, M, a, b, T0, T1, hinP, hinM, houtP, houtM);
+    if (nl > 0) {
+        int d = __popcll(houtP) - __popcll(houtM);          // sum of the bottom-row deltas of slot k, from the lowest up
+#pragma unroll
+        for (int k = K - 1; k >= 0; --k) {
+            if (k < nl) {
+                S[(int64_t)score_lds_row(r + k) * 64] = sc[k] + d;
+                Pv[(int64_t)(i + k - 1) * 64] = P[k]; Mv[(int64_t)(i + k - 1) * 64] = M[k];   // band shift (bpm_banded.c:903-909)
+            }
+            d -= (__popcll(P[k]) - __popcll(M[k])) - v0[k];
+        }
+        adv += 64u * (u32)nl;
+    }
+    hinP = houtP; hinM = houtM;
+}
+
 // Second 64-column chunk of an on-chip WindowEd(2,1) window: its two blocks in one skewed pass (slot 1 one column behind
 // slot 0, cf. run64_skew).  Slot 0 collects its 64 carry-outs (gP / gM: the traceback recomputes block 1's tiles from
 // them), slot 1 leaves {Pv, Mv} BEFORE every 8th column in LDS (st[grp * st_stride], run64_fast's STORE == 3).
@@ -1021,6 +1125,25 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                     return !__any(bad);
                 };
                 if (i == first) { hinP = QE_ONES; hinM = 0; }
+                if constexpr (LDS) {
+                    // one pass at the height of the chunk's walk (tall_height; a taller walk: its head) where no lane needs
+                    // the general form or starts inside it; otherwise, and for what is left, the plan below
+                    if (x == i0 && A.score_tall) {
+                        const int K = __builtin_amdgcn_readfirstlane(tall_height(i1 - i0 + 1));
+                        if (K && planned(K)) {
+                            switch (K) {
+                            case 5: slots_pass_tall<5>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            case 6: slots_pass_tall<6>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            case 7: slots_pass_tall<7>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            case 8: slots_pass_tall<8>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            case 9: slots_pass_tall<9>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            default: slots_pass_tall<10>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                            }
+                            x += K - 1;
+                            continue;
+                        }
+                    }
+                }
                 if (x + 3 <= i1 && planned(4)) { slots_pass<4, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
                 if (x + 1 <= i1 && planned(2)) { slots_pass<2, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
             }

@@ -529,7 +529,8 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     if (x.qp > 0) a.prune = x.prune1;                // (without a ratio prune1 = cut1: today's launch)
     a.lane_rel = sw(Sw::LaneRel);
     a.lds_slots = score_lds_slots(C, L, slots1);
-    if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots)\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots);
+    a.score_tall = (a.lds_slots && sw(Sw::ScoreTall) != 0) ? 1 : 0;      // tall passes: the LDS form only
+    if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots), tall passes %s\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots, a.score_tall ? "on" : "off");
 #ifdef QE_HAVE_K_BANDED_LDS
     if (a.lds_slots) launch_groups(C, k_banded<false, true>, a, L.ngroups(), 8, (size_t)score_lds_bytes(a.lds_slots));
     else

@@ -96,6 +96,7 @@ struct BandedArgs {
                                   // that is not below the task's cutoff: the geometry's (clamped) cutoff, as every other launch
     int32_t lds_slots = 0;        // k_banded<false, true> only: the band slots every wave's slice of the LDS holds (score_lds_bytes(lds_slots)
                                   // per wave); the group workspace is not touched
+    int32_t score_tall = 0;       // k_banded<false, true> only: one pass of tall_height() slots at the head of every chunk (0: the 4 / 2 / 1 plan alone)
 };
 
 // Bounded edit distance, diagonal-word form (k_bounded_diag, qe_bounded.h): whole pairs (p0 = t0 = 0), T.cutoff = the pair's
@@ -359,6 +360,19 @@ QE_T_HD int pass_plan(int i, int K, int lo, int hi, int r, int nw, bool plain, b
     const int nl = a1 >= a0 ? a1 - a0 + 1 : 0;
     fallback = nl > 0 && (a0 != i || !plain || r + nl - 1 >= nw - 1);
     return nl;
+}
+// Tall passes of k_banded<false, true> ("Tall passes"): at the first step of a chunk whose walk is h slots
+// long the wave takes ONE pass of tall_height(h) slots from the top of the band -- a prefix, as masked passes need -- where
+// pass_plan at that height has no fallback; the 4 / 2 / 1 plan walks what is left, and the whole chunk where this says 0.
+// h = 5 .. 10: the walk itself.  A taller walk: the largest height whose remainder the old plan takes in whole passes
+// (0, 1, 2 or at least 4 slots; 3 would be a 2-slot and a single-slot pass).
+enum : int { QE_TALL_MIN = 5, QE_TALL_MAX = 10 };
+QE_T_HD int tall_height(int h) {
+    for (int K = QE_TALL_MAX; K >= QE_TALL_MIN; --K) {
+        const int rem = h - K;
+        if (rem >= 0 && rem != 3) return K;
+    }
+    return 0;
 }
 
 // Band state in LDS (k_banded<false, true>; DESIGN.md 4.1, "Band state in LDS"): the budget, one definition for the launch
