@@ -1125,27 +1125,21 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                     return !__any(bad);
                 };
                 if (i == first) { hinP = QE_ONES; hinM = 0; }
-                if constexpr (LDS) {
-                    // one pass at the height of the chunk's walk (tall_height; a taller walk: its head) where no lane needs
-                    // the general form or starts inside it; otherwise, and for what is left, the plan below
-                    if (x == i0 && A.score_tall) {
-                        const int K = __builtin_amdgcn_readfirstlane(tall_height(i1 - i0 + 1));
-                        if (K && planned(K)) {
-                            switch (K) {
-                            case 5: slots_pass_tall<5>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            case 6: slots_pass_tall<6>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            case 7: slots_pass_tall<7>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            case 8: slots_pass_tall<8>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            case 9: slots_pass_tall<9>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            default: slots_pass_tall<10>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                            }
-                            x += K - 1;
-                            continue;
-                        }
-                    }
+                // score_pass_height: in the LDS form one pass at the height of the chunk's walk (tall_height; a taller walk: its
+                // head) where no lane needs the general form or starts inside it; otherwise, and for what is left, 4 or 2 slots
+                const int K = __builtin_amdgcn_readfirstlane(score_pass_height(x, i0, i1, LDS && A.score_tall, planned));
+                switch (K) {
+                case 0: break;
+                case 2: slots_pass<2, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); break;
+                case 4: slots_pass<4, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); break;
+                case 5: if constexpr (LDS) slots_pass_tall<5>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 6: if constexpr (LDS) slots_pass_tall<6>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 7: if constexpr (LDS) slots_pass_tall<7>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 8: if constexpr (LDS) slots_pass_tall<8>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 9: if constexpr (LDS) slots_pass_tall<9>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                default: if constexpr (LDS) slots_pass_tall<10>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
                 }
-                if (x + 3 <= i1 && planned(4)) { slots_pass<4, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 3; continue; }
-                if (x + 1 <= i1 && planned(2)) { slots_pass<2, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); x += 1; continue; }
+                if (K) { x += K - 1; continue; }
             }
             if (FILL && QE_FILL_K > 1 && A.fill_multi && x + QE_FILL_K - 1 <= i1) {
                 // K slots in one skewed pass, every lane with the slots inside its own band, unless a lane needs the

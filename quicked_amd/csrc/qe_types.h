@@ -374,6 +374,17 @@ QE_T_HD int tall_height(int h) {
     }
     return 0;
 }
+// the height of the pass that starts at step x of a chunk walked i0 .. i1: the tall height at the first step where `tall`
+// and planned(K) holds, else 4, else 2 where that many steps are left and planned, else 0 (a single-slot pass)
+template <class Planned> QE_T_HD int score_pass_height(int x, int i0, int i1, bool tall, Planned&& planned) {
+    if (tall && x == i0) {
+        const int K = tall_height(i1 - i0 + 1);
+        if (K && planned(K)) return K;
+    }
+    if (x + 3 <= i1 && planned(4)) return 4;
+    if (x + 1 <= i1 && planned(2)) return 2;
+    return 0;
+}
 
 // Band state in LDS (k_banded<false, true>; DESIGN.md 4.1, "Band state in LDS"): the budget, one definition for the launch
 // and the kernel.  A wave's slice holds Pv[s + 1][64] u64 | Mv[s + 1][64] u64 (slot -1 included) for bands of up to s slots

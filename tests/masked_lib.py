@@ -9,9 +9,9 @@ import subprocess
 
 import narrow_fit_lib as FL
 import narrow_lib as NL
+import native_build
 from quicked_amd import datagen
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BW = 15
 
 
@@ -105,12 +105,7 @@ def write_launch(path, pairs, launch):
 
 
 def build_walk(out_dir, sanitize=False):
-    exe = os.path.join(out_dir, "pass_plan_cpu_san" if sanitize else "pass_plan_cpu")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror"] + flags +
-                   ["-I", os.path.join(ROOT, "tests", "native", "hip_stub"), "-I", os.path.join(ROOT, "quicked_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "pass_plan_cpu.cpp"), "-o", exe], check=True)
-    return exe
+    return native_build.build_walk("pass_plan_cpu", out_dir, sanitize)
 
 
 def walk(exe, path, lane_rel=1, masked=1):

@@ -2,13 +2,12 @@
 qe_types.h's narrow_fit_* restated in Python, the brute force they are checked against, and the model of a run -- groups of
 64 tasks in library order, one slot count per group, the oracle's pass at every task's fitted cutoff, the rule, the pass at
 C.  What the CPU tests and the GPU tests of the fit compare with.  Test infrastructure only."""
-import ctypes as C
 import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import narrow_lib as NL
 import oracle_lib as O
+from native_build import host_lib
 
 
 def rhat(q, cutoff):
@@ -157,17 +156,10 @@ def totals(res):
 
 def native_fit(tmp_dir):
     """qe_types.h's narrow_fit_* compiled for the host, as narrow_lib.native_rule compiles the rule"""
-    src = os.path.join(tmp_dir, "narrow_fit.cpp")
-    lib = os.path.join(tmp_dir, "libnarrow_fit.so")
-    with open(src, "w") as f:
-        f.write('#include <hip/hip_runtime.h>\n#include "qe_types.h"\n'
-                'extern "C" int nf_rhat(int q, int c) { return qe::narrow_rhat(q, c); }\n'
-                'extern "C" int nf_room(int m, int n, int c1, int c) { return qe::narrow_room(m, n, c1, c); }\n'
-                'extern "C" int nf_slots(int m, int n, int c, int r) { return qe::narrow_fit_slots(m, n, c, r); }\n'
-                'extern "C" int nf_cutoff(int m, int n, int c, int s) { return qe::narrow_fit_cutoff(m, n, c, s); }\n'
-                'extern "C" int nf_lane(int m, int n, int c, int q, int s) { return qe::narrow_fit_lane(m, n, c, q, s); }\n'
-                'extern "C" int nf_ratio(int m, int n, int c, int r) { return qe::narrow_ratio(m, n, c, r); }\n')
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(root, "tests", "native", "hip_stub"),
-                    "-I", os.path.join(root, "quicked_amd", "csrc"), src, "-o", lib], check=True)
-    return C.CDLL(lib)
+    return host_lib(tmp_dir, "narrow_fit",
+                    'extern "C" int nf_rhat(int q, int c) { return qe::narrow_rhat(q, c); }\n'
+                    'extern "C" int nf_room(int m, int n, int c1, int c) { return qe::narrow_room(m, n, c1, c); }\n'
+                    'extern "C" int nf_slots(int m, int n, int c, int r) { return qe::narrow_fit_slots(m, n, c, r); }\n'
+                    'extern "C" int nf_cutoff(int m, int n, int c, int s) { return qe::narrow_fit_cutoff(m, n, c, s); }\n'
+                    'extern "C" int nf_lane(int m, int n, int c, int q, int s) { return qe::narrow_fit_lane(m, n, c, q, s); }\n'
+                    'extern "C" int nf_ratio(int m, int n, int c, int r) { return qe::narrow_ratio(m, n, c, r); }\n')

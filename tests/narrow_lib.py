@@ -7,6 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 import oracle_lib as O
+from native_build import host_lib
 from quicked_amd import datagen
 
 
@@ -97,19 +98,11 @@ def probe_expectation(pairs, res):
 
 def native_rule(tmp_dir):
     """qe_types.h's narrow_cutoff / narrow_cover / narrow_accepts compiled for the host (the header is plain C++ there)"""
-    import subprocess
-    src = os.path.join(tmp_dir, "narrow_rule.cpp")
-    lib = os.path.join(tmp_dir, "libnarrow_rule.so")
-    with open(src, "w") as f:
-        f.write('#include <hip/hip_runtime.h>\n#include "qe_types.h"\n'
-                'extern "C" int nr_cutoff(int m, int n, int c) { return qe::narrow_cutoff(m, n, c); }\n'
-                'extern "C" int nr_cover(int m, int n, int c) { return qe::narrow_cover(m, n, c); }\n'
-                'extern "C" int nr_slots(int m, int n, int c) { return qe::narrow_slots(m, n, c); }\n'
-                'extern "C" int nr_accepts(int m, int n, int c1, int c, int r) { return qe::narrow_accepts(m, n, c1, c, r) ? 1 : 0; }\n')
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(root, "tests", "native", "hip_stub"),
-                    "-I", os.path.join(root, "quicked_amd", "csrc"), src, "-o", lib], check=True)
-    return C.CDLL(lib)
+    return host_lib(tmp_dir, "narrow_rule",
+                    'extern "C" int nr_cutoff(int m, int n, int c) { return qe::narrow_cutoff(m, n, c); }\n'
+                    'extern "C" int nr_cover(int m, int n, int c) { return qe::narrow_cover(m, n, c); }\n'
+                    'extern "C" int nr_slots(int m, int n, int c) { return qe::narrow_slots(m, n, c); }\n'
+                    'extern "C" int nr_accepts(int m, int n, int c1, int c, int r) { return qe::narrow_accepts(m, n, c1, c, r) ? 1 : 0; }\n')
 
 
 # The grid of shapes the property is checked on (committed: the lists below ARE the cases).

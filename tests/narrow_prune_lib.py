@@ -10,8 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import narrow_fit_lib as FL
 import narrow_lib as NL
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import native_build
 
 
 def prune_of(m, n, cutoff, c1, qp):
@@ -43,12 +42,7 @@ def write_launch(path, pairs, launch):
 
 
 def build_walk(out_dir, sanitize=False):
-    exe = os.path.join(out_dir, "narrow_prune_cpu_san" if sanitize else "narrow_prune_cpu")
-    flags = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags +
-                   ["-I", os.path.join(ROOT, "tests", "native", "hip_stub"), "-I", os.path.join(ROOT, "quicked_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "narrow_prune_cpu.cpp"), "-o", exe], check=True)
-    return exe
+    return native_build.build_walk("narrow_prune_cpu", out_dir, sanitize)
 
 
 def walk(exe, path, lane_rel=1, masked=1):
@@ -118,13 +112,6 @@ def prune_model(pairs, q, qp, exe, tmp_dir, bandwidth=15, cutoffs=None, memo=Non
 
 def native_rule(tmp_dir):
     """qe_types.h's narrow_prune / narrow_accepts_pruned compiled for the host"""
-    import ctypes as C
-    src = os.path.join(tmp_dir, "narrow_prune_rule.cpp")
-    lib = os.path.join(tmp_dir, "libnarrow_prune_rule.so")
-    with open(src, "w") as f:
-        f.write('#include <hip/hip_runtime.h>\n#include "qe_types.h"\n'
-                'extern "C" int np_prune(int m, int n, int c, int c1, int qp) { return qe::narrow_prune(m, n, c, c1, qp); }\n'
-                'extern "C" int np_accepts(int m, int n, int c1, int c, int p, int r) { return qe::narrow_accepts_pruned(m, n, c1, c, p, r) ? 1 : 0; }\n')
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "tests", "native", "hip_stub"),
-                    "-I", os.path.join(ROOT, "quicked_amd", "csrc"), src, "-o", lib], check=True)
-    return C.CDLL(lib)
+    return native_build.host_lib(tmp_dir, "narrow_prune_rule",
+                                 'extern "C" int np_prune(int m, int n, int c, int c1, int qp) { return qe::narrow_prune(m, n, c, c1, qp); }\n'
+                                 'extern "C" int np_accepts(int m, int n, int c1, int c, int p, int r) { return qe::narrow_accepts_pruned(m, n, c1, c, p, r) ? 1 : 0; }\n')

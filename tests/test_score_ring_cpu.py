@@ -14,20 +14,15 @@ import masked_lib as ML
 import narrow_fit_lib as FL
 import narrow_lib as NL
 import narrow_prune_lib as PL
+import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QS = (90, 200, 340, 520)            # the ratios of tests/test_narrow_fit_cpu.py
 MASKED_CASES = ("interleaved", "indels", "ragged_symbols", "last_row", "fit_interleaved")
 CAP, RING = 13, 16
 
 
 def build_walk(out_dir, sanitize=False):
-    exe = os.path.join(out_dir, "score_ring_cpu_san" if sanitize else "score_ring_cpu")
-    flags = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags +
-                   ["-I", os.path.join(ROOT, "tests", "native", "hip_stub"), "-I", os.path.join(ROOT, "quicked_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "score_ring_cpu.cpp"), "-o", exe], check=True)
-    return exe
+    return native_build.build_walk("score_ring_cpu", out_dir, sanitize)
 
 
 def walk(exe, path, lane_rel=1, masked=1):
@@ -82,17 +77,10 @@ def _check(counts, rows, code, out, launch, pairs):
 
 
 def test_the_budget_is_one_definition(tmp_path):
-    import ctypes as C
-    src = os.path.join(str(tmp_path), "budget.cpp")
-    lib = os.path.join(str(tmp_path), "libbudget.so")
-    with open(src, "w") as f:
-        f.write('#include <hip/hip_runtime.h>\n#include "qe_types.h"\n'
-                'extern "C" int b_cap() { return qe::score_lds_cap(); }\nextern "C" int b_ring() { return qe::score_lds_ring(); }\n'
-                'extern "C" int b_fits(int s) { return qe::score_lds_fits(s) ? 1 : 0; }\nextern "C" int b_row(int r) { return qe::score_lds_row(r); }\n'
-                'extern "C" int b_bytes(int s) { return qe::score_lds_bytes(s); }\n')
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "tests", "native", "hip_stub"),
-                    "-I", os.path.join(ROOT, "quicked_amd", "csrc"), src, "-o", lib], check=True)
-    L = C.CDLL(lib)
+    L = native_build.host_lib(str(tmp_path), "budget",
+                              'extern "C" int b_cap() { return qe::score_lds_cap(); }\nextern "C" int b_ring() { return qe::score_lds_ring(); }\n'
+                              'extern "C" int b_fits(int s) { return qe::score_lds_fits(s) ? 1 : 0; }\nextern "C" int b_row(int r) { return qe::score_lds_row(r); }\n'
+                              'extern "C" int b_bytes(int s) { return qe::score_lds_bytes(s); }\n')
     assert (L.b_cap(), L.b_ring()) == (CAP, RING) and RING & (RING - 1) == 0
     assert CAP + 1 <= RING - 2                                   # a chunk's window of slots + 1 rows is shorter than the ring by two
     assert [s for s in range(0, 40) if L.b_fits(s)] == list(range(1, CAP + 1))

@@ -16,8 +16,8 @@ import masked_lib as ML
 import narrow_fit_lib as FL
 import narrow_lib as NL
 import narrow_prune_lib as PL
+import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QS = (90, 200, 340, 520)            # the ratios of tests/test_narrow_fit_cpu.py
 MASKED_CASES = ("interleaved", "indels", "ragged_symbols", "last_row", "fit_interleaved")
 HEIGHTS = tuple(range(5, 11))       # qe_types.h: QE_TALL_MIN .. QE_TALL_MAX
@@ -25,12 +25,7 @@ CAP = 13
 
 
 def build_walk(out_dir, sanitize=False):
-    exe = os.path.join(out_dir, "tall_plan_cpu_san" if sanitize else "tall_plan_cpu")
-    flags = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags +
-                   ["-I", os.path.join(ROOT, "tests", "native", "hip_stub"), "-I", os.path.join(ROOT, "quicked_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "tall_plan_cpu.cpp"), "-o", exe], check=True)
-    return exe
+    return native_build.build_walk("tall_plan_cpu", out_dir, sanitize)
 
 
 def walk(exe, path, lane_rel=1, masked=1):
@@ -100,15 +95,9 @@ def _check(counts, rows, code, out, launch, pairs):
 def test_the_height_rule(tmp_path):
     """qe_types.h: tall_height compiled for the host: the walk itself at 5 .. 10 slots, the largest height whose remainder is
     0, 1, 2 or at least 4 slots above that, nothing below 5"""
-    import ctypes as C
-    src = os.path.join(str(tmp_path), "height.cpp")
-    lib = os.path.join(str(tmp_path), "libheight.so")
-    with open(src, "w") as f:
-        f.write('#include <hip/hip_runtime.h>\n#include "qe_types.h"\nextern "C" int t_height(int h) { return qe::tall_height(h); }\n'
-                'extern "C" int t_min() { return qe::QE_TALL_MIN; }\nextern "C" int t_max() { return qe::QE_TALL_MAX; }\n')
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "tests", "native", "hip_stub"),
-                    "-I", os.path.join(ROOT, "quicked_amd", "csrc"), src, "-o", lib], check=True)
-    L = C.CDLL(lib)
+    L = native_build.host_lib(str(tmp_path), "height",
+                              'extern "C" int t_height(int h) { return qe::tall_height(h); }\n'
+                              'extern "C" int t_min() { return qe::QE_TALL_MIN; }\nextern "C" int t_max() { return qe::QE_TALL_MAX; }\n')
     assert (L.t_min(), L.t_max()) == (HEIGHTS[0], HEIGHTS[-1])
     assert [L.t_height(h) for h in range(-3, 5)] == [0] * 8
     assert [L.t_height(h) for h in HEIGHTS] == list(HEIGHTS)
