@@ -151,8 +151,28 @@ quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const int32_t
  * keeps the whole state of a pattern of up to 256 bases in registers; QE_SEARCH_FORM=0 the workspace form always, 1 the
  * register form wherever it applies.
  * quicked_batch_locations: text_start / text_end (n values each, either may be NULL) of the last sync != 0 search run or of
- * the fetch of a queued one; QUICKED_ERROR after any run that was not a search run, as the tag getters. */
+ * the fetch of a queued one; QUICKED_ERROR after any run that was not a search run, as the tag getters.
+ *
+ * IUPAC degenerate bases (primers and adapters written with R, Y, N ...): one of the two flags below, OR-ed into `mode` of
+ * quicked_batch_run_search or quicked_batch_run_search_all, replaces the equality.  Every byte then stands for a set of bases,
+ * case folded -- A, C, G, T (U = T); R = AG, Y = CT, S = CG, W = AT, K = GT, M = AC; B = CGT, D = AGT, H = ACT, V = ACG;
+ * N = ACGT; any other byte the empty set -- and two symbols are equal when their sets intersect.  The relation is symmetric
+ * and not transitive (R = A, R = G, A != G); a byte outside the alphabet equals nothing, itself included.
+ *   QUICKED_SEARCH_IUPAC          both sequences are read through the table: a text N matches every pattern symbol
+ *   QUICKED_SEARCH_IUPAC_PATTERN  the pattern only: a text byte that is not one of A C G T U (either case) has the empty
+ *                                 set, so a poly-N read does not match every adapter
+ * On input of upper- or lower-case ACGT only both give exactly the results of the unflagged run.  Everything else -- D, the
+ * modes, the results and their tie rules, the bounds, "beyond", empty sequences, the occurrence definition, max_hits, found /
+ * stored, queued only_score != 0 runs and their fetch, counters [0], kernel_times slot [0], QE_SEARCH_FORM -- is that of the
+ * unflagged run described above and below.  The base mode (mode & 15) must be PREFIX or INFIX, at most one of the two flags
+ * may be set and no other bit: anything else is QUICKED_ERROR, nothing is launched.  A flagged quicked_batch_run_search with
+ * only_score == 0 returns QUICKED_UNIMPLEMENTED and queues nothing (the traceback and the formatter compare raw bytes: a
+ * CIGAR's edit count would not be d).  Packed batches: QUICKED_WIRE_2BIT holds ACGT only; the fifth symbol of
+ * QUICKED_WIRE_PLANES3 is N -- the full set under QUICKED_SEARCH_IUPAC, under QUICKED_SEARCH_IUPAC_PATTERN the full set in
+ * patterns and the empty set in texts -- so a packed batch and the ASCII batch of the same sequences over ACGTN agree.
+ * A flagged run packs four base-membership planes of the batch into its own pool first. */
 typedef enum { QUICKED_SEARCH_PREFIX = 1, QUICKED_SEARCH_INFIX = 2 } quicked_search_mode_t;
+enum { QUICKED_SEARCH_IUPAC = 16, QUICKED_SEARCH_IUPAC_PATTERN = 32 };
 quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mode,
                                           const int32_t* max_dist, int32_t max_dist_all,
                                           int only_score, int sync);

@@ -66,6 +66,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
 HIT_DTYPE = np.dtype([("text_start", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_hit_t
 SEARCH_PREFIX, SEARCH_INFIX = 1, 2
+SEARCH_IUPAC, SEARCH_IUPAC_PATTERN = 16, 32      # OR-ed into a search mode: IUPAC base sets on both sides / on the pattern only
 
 _LIB = None
 
@@ -359,7 +360,9 @@ class ResidentBatch:
     def run_search(self, mode, max_dist=None, only_score=True, sync=True):
         """quicked_batch_run_search: where the pattern fits the text best (SEARCH_PREFIX: from the text's start, SEARCH_INFIX:
         anywhere) and at what cost.  max_dist: None = no bound, one int for every pair, or an array of n bounds.
-        only_score=False (sync only): a CIGAR of the pattern against text[start:end] for every pair within its bound."""
+        only_score=False (sync only): a CIGAR of the pattern against text[start:end] for every pair within its bound.
+        mode | SEARCH_IUPAC reads both sequences as IUPAC base sets (equal when the sets intersect), mode | SEARCH_IUPAC_PATTERN
+        the pattern only; such runs are score-and-location runs (only_score=False: QUICKED_UNIMPLEMENTED)."""
         if max_dist is None:
             max_dist = 2**31 - 1
         if np.ndim(max_dist) == 0:
@@ -371,7 +374,8 @@ class ResidentBatch:
 
     def run_search_all(self, mode, max_dist=None, max_hits=16, sync=True):
         """quicked_batch_run_search_all: every occurrence of the pattern within the bound (the first columns of the valleys of
-        row m), at most max_hits (1 .. 4096) stored per pair.  max_dist as in run_search.  Sync runs only."""
+        row m), at most max_hits (1 .. 4096) stored per pair.  max_dist as in run_search.  Sync runs only.
+        mode | SEARCH_IUPAC or mode | SEARCH_IUPAC_PATTERN: under the IUPAC base-set equality, as in run_search."""
         if max_dist is None:
             max_dist = 2**31 - 1
         if np.ndim(max_dist) == 0:

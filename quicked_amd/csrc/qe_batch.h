@@ -200,7 +200,9 @@ inline bool trace_on() { return sw_set(Sw::Trace); }
 struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 // sr != nullptr: a search run (quicked_batch_run_search) in `mode` (QUICKED_SEARCH_*), bounds as in a bounded run; p as there
 // max_hits > 0: every occurrence within the bound (quicked_batch_run_search_all), at most max_hits stored per pair; fetch only
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; };
+// eq: the run's equality -- 0 the library's, 1 QUICKED_SEARCH_IUPAC (both sequences as base sets), 2 QUICKED_SEARCH_IUPAC_PATTERN
+// (the pattern as base sets, a text byte that is not A C G T U the empty set); mode is the base mode, without the flags
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; };
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr, const SearchRun* sr = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);

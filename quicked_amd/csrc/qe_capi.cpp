@@ -215,16 +215,26 @@ QE_API quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const 
     }, &arg);
 }
 
+// The mode of a search run: the base mode (mode & 15: PREFIX or INFIX) with at most one of the two equality flags and no other
+// bit.  -> the run's equality (SearchRun::eq: 0, 1 QUICKED_SEARCH_IUPAC, 2 QUICKED_SEARCH_IUPAC_PATTERN), -1: not a mode
+static int search_mode_eq(int mode) {
+    const int base = mode & 15, fl = mode & ~15;
+    if (base != QUICKED_SEARCH_PREFIX && base != QUICKED_SEARCH_INFIX) return -1;
+    return fl == 0 ? 0 : (fl == QUICKED_SEARCH_IUPAC ? 1 : (fl == QUICKED_SEARCH_IUPAC_PATTERN ? 2 : -1));
+}
+
 // Pattern search: the arguments are checked before anything touches the device
 QE_API quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mode, const int32_t* max_dist, int32_t max_dist_all,
                                                  int only_score, int sync) {
-    if (!batch || (mode != QUICKED_SEARCH_PREFIX && mode != QUICKED_SEARCH_INFIX) || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
-    struct Arg { SearchRun sr; int only_score, sync; } arg{{mode, max_dist, max_dist_all}, only_score, sync};
+    const int eq = search_mode_eq(mode);
+    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    struct Arg { SearchRun sr; int only_score, sync; } arg{{mode & 15, max_dist, max_dist_all, 0, eq}, only_score, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         if (x->sr.max_dist) for (int64_t i = 0; i < B->n; ++i) if (x->sr.max_dist[i] < 0) return QUICKED_ERROR;
         if (B->check) return QUICKED_UNIMPLEMENTED;                         // the in-run validator walks the text from its origin
         if (!x->only_score && !x->sync) return QUICKED_UNIMPLEMENTED;      // CIGARs need the locations on the host first
+        if (!x->only_score && x->sr.eq) return QUICKED_UNIMPLEMENTED;      // the traceback compares raw bytes: its edit count would not be d
         quicked_params_t p = quicked_default_params();
         p.algo = BANDED;
         p.only_score = x->only_score != 0;
@@ -243,9 +253,10 @@ QE_API quicked_status_t quicked_batch_locations(quicked_batch_t* batch, int32_t*
 static_assert(sizeof(quicked_hit_t) == 12, "quicked_hit_t is three int32 (k_hits_expand writes it as such)");
 QE_API quicked_status_t quicked_batch_run_search_all(quicked_batch_t* batch, int mode, const int32_t* max_dist, int32_t max_dist_all,
                                                      int32_t max_hits, int sync) {
-    if (!batch || (mode != QUICKED_SEARCH_PREFIX && mode != QUICKED_SEARCH_INFIX) || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    const int eq = search_mode_eq(mode);
+    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
     if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
-    struct Arg { SearchRun sr; int sync; } arg{{mode, max_dist, max_dist_all, max_hits}, sync};
+    struct Arg { SearchRun sr; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq}, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         int64_t tasks = 0;

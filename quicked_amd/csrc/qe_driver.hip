@@ -706,6 +706,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     for (const auto& q : C.pool_a2) pools_held += q.cap;
     size_t need_mat = B.last_mat_bytes, need_fixed = B.last_fixed_bytes;
     int need_groups = B.last_groups;
+    if (sr) need_fixed += search_iupac_bytes(B, sr->eq, sr->mode);      // a flagged search run packs its four planes into its pool
     if (need_groups == 0 && !p.only_score && p.algo != WINDOWED) {
         // first CIGAR run of this batch: leaves as wide as the bandwidth cutoff allows (QuickEd's bounds are tighter)
         for (int64_t i = 0; i < B.n; ++i) {
@@ -868,7 +869,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // All-occurrences run (sync only): found / smallest score / offsets per pair and the stored occurrences, already in the
         // order of the pairs, in one read-back
         enter_a();
-        const SearchHitsOut HO = run_search_hits(B, C, SLs, sr->mode, sr->max_hits);
+        const SearchHitsOut HO = run_search_hits(B, C, SLs, sr->mode, sr->max_hits, sr->eq);
         const size_t n = (size_t)B.n, nh = (size_t)HO.total;
         std::vector<int32_t> best; std::vector<u32> adv, adv2;
         B.wr->hits.resize(nh);
@@ -890,7 +891,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // so the run buffers are tight (the path bounded CIGAR runs take).  Pairs with lower-case / IUPAC bytes are scored and
         // located like the others but get no alignment: the traceback compares raw bytes, its edit count would not be d
         enter_a();
-        const SearchOut SO = run_search(B, C, SLs, sr->mode);
+        const SearchOut SO = run_search(B, C, SLs, sr->mode, sr->eq);
         B.d_score = SO.d_score;
         if (pf) {
             pf->kind = 1; pf->task_pair = SO.task_pair; pf->d_score = SO.d_score; pf->d_adv = SO.d_adv; pf->counter_slot = 0;

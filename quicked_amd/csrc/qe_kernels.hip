@@ -958,6 +958,94 @@ __global__ __launch_bounds__(256) void k_reverse_planes(RevArgs A) {
     }
 }
 
+// ===========================================================================
+// The four membership planes of a flagged search run (qe_iupac.h).  k_pack_iupac: resident ASCII -> planes,
+// laid out as k_pack -- one wave per sequence, a lane takes 16 consecutive bases with one 16-byte load, four neighbouring
+// lanes make one 64-base row -- with every byte classified through the 32-entry nibble table of iupac_mask (two 64-bit
+// constants).  The filler past a sequence's end is byte 0: the empty set, zero planes.
+// ===========================================================================
+#define QE_HAVE_K_SEARCH_IUPAC 1
+__global__ __launch_bounds__(256) void k_pack_iupac(IupacPackArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seq >= A.nseq) return;
+    const int len = A.len[seq];
+    const uint8_t* __restrict__ src = A.asc + A.asc_off[seq];
+    u64* __restrict__ dst = A.planes + iupac_offset(A.pl_off[seq]);
+    const int nrows = ((len + 63) >> 6) + 2;
+    const int nspan = (nrows + 15) >> 4;
+    const bool acgt_only = A.acgt_only != 0;
+    constexpr int UNR = 4;                                    // 16-byte loads in flight per lane
+    for (int s0 = 0; s0 < nspan; s0 += UNR) {
+        uint4 raw[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int pos = (s0 + u) * 1024 + 16 * lane;
+            uint4 x = make_uint4(0u, 0u, 0u, 0u);
+            if (pos + 16 <= len) {
+                if (A.reverse) {
+                    uint4 y; __builtin_memcpy(&y, src + (len - 16 - pos), 16);
+                    x = make_uint4(__builtin_bswap32(y.w), __builtin_bswap32(y.z), __builtin_bswap32(y.y), __builtin_bswap32(y.x));
+                } else {
+                    __builtin_memcpy(&x, src + pos, 16);
+                }
+            } else if (pos < len) {                           // the one ragged lane of a sequence
+                u64 lo = 0, hi = 0;
+                for (int i = 0; i < len - pos; ++i) {
+                    const u64 c = A.reverse ? src[len - 1 - pos - i] : src[pos + i];
+                    if (i < 8) lo |= c << (8 * i); else hi |= c << (8 * (i - 8));
+                }
+                x = make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
+            }
+            raw[u] = x;
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int span = s0 + u;
+            if (span >= nspan) break;
+            const u32 wv[4] = {raw[u].x, raw[u].y, raw[u].z, raw[u].w};
+            u32 ac = 0, gt = 0;                               // this lane's 16 bases: A | C << 16, G | T << 16
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const u32 mk = iupac_mask((wv[k] >> (8 * i)) & 0xFFu, acgt_only);
+                    ac |= ((mk & 1u) | ((mk & 2u) << 15)) << (4 * k + i);
+                    gt |= (((mk >> 2) & 1u) | ((mk & 8u) << 13)) << (4 * k + i);
+                }
+            }
+            // 16-bit masks of this lane's 16 bases -> 64-bit row words on every fourth lane
+            const u32 ac1 = __shfl_down(ac, 1), gt1 = __shfl_down(gt, 1);
+            const u32 a32 = (ac & 0xFFFFu) | (ac1 << 16), c32 = (ac >> 16) | (ac1 & 0xFFFF0000u);
+            const u32 g32 = (gt & 0xFFFFu) | (gt1 << 16), t32 = (gt >> 16) | (gt1 & 0xFFFF0000u);
+            const u32 a32h = __shfl_down(a32, 2), c32h = __shfl_down(c32, 2), g32h = __shfl_down(g32, 2), t32h = __shfl_down(t32, 2);
+            const int row = span * 16 + (lane >> 2);
+            if ((lane & 3) == 0 && row < nrows) {
+                u64* q = dst + 4 * (int64_t)row;
+                q[0] = mk64(a32, a32h); q[1] = mk64(c32, c32h); q[2] = mk64(g32, g32h); q[3] = mk64(t32, t32h);
+            }
+        }
+    }
+}
+
+// ... and from the three planes of a packed batch, forward or reversed (the wire format's not-ACGT symbol is N): a lane per
+// 64-base row, masked to the sequence's length; the two padding rows are written as zeros
+__global__ __launch_bounds__(256) void k_planes_iupac(IupacPlanesArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seq >= A.nseq) return;
+    const int len = A.len[seq];
+    const int nw = (len + 63) >> 6;
+    const u64* __restrict__ src = A.src + A.pl_off[seq];
+    u64* __restrict__ dst = A.dst + iupac_offset(A.pl_off[seq]);
+    for (int r = lane; r < nw + 2; r += 64) {
+        u64 o[4] = {0, 0, 0, 0};
+        if (r < nw) iupac_row_from_planes3(src[3 * (int64_t)r], src[3 * (int64_t)r + 1], src[3 * (int64_t)r + 2], min(len - 64 * r, 64), A.n_empty != 0, o);
+        u64* q = dst + 4 * (int64_t)r;
+        q[0] = o[0]; q[1] = o[1]; q[2] = o[2]; q[3] = o[3];
+    }
+}
+
 // ---------------------------------------------------------------------------
 // band geometry (bpm_banded.c:121-135)
 // ---------------------------------------------------------------------------
@@ -1348,8 +1436,10 @@ __global__ __launch_bounds__(256) void k_bounded_threshold(int nt, const int32_t
 // every lane has its answer (an exact occurrence: nothing later can be better).
 // The start pass of an INFIX run is the PREFIX form over the reversed planes (SearchArgs::in_score).
 // ===========================================================================
+// Eq: the equality (qe_search.h) -- SearchEq3 over the batch's three planes, or SearchEqIupac over the four membership planes
+// a flagged run packs (A.P.pl_p / pl_t then point at those; the offsets stay the three-plane ones, Eq::offset maps them).
 #define QE_HAVE_K_SEARCH 1
-template <int NB>
+template <int NB, class Eq = SearchEq3>
 __global__ __launch_bounds__(256) void k_search(SearchArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
     if (g * 64 >= A.T.ntasks) return;
@@ -1372,12 +1462,16 @@ __global__ __launch_bounds__(256) void k_search(SearchArgs A) {
     if (!__any(valid)) return;
     SearchLane L;
     search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, A.flags);
-    if (valid) { pp = A.P.pl_p + A.P.pl_p_off[pair]; tp = A.P.pl_t + A.P.pl_t_off[pair]; }
-    SearchRegStore<(NB > 0 ? NB : 1)> R;
-    SearchWsStore W;
+    if (valid) { pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]); tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]); }
+    SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
+    SearchWsStoreOf<Eq> W;
     if constexpr (NB > 0) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = R.pa[b] = R.pb[b] = R.pn[b] = 0; R.s[b] = 0; }
+        for (int b = 0; b < NB; ++b) {
+            R.pv[b] = R.mv[b] = 0; R.s[b] = 0;
+#pragma unroll
+            for (int k = 0; k < Eq::W; ++k) R.pl[b][k] = 0;
+        }
         if (valid) { R.load(pp, m); search_store_init<NB>(R, L); }
     } else {
         uint8_t* base = A.ws + A.g_ws_off[g];
@@ -1393,10 +1487,10 @@ __global__ __launch_bounds__(256) void k_search(SearchArgs A) {
         if (!__any(live)) break;
         if (live) {
             const int col0 = 64 * c, ncols = min(64, n - col0);
-            u64 T0, T1, TN;
-            search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
-            if constexpr (NB > 0) search_chunk<NB>(R, L, T0, T1, TN, col0, ncols);
-            else search_chunk<0>(W, L, T0, T1, TN, col0, ncols);
+            u64 tw[Eq::W];
+            Eq::text_chunk(tp, tbit + col0, ncols, tw);
+            if constexpr (NB > 0) search_chunk<NB>(R, L, tw, col0, ncols);
+            else search_chunk<0>(W, L, tw, col0, ncols);
         }
     }
     if (pair >= 0) {
@@ -1416,13 +1510,17 @@ template __global__ void k_search<0>(SearchArgs);
 template __global__ void k_search<1>(SearchArgs);
 template __global__ void k_search<2>(SearchArgs);
 template __global__ void k_search<4>(SearchArgs);
+template __global__ void k_search<0, SearchEqIupac>(SearchArgs);
+template __global__ void k_search<1, SearchEqIupac>(SearchArgs);
+template __global__ void k_search<2, SearchEqIupac>(SearchArgs);
+template __global__ void k_search<4, SearchEqIupac>(SearchArgs);
 
 // Every occurrence within the bound (quicked_batch_run_search_all): the forward pass above with SearchHitScan in the place of
 // the end-position scan -- the same stores, the same group layout, the bound kept for the whole text, no early exit.  A lane
 // emits an occurrence when row m rises out of a valley (rarely more than a few per text): one 8-byte store into its own
 // stretch of `raw`, never past max_hits entries (SearchHitSink::cap); a lane without a valid task has cap 0 and a null sink.
 #define QE_HAVE_K_SEARCH_HITS 1
-template <int NB>
+template <int NB, class Eq = SearchEq3>
 __global__ __launch_bounds__(256) void k_search_hits(SearchHitsArgs X) {
     const SearchArgs& A = X.S;
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
@@ -1440,12 +1538,16 @@ __global__ __launch_bounds__(256) void k_search_hits(SearchHitsArgs X) {
     search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, 0);
     SearchHitScan H;
     H.init(L, valid ? reinterpret_cast<SearchHit*>(X.raw) + (int64_t)t * X.max_hits : nullptr, 1, valid ? X.max_hits : 0);
-    if (valid) { pp = A.P.pl_p + A.P.pl_p_off[pair]; tp = A.P.pl_t + A.P.pl_t_off[pair]; }
-    SearchRegStore<(NB > 0 ? NB : 1)> R;
-    SearchWsStore W;
+    if (valid) { pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]); tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]); }
+    SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
+    SearchWsStoreOf<Eq> W;
     if constexpr (NB > 0) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = R.pa[b] = R.pb[b] = R.pn[b] = 0; R.s[b] = 0; }
+        for (int b = 0; b < NB; ++b) {
+            R.pv[b] = R.mv[b] = 0; R.s[b] = 0;
+#pragma unroll
+            for (int k = 0; k < Eq::W; ++k) R.pl[b][k] = 0;
+        }
         if (valid) { R.load(pp, m); search_store_init<NB>(R, L); }
     } else {
         uint8_t* base = A.ws + A.g_ws_off[g];
@@ -1459,10 +1561,10 @@ __global__ __launch_bounds__(256) void k_search_hits(SearchHitsArgs X) {
     for (int c = 0; c < wave_chunks; ++c) {
         if (c < my_chunks) {
             const int col0 = 64 * c, ncols = min(64, n - col0);
-            u64 T0, T1, TN;
-            search_text_chunk(tp, col0, ncols, T0, T1, TN);
-            if constexpr (NB > 0) search_chunk<NB>(R, L, T0, T1, TN, col0, ncols, H);
-            else search_chunk<0>(W, L, T0, T1, TN, col0, ncols, H);
+            u64 tw[Eq::W];
+            Eq::text_chunk(tp, col0, ncols, tw);
+            if constexpr (NB > 0) search_chunk<NB>(R, L, tw, col0, ncols, H);
+            else search_chunk<0>(W, L, tw, col0, ncols, H);
         }
     }
     if (valid) {
@@ -1475,6 +1577,10 @@ template __global__ void k_search_hits<0>(SearchHitsArgs);
 template __global__ void k_search_hits<1>(SearchHitsArgs);
 template __global__ void k_search_hits<2>(SearchHitsArgs);
 template __global__ void k_search_hits<4>(SearchHitsArgs);
+template __global__ void k_search_hits<0, SearchEqIupac>(SearchHitsArgs);
+template __global__ void k_search_hits<1, SearchEqIupac>(SearchHitsArgs);
+template __global__ void k_search_hits<2, SearchEqIupac>(SearchHitsArgs);
+template __global__ void k_search_hits<4, SearchEqIupac>(SearchHitsArgs);
 
 // one thread per task of a forward list: its stored occurrences to their places in the run's occurrence list (HitExpandArgs)
 __global__ __launch_bounds__(256) void k_hits_expand(HitExpandArgs A) {

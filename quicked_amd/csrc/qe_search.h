@@ -44,10 +44,20 @@
 // The set depends on min(R[e], k + 1) only -- a value above k is no occurrence, ends a plateau as a rise whatever it is, and
 // is a column every value <= k lies below -- and the sweep's values are exact wherever the true value is <= k and above k
 // wherever it is not (the rule's first two points), so the scan walks w = min(computed value, k + 1).
+//
+// The equality is a parameter.  Everything above argues from path costs only -- what a cell costs given the cells it is
+// reached from -- and never from what makes two symbols equal: the recurrence takes any Eq word, and the live-block rule,
+// the two scans, the start pass over the reversed sequences (a path read backwards has the cost it has forwards: the relation
+// is applied to the same two symbols) and the m + score window hold for any match relation between a pattern symbol and a
+// text symbol, symmetric or not, transitive or not.  So the equality is a small policy type that the stores carry (Store::Eq):
+// how many plane words a block and a chunk have (W), where a sequence's words start, how they are loaded, and how Eq is formed
+// for column c.  SearchEq3 is the library's equality above over the three planes of qe_types.h and the default everywhere;
+// SearchEqIupac is the set-intersection equality over the four membership planes of qe_iupac.h.
 #pragma once
 #include <stdint.h>
 
 #include "qe_bounded.h"
+#include "qe_iupac.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define QE_S_HD __host__ __device__ __forceinline__
@@ -83,29 +93,63 @@ QE_S_HD int search_first_live(int k, int m, int flags) {
     return search_want(L, nb);
 }
 
-// 64 text columns starting at bit offset `bit` of a text's planes; words past the one that holds the chunk's last column
-// (bit + ncols - 1) are not read
-QE_S_HD void search_text_chunk(const uint64_t* tp, int64_t bit, int ncols, uint64_t& t0, uint64_t& t1, uint64_t& tn) {
+// 64 text columns starting at bit offset `bit` of a text's planes, W words per 64 bases; words past the one that holds the
+// chunk's last column (bit + ncols - 1) are not read
+template <int W>
+QE_S_HD void search_text_words(const uint64_t* tp, int64_t bit, int ncols, uint64_t (&t)[W]) {
     const int64_t w = bit >> 6;
     const int sh = (int)(bit & 63);
-    const uint64_t* q = tp + 3 * w;
-    t0 = q[0] >> sh; t1 = q[1] >> sh; tn = q[2] >> sh;
-    if (sh && ((bit + ncols - 1) >> 6) > w) { t0 |= q[3] << (64 - sh); t1 |= q[4] << (64 - sh); tn |= q[5] << (64 - sh); }
+    const uint64_t* q = tp + W * w;
+    for (int k = 0; k < W; ++k) t[k] = q[k] >> sh;
+    if (sh && ((bit + ncols - 1) >> 6) > w) for (int k = 0; k < W; ++k) t[k] |= q[W + k] << (64 - sh);
 }
 
-// One block over one chunk: Pv / Mv the block's vertical deltas, (a, b, nn) its pattern planes, (T0, T1, TN) the chunk's text
-// planes, hinP / hinM the horizontal deltas of the row above.  Leaves in oP / oM the raw horizontal deltas of the block's
+// The library's equality over three planes {code bit 0, code bit 1, not-ACGT}: both not-ACGT, or neither and the codes agree
+struct SearchEq3 {
+    enum : int { W = 3 };
+    static QE_S_HD int64_t offset(int64_t off3) { return off3; }                  // of a sequence, from its three-plane word offset
+    static QE_S_HD void pattern_rows(const uint64_t* pp, int m, int b, uint64_t (&p)[W]) { bounded_pattern_rows(pp, m, 64 * b, p[0], p[1], p[2]); }
+    static QE_S_HD void text_chunk(const uint64_t* tp, int64_t bit, int ncols, uint64_t (&t)[W]) { search_text_words<W>(tp, bit, ncols, t); }
+    static QE_S_HD uint64_t eq(const uint64_t (&p)[W], const uint64_t (&t)[W], int c) {
+        const uint64_t m0 = (uint64_t)0 - ((t[0] >> c) & 1), m1 = (uint64_t)0 - ((t[1] >> c) & 1), mn = (uint64_t)0 - ((t[2] >> c) & 1);
+        const uint64_t acgt = ~(p[0] ^ m0) & ~(p[1] ^ m1) & ~p[2];
+        return (mn & p[2]) | (~mn & acgt);
+    }
+};
+// Set intersection over four membership planes {A, C, G, T} (qe_iupac.h): a row matches the column when they share a base
+struct SearchEqIupac {
+    enum : int { W = 4 };
+    static QE_S_HD int64_t offset(int64_t off3) { return iupac_offset(off3); }
+    static QE_S_HD void pattern_rows(const uint64_t* pp, int m, int b, uint64_t (&p)[W]) {      // rows 64 b .. of the pattern; none: zeros
+        const bool in = b < ((m + 63) >> 6);
+        for (int k = 0; k < W; ++k) p[k] = in ? pp[W * (int64_t)b + k] : 0;
+    }
+    static QE_S_HD void text_chunk(const uint64_t* tp, int64_t bit, int ncols, uint64_t (&t)[W]) { search_text_words<W>(tp, bit, ncols, t); }
+    static QE_S_HD uint64_t eq(const uint64_t (&p)[W], const uint64_t (&t)[W], int c) {
+        const uint64_t mA = (uint64_t)0 - ((t[0] >> c) & 1), mC = (uint64_t)0 - ((t[1] >> c) & 1);
+        const uint64_t mG = (uint64_t)0 - ((t[2] >> c) & 1), mT = (uint64_t)0 - ((t[3] >> c) & 1);
+        return (mA & p[0]) | (mC & p[1]) | (mG & p[2]) | (mT & p[3]);
+    }
+};
+
+QE_S_HD void search_text_chunk(const uint64_t* tp, int64_t bit, int ncols, uint64_t& t0, uint64_t& t1, uint64_t& tn) {
+    uint64_t t[3];
+    SearchEq3::text_chunk(tp, bit, ncols, t);
+    t0 = t[0]; t1 = t[1]; tn = t[2];
+}
+
+// One block over one chunk: Pv / Mv the block's vertical deltas, p its pattern planes, t the chunk's text planes (Eq::W words
+// each), hinP / hinM the horizontal deltas of the row above.  Leaves in oP / oM the raw horizontal deltas of the block's
 // row `lvl` (63: its last row = the carry words of the block below), bits >= ncols zero.
-QE_S_HD void search_block_chunk(uint64_t& Pv, uint64_t& Mv, uint64_t a, uint64_t b, uint64_t nn, uint64_t T0, uint64_t T1, uint64_t TN,
+template <class Eq = SearchEq3>
+QE_S_HD void search_block_chunk(uint64_t& Pv, uint64_t& Mv, const uint64_t (&p)[Eq::W], const uint64_t (&t)[Eq::W],
                                 uint64_t hinP, uint64_t hinM, int lvl, int ncols, uint64_t& oP, uint64_t& oM) {
     uint64_t P = Pv, M = Mv, qP = 0, qM = 0;
     for (int c = 0; c < ncols; ++c) {
-        const uint64_t m0 = (uint64_t)0 - ((T0 >> c) & 1), m1 = (uint64_t)0 - ((T1 >> c) & 1), mn = (uint64_t)0 - ((TN >> c) & 1);
-        const uint64_t acgt = ~(a ^ m0) & ~(b ^ m1) & ~nn;
-        const uint64_t Eq = (mn & nn) | (~mn & acgt);
+        const uint64_t E = Eq::eq(p, t, c);
         const uint64_t PHin = (hinP >> c) & 1, MHin = (hinM >> c) & 1;
-        const uint64_t Xv = Eq | M;
-        const uint64_t Eqc = Eq | MHin;
+        const uint64_t Xv = E | M;
+        const uint64_t Eqc = E | MHin;
         const uint64_t Xh = (((Eqc & P) + P) ^ P) | Eqc;
         uint64_t Ph = M | ~(Xh | P);
         uint64_t Mh = P & Xh;
@@ -117,6 +161,12 @@ QE_S_HD void search_block_chunk(uint64_t& Pv, uint64_t& Mv, uint64_t a, uint64_t
         M = Ph & Xv;
     }
     Pv = P; Mv = M; oP = qP; oM = qM;
+}
+// ... with the three planes of the library's equality word by word: (a, b, nn) the block's, (T0, T1, TN) the chunk's
+QE_S_HD void search_block_chunk(uint64_t& Pv, uint64_t& Mv, uint64_t a, uint64_t b, uint64_t nn, uint64_t T0, uint64_t T1, uint64_t TN,
+                                uint64_t hinP, uint64_t hinM, int lvl, int ncols, uint64_t& oP, uint64_t& oM) {
+    const uint64_t p[3] = {a, b, nn}, t[3] = {T0, T1, TN};
+    search_block_chunk<SearchEq3>(Pv, Mv, p, t, hinP, hinM, lvl, ncols, oP, oM);
 }
 
 // what a lane carries besides its blocks' {Pv, Mv, S}
@@ -150,14 +200,16 @@ QE_S_HD void search_scan(SearchLane& L, int32_t start, uint64_t oP, uint64_t oM,
 
 // The state of a lane's blocks.  NBT > 0: at most NBT blocks, every index a compile-time constant after unrolling (the
 // register form: arrays that stay in registers); NBT == 0: any number (the workspace form).  A store has
-//   uint64_t& P(int b), & M(int b);  int32_t& S(int b);  void planes(int b, uint64_t& a, uint64_t& b, uint64_t& nn)
+//   typedef .. Eq;  uint64_t& P(int b), & M(int b);  int32_t& S(int b);  void planes(int b, uint64_t (&p)[Eq::W])
 //
-// One chunk: text columns [col0, col0 + ncols) of the task, planes (T0, T1, TN).
+// One chunk: text columns [col0, col0 + ncols) of the task, planes t (Store::Eq::W words; the library's equality also as
+// (T0, T1, TN)).
 //
 // Scan: what becomes of row m.  row(): the last block was computed, its row-m deltas are (oP, oM) from the value `start`;
 // no_row(): the chunk left the last block out.
 template <int NBT, class Store, class Scan>
-QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols, Scan& scan) {
+QE_S_HD void search_chunk(Store& st, SearchLane& L, const uint64_t (&t)[Store::Eq::W], int col0, int ncols, Scan& scan) {
+    typedef typename Store::Eq Eq;
     constexpr int UF = NBT ? NBT : 1;                         // the register form unrolls over its blocks; the workspace form does not
     (void)UF;
     const int nbl = NBT ? NBT : L.nb;
@@ -187,10 +239,10 @@ QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, ui
 #endif
     for (int b = 0; b < nbl; ++b) {
         if (b >= L.live) continue;
-        uint64_t pa, pb, pn, oP, oM;
-        st.planes(b, pa, pb, pn);
+        uint64_t p[Eq::W], oP, oM;
+        st.planes(b, p);
         const bool last = b == L.nb - 1;
-        search_block_chunk(st.P(b), st.M(b), pa, pb, pn, T0, T1, TN, hP, hM, last ? ((L.m - 1) & 63) : 63, ncols, oP, oM);
+        search_block_chunk<Eq>(st.P(b), st.M(b), p, t, hP, hM, last ? ((L.m - 1) & 63) : 63, ncols, oP, oM);
         const int32_t start = st.S(b);
         st.S(b) = start + search_popc(oP) - search_popc(oM);
         if (last) scan.row(L, start, oP, oM, col0, ncols);
@@ -205,9 +257,19 @@ struct SearchBestScan {
     QE_S_HD void no_row(SearchLane&) {}
 };
 template <int NBT, class Store>
-QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols) {
+QE_S_HD void search_chunk(Store& st, SearchLane& L, const uint64_t (&t)[Store::Eq::W], int col0, int ncols) {
     SearchBestScan scan;
-    search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols, scan);
+    search_chunk<NBT>(st, L, t, col0, ncols, scan);
+}
+template <int NBT, class Store, class Scan>
+QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols, Scan& scan) {
+    const uint64_t t[3] = {T0, T1, TN};
+    search_chunk<NBT>(st, L, t, col0, ncols, scan);
+}
+template <int NBT, class Store>
+QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, uint64_t TN, int col0, int ncols) {
+    const uint64_t t[3] = {T0, T1, TN};
+    search_chunk<NBT>(st, L, t, col0, ncols);
 }
 
 // ---- every occurrence.  Where a lane's occurrences go: {end, score} number i at out[i * stride], the first `cap` of them
@@ -271,31 +333,35 @@ QE_S_HD void search_answer(const SearchLane& L, int32_t& score, int32_t& end) { 
 
 // The workspace form's store: Pv / Mv / S of block b at stride `stride` elements (64 on the device: [block][lane]), the
 // pattern planes read from memory every chunk
-struct SearchWsStore {
+template <class E>
+struct SearchWsStoreOf {
+    typedef E Eq;
     uint64_t* pv; uint64_t* mv; int32_t* s; int64_t stride;
     const uint64_t* pp; int32_t m;
     QE_S_HD uint64_t& P(int b) { return pv[(int64_t)b * stride]; }
     QE_S_HD uint64_t& M(int b) { return mv[(int64_t)b * stride]; }
     QE_S_HD int32_t& S(int b) { return s[(int64_t)b * stride]; }
-    QE_S_HD void planes(int b, uint64_t& a, uint64_t& bb, uint64_t& nn) { bounded_pattern_rows(pp, m, 64 * b, a, bb, nn); }
+    QE_S_HD void planes(int b, uint64_t (&p)[E::W]) { E::pattern_rows(pp, m, b, p); }
 };
+typedef SearchWsStoreOf<SearchEq3> SearchWsStore;
 // The register form's: everything of up to NB blocks in arrays
-template <int NB>
+template <int NB, class E = SearchEq3>
 struct SearchRegStore {
-    uint64_t pv[NB], mv[NB], pa[NB], pb[NB], pn[NB]; int32_t s[NB];
+    typedef E Eq;
+    uint64_t pv[NB], mv[NB], pl[NB][E::W]; int32_t s[NB];
     QE_S_HD uint64_t& P(int b) { return pv[b]; }
     QE_S_HD uint64_t& M(int b) { return mv[b]; }
     QE_S_HD int32_t& S(int b) { return s[b]; }
-    QE_S_HD void planes(int b, uint64_t& a, uint64_t& bb, uint64_t& nn) { a = pa[b]; bb = pb[b]; nn = pn[b]; }
+    QE_S_HD void planes(int b, uint64_t (&p)[E::W]) { for (int k = 0; k < E::W; ++k) p[k] = pl[b][k]; }
     QE_S_HD void load(const uint64_t* pp, int m) {
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
-        for (int b = 0; b < NB; ++b) bounded_pattern_rows(pp, m, 64 * b, pa[b], pb[b], pn[b]);
+        for (int b = 0; b < NB; ++b) E::pattern_rows(pp, m, b, pl[b]);
     }
 };
 
-// One task, lane by lane as the kernels do it: pattern planes pp (m bases, words [0, 3 ceil(m / 64))), the text's planes tp
+// One task, lane by lane as the kernels do it: pattern planes pp (m bases, words [0, W ceil(m / 64))), the text's planes tp
 // read from bit offset tbit for n columns.  A lane whose bound has dropped below zero has its answer (an exact occurrence
 // at the smallest end) and stops.
 template <int NBT, class Store>
@@ -303,9 +369,9 @@ QE_S_HD void search_run(Store& st, SearchLane& L, const uint64_t* tp, int64_t tb
     search_store_init<NBT>(st, L);
     for (int col0 = 0; col0 < L.n && L.k >= 0; col0 += 64) {
         const int ncols = L.n - col0 < 64 ? L.n - col0 : 64;
-        uint64_t T0, T1, TN;
-        search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
-        search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols);
+        uint64_t t[Store::Eq::W];
+        Store::Eq::text_chunk(tp, tbit + col0, ncols, t);
+        search_chunk<NBT>(st, L, t, col0, ncols);
     }
 }
 
@@ -315,9 +381,9 @@ QE_S_HD void search_run_hits(Store& st, SearchLane& L, SearchHitScan& H, const u
     search_store_init<NBT>(st, L);
     for (int col0 = 0; col0 < L.n; col0 += 64) {
         const int ncols = L.n - col0 < 64 ? L.n - col0 : 64;
-        uint64_t T0, T1, TN;
-        search_text_chunk(tp, tbit + col0, ncols, T0, T1, TN);
-        search_chunk<NBT>(st, L, T0, T1, TN, col0, ncols, H);
+        uint64_t t[Store::Eq::W];
+        Store::Eq::text_chunk(tp, tbit + col0, ncols, t);
+        search_chunk<NBT>(st, L, t, col0, ncols, H);
     }
     H.finish();
 }

@@ -1005,7 +1005,7 @@ static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList
 #ifndef QE_HAVE_K_SEARCH
 // a kernels header without it (the host-only build's stand-ins): the same source on the host, task by task, in the
 // layout and with the arguments of the device form
-template <int NB>
+template <int NB, class Eq = SearchEq3>
 static void k_search(SearchArgs A) {
     for (int t = 0; t < A.T.ntasks; ++t) {
         const int pair = A.T.pair[t];
@@ -1023,17 +1023,17 @@ static void k_search(SearchArgs A) {
         valid = valid && search_blocks(m) <= nbg;
         SearchLane L;
         search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, A.flags);
-        const u64* pp = A.P.pl_p + A.P.pl_p_off[pair];
-        const u64* tp = A.P.pl_t + A.P.pl_t_off[pair];
+        const u64* pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]);
+        const u64* tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]);
         if (valid) {
             if constexpr (NB > 0) {
-                SearchRegStore<(NB > 0 ? NB : 1)> R;
+                SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
                 for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
                 R.load(pp, m);
                 search_run<NB>(R, L, tp, tbit);
             } else {
                 u64* base = (u64*)(A.ws + A.g_ws_off[g]);
-                SearchWsStore W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
+                SearchWsStoreOf<Eq> W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
                 search_run<0>(W, L, tp, tbit);
             }
         }
@@ -1053,7 +1053,7 @@ static void k_search(SearchArgs A) {
 
 #ifndef QE_HAVE_K_SEARCH_HITS
 // ... and of the all-occurrences kernels (SearchHitsArgs, HitExpandArgs)
-template <int NB>
+template <int NB, class Eq = SearchEq3>
 static void k_search_hits(SearchHitsArgs X) {
     const SearchArgs& A = X.S;
     for (int t = 0; t < A.T.ntasks; ++t) {
@@ -1066,16 +1066,16 @@ static void k_search_hits(SearchHitsArgs X) {
         search_lane_init(L, m, n, A.mode, bound, 0);
         SearchHitScan H;
         H.init(L, reinterpret_cast<SearchHit*>(X.raw) + (int64_t)t * X.max_hits, 1, X.max_hits);
-        const u64* pp = A.P.pl_p + A.P.pl_p_off[pair];
-        const u64* tp = A.P.pl_t + A.P.pl_t_off[pair];
+        const u64* pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]);
+        const u64* tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]);
         if constexpr (NB > 0) {
-            SearchRegStore<(NB > 0 ? NB : 1)> R;
+            SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
             for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
             R.load(pp, m);
             search_run_hits<NB>(R, L, H, tp, 0);
         } else {
             u64* base = (u64*)(A.ws + A.g_ws_off[g]);
-            SearchWsStore W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
+            SearchWsStoreOf<Eq> W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
             search_run_hits<0>(W, L, H, tp, 0);
         }
         X.o_found[pair] = H.found; X.o_best[pair] = H.best; X.o_len[pair] = H.sink.count - 1;
@@ -1100,6 +1100,18 @@ static void k_hits_expand(HitExpandArgs A) {
 }
 static void k_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) {
     for (int64_t j = 0; j < total; ++j) hits[3 * j] = o_start[j] < 0 ? -1 : hits[3 * j] + o_start[j];
+}
+#endif
+
+#ifndef QE_HAVE_K_SEARCH_IUPAC
+// ... and of the two producers of a flagged run's four planes: the scalar code of qe_iupac.h, so the host-only build of a
+// flagged run gives true answers (of an ASCII batch; a packed one derives them from the zeros k_unpack_wire's stand-in leaves)
+static void k_pack_iupac(IupacPackArgs A) {
+    for (int i = 0; i < A.nseq; ++i)
+        iupac_pack(A.asc + A.asc_off[i], A.len[i], A.reverse != 0, A.acgt_only != 0, A.planes + iupac_offset(A.pl_off[i]));
+}
+static void k_planes_iupac(IupacPlanesArgs A) {
+    for (int i = 0; i < A.nseq; ++i) iupac_from_planes3(A.src + A.pl_off[i], A.len[i], A.n_empty != 0, A.dst + iupac_offset(A.pl_off[i]));
 }
 #endif
 
@@ -1157,12 +1169,70 @@ static SearchWs search_workspace(Context& C, const TaskList& Lw) {
     return W;
 }
 
+// The kernel of a form (0 the workspace form, 1 / 2 / 3 the register form of 1 / 2 / 4 blocks) under the run's equality
+template <class Eq> static void launch_search_eq(Context& C, int f, const SearchArgs& a, size_t ng) {
+    if (f == 0) launch_groups(C, k_search<0, Eq>, a, ng, 4, 0);
+    else if (f == 1) launch_groups(C, k_search<1, Eq>, a, ng, 4, 0);
+    else if (f == 2) launch_groups(C, k_search<2, Eq>, a, ng, 4, 0);
+    else launch_groups(C, k_search<4, Eq>, a, ng, 4, 0);
+}
+static void launch_search(Context& C, int eq, int f, const SearchArgs& a, size_t ng) {
+    if (eq) launch_search_eq<SearchEqIupac>(C, f, a, ng); else launch_search_eq<SearchEq3>(C, f, a, ng);
+}
+template <class Eq> static void launch_search_hits_eq(Context& C, int f, const SearchHitsArgs& x, size_t ng) {
+    if (f == 0) launch_groups(C, k_search_hits<0, Eq>, x, ng, 4, 0);
+    else if (f == 1) launch_groups(C, k_search_hits<1, Eq>, x, ng, 4, 0);
+    else if (f == 2) launch_groups(C, k_search_hits<2, Eq>, x, ng, 4, 0);
+    else launch_groups(C, k_search_hits<4, Eq>, x, ng, 4, 0);
+}
+static void launch_search_hits(Context& C, int eq, int f, const SearchHitsArgs& x, size_t ng) {
+    if (eq) launch_search_hits_eq<SearchEqIupac>(C, f, x, ng); else launch_search_hits_eq<SearchEq3>(C, f, x, ng);
+}
+
+// The planes a search pass reads.  The library's equality: the batch's own (pair_view).  A flagged run (eq 1
+// QUICKED_SEARCH_IUPAC, 2 QUICKED_SEARCH_IUPAC_PATTERN): four membership planes, packed into the run's pool
+// when a pass first asks for them -- forward for the forward pass, reversed for the start pass -- from the resident ASCII
+// (k_pack_iupac) or, packed batch, from its three planes (k_planes_iupac; the reversed ones from the reversed three).  They
+// live as long as the run: no batch state, nothing a reload, the other flag or another plane set could leave stale.  The
+// offsets stay the batch's three-plane ones (SearchEqIupac::offset).
+static size_t search_iupac_bytes(const quicked_batch& B, int eq, int mode) {      // what a flagged run takes from its pool for them
+    if (!eq) return 0;
+    const size_t one = (iupac_offset((int64_t)B.pl_p_words) + iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64) + 512;
+    return mode == SEARCH_INFIX ? 2 * one : one;
+}
+static PairView search_planes(quicked_batch& B, Context& C, int eq, bool reversed) {
+    if (!eq) return pair_view(B, reversed);
+    if (B.packed && reversed && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    PairView v = pair_view(B, reversed);
+    u64* pl_p = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_p_words) + 8);
+    u64* pl_t = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_t_words) + 8);
+    const int blocks = (int)((B.n + 3) / 4);
+    if (B.packed) {
+        IupacPlanesArgs a;
+        a.nseq = (int32_t)B.n;
+        a.src = v.pl_p; a.dst = pl_p; a.pl_off = B.d_plp_off; a.len = B.d_p_len; a.n_empty = 0;
+        hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+        a.src = v.pl_t; a.dst = pl_t; a.pl_off = B.d_plt_off; a.len = B.d_t_len; a.n_empty = eq == 2 ? 1 : 0;
+        hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+    } else {
+        IupacPackArgs a;
+        a.nseq = (int32_t)B.n; a.reverse = reversed ? 1 : 0;
+        a.asc = B.d_asc_p; a.asc_off = B.d_p_off; a.len = B.d_p_len; a.planes = pl_p; a.pl_off = B.d_plp_off; a.acgt_only = 0;
+        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+        a.asc = B.d_asc_t; a.asc_off = B.d_t_off; a.len = B.d_t_len; a.planes = pl_t; a.pl_off = B.d_plt_off; a.acgt_only = eq == 2 ? 1 : 0;
+        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    v.pl_p = pl_p; v.pl_t = pl_t;
+    return v;
+}
+
 // Forward pass over whole pairs, then -- INFIX -- the start pass: the PREFIX form over the reversed planes on the stretch
 // that ends at text_end, bound d, the largest end; it reads the forward pass's results on the device and runs only the
 // tasks within their bound (no host round trip).  Leaves per task of `task_pair` score / start / end and the block steps
 // of both passes on the device.  Both passes are timed as kind 0 (quicked_batch_kernel_times).
 struct SearchOut { std::vector<int32_t> task_pair; int32_t *d_score = nullptr, *d_start = nullptr, *d_end = nullptr; u32* d_adv = nullptr; };
-static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, int mode) {
+static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, int mode, int eq = 0) {
     SearchOut O;
     size_t off[5] = {0, 0, 0, 0, 0};
     for (int f = 0; f < 4; ++f) {
@@ -1180,26 +1250,25 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
     DevTasks T[4];
     for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
     auto pass = [&](bool start_pass) {
+        const PairView PV = search_planes(B, C, eq, start_pass);
         auto* ke = C.kernel_events(0);
         if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
         for (int f = 0; f < 4; ++f) {
             if (S.L[f].pair.empty()) continue;
             SearchArgs a{};
-            a.P = pair_view(B, start_pass); a.T = T[f].v;
+            a.P = PV; a.T = T[f].v;
             a.mode = start_pass ? SEARCH_PREFIX : mode; a.flags = start_pass ? SEARCH_LARGEST_END : 0;
             a.in_score = start_pass ? O.d_score + off[f] : nullptr; a.in_end = start_pass ? O.d_end + off[f] : nullptr;
             a.o_score = O.d_score + off[f]; a.o_end = O.d_end + off[f]; a.o_start = O.d_start + off[f]; a.o_adv = O.d_adv + off[f];
             const size_t ng = (size_t)S.L[f].ngroups();
-            if (f == 0) { a.ws = ws; a.g_ws_off = d_ws_off; a.g_nb = d_nb; launch_groups(C, k_search<0>, a, ng, 4, 0); }
-            else if (f == 1) launch_groups(C, k_search<1>, a, ng, 4, 0);
-            else if (f == 2) launch_groups(C, k_search<2>, a, ng, 4, 0);
-            else launch_groups(C, k_search<4>, a, ng, 4, 0);
+            if (f == 0) { a.ws = ws; a.g_ws_off = d_ws_off; a.g_nb = d_nb; }
+            launch_search(C, eq, f, a, ng);
         }
         if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     };
     pass(false);
     if (mode == SEARCH_INFIX) {
-        if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+        if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
         pass(true);
     }
     return O;
@@ -1219,7 +1288,7 @@ struct SearchHitsOut {
     int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
     int64_t total = 0;
 };
-static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits) {
+static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits, int eq = 0) {
     SearchHitsOut O;
     size_t off[5] = {0, 0, 0, 0, 0};
     for (int f = 0; f < 4; ++f) {
@@ -1240,19 +1309,18 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
     const SearchWs Wk = search_workspace(C, S.L[0]);
     DevTasks T[4];
     for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
+    const PairView PF = search_planes(B, C, eq, false);
     auto* ke = C.kernel_events(0);
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
     for (int f = 0; f < 4; ++f) {
         if (S.L[f].pair.empty()) continue;
         SearchHitsArgs x{};
-        x.S.P = pair_view(B, false); x.S.T = T[f].v; x.S.mode = mode; x.S.o_adv = O.d_adv + off[f];
+        x.S.P = PF; x.S.T = T[f].v; x.S.mode = mode; x.S.o_adv = O.d_adv + off[f];
         x.max_hits = max_hits; x.raw = raw + 2 * off[f] * (size_t)max_hits;
         x.o_found = O.d_found; x.o_best = O.d_best; x.o_len = d_len;
         const size_t ng = (size_t)S.L[f].ngroups();
-        if (f == 0) { x.S.ws = Wk.ws; x.S.g_ws_off = Wk.d_ws_off; x.S.g_nb = Wk.d_nb; launch_groups(C, k_search_hits<0>, x, ng, 4, 0); }
-        else if (f == 1) launch_groups(C, k_search_hits<1>, x, ng, 4, 0);
-        else if (f == 2) launch_groups(C, k_search_hits<2>, x, ng, 4, 0);
-        else launch_groups(C, k_search_hits<4>, x, ng, 4, 0);
+        if (f == 0) { x.S.ws = Wk.ws; x.S.g_ws_off = Wk.d_ws_off; x.S.g_nb = Wk.d_nb; }
+        launch_search_hits(C, eq, f, x, ng);
     }
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     // offsets in the order of the pairs (a pair without a task has -1 + 1 = 0 stored; every pair counts: the lengths stand in
@@ -1293,14 +1361,15 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
         HIP_CHECK(hipGetLastError());
     }
     if (!infix) return O;
-    if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    const PairView PR = search_planes(B, C, eq, true);
     ke = C.kernel_events(0);
     if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
     const size_t ngh = (nh + 63) / 64;
     for (int f = 0; f < 4; ++f) {
         if (S.L[f].pair.empty()) continue;
         SearchArgs a{};
-        a.P = pair_view(B, true);
+        a.P = PR;
         a.mode = SEARCH_PREFIX; a.flags = SEARCH_LARGEST_END;
         size_t slice = ngh;                              // groups per launch
         if (f == 0) {
@@ -1323,10 +1392,7 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
             a.T.ntasks = (int32_t)std::min(nh - j0, ng * 64);
             a.T.pair = o_pair[f] + j0; a.T.m = o_m + j0; a.T.n = o_n + j0; a.T.cutoff = o_score + j0;
             a.in_score = o_score + j0; a.in_end = o_end + j0; a.o_start = o_start + j0; a.o_adv = O.d_adv2 + j0;
-            if (f == 0) launch_groups(C, k_search<0>, a, ng, 4, 0);
-            else if (f == 1) launch_groups(C, k_search<1>, a, ng, 4, 0);
-            else if (f == 2) launch_groups(C, k_search<2>, a, ng, 4, 0);
-            else launch_groups(C, k_search<4>, a, ng, 4, 0);
+            launch_search(C, eq, f, a, ng);
         }
     }
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));

@@ -69,6 +69,22 @@ struct RevArgs {
     const u64* fwd;  u64* rev;  const int64_t* pl_off;  const int32_t* len;
 };
 
+// The four membership planes of a flagged search run (qe_iupac.h; k_pack_iupac from resident ASCII, k_planes_iupac from the
+// three planes of a packed batch): [row][4] = {A, C, G, T} per 64 bases, two zero rows behind every sequence, a sequence at
+// word iupac_offset(pl_off[seq]) -- pl_off are the three-plane offsets.  No pack flags are written.
+struct IupacPackArgs {
+    int32_t nseq;
+    const uint8_t* asc;  const int64_t* asc_off;  const int32_t* len;
+    u64* planes;  const int64_t* pl_off;
+    int32_t reverse;         // != 0: the reversed string
+    int32_t acgt_only;       // != 0: a byte that is not A C G T U (either case) has the empty set
+};
+struct IupacPlanesArgs {
+    int32_t nseq;
+    const u64* src;  u64* dst;  const int64_t* pl_off;  const int32_t* len;      // src: forward or reversed three planes
+    int32_t n_empty;         // != 0: the not-ACGT symbol has the empty set (else the full one)
+};
+
 // BandEd, score-only or fill (bpm_banded.c:791-964 / 199-316)
 struct BandedArgs {
     PairView P;
