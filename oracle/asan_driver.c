@@ -5,7 +5,8 @@
  * the host-side restatement of every kernel's arithmetic is what gets sanitised.
  *
  * Walks shapes that stress the index arithmetic: lengths around block borders, length mismatch, empty-ish inputs,
- * N / lower-case symbols, large indels (all QuickEd stages), forced deep Hirschberg splits; every alignment is
+ * N / lower-case symbols, large indels (all QuickEd stages), forced deep Hirschberg splits, texts from half to twice
+ * their pattern (a slice of the grid of tests/unequal_lib.py); every alignment is
  * checked (valid CIGAR, edit count == score, QuickEd / BandEd / Hirschberg score == full-height exact distance).
  */
 #include <stdint.h>
@@ -47,6 +48,9 @@ static void one(const char* p, int m, const char* t, int n, int exact_algos) {
             free(ops);
         }
         /* exact on upper-case ACGT input with a band that holds the distance (bandwidth 15 %, <= 10 % divergence here) */
+        /* (exact_algos == 2, very unequal lengths: score-only BandEd cuts its band by scores that the length difference
+           inflates and may return a path's cost above the distance, as the reference does) */
+        if (exact_algos == 2 && prm.algo == QO_BANDED && prm.only_score) { CHECK(score == -1 || score >= exact, "score-only BandEd: %d below the distance %lld", score, (long long)exact); qo_free(cg); continue; }
         if (exact_algos && prm.bandwidth == 15 && (prm.algo == QO_QUICKED || ((prm.algo == QO_BANDED || prm.algo == QO_HIRSCHBERG) && exact * 100 <= (int64_t)15 * (m > n ? m : n))))
             CHECK(score == exact, "algo %d only_score %d: score %d != exact %lld (m %d n %d)", prm.algo, prm.only_score, score, (long long)exact, m, n);
         qo_free(cg);
@@ -77,6 +81,32 @@ int main(void) {
         free(p); free(t);
     }
     one("ACGT", 4, "", 0, 0); one("", 0, "ACGT", 4, 0);
+    /* unequal lengths: every ratio and both shapes of tests/unequal_lib.py's grid at pattern lengths 65 and 500 (its cases
+       17 .. 32 and 97 .. 112: seed 7000 + case, 3 % errors, the sequence that has to be the shorter one cut at its end or in
+       its middle) */
+    {
+        static const int LENS[] = {64, 65, 127, 128, 129, 200, 500, 1000, 2500};
+        static const int RATIOS[][2] = {{1, 2}, {2, 3}, {4, 5}, {9, 10}, {11, 10}, {5, 4}, {3, 2}, {2, 1}};
+        int k = 0;
+        for (int li = 0; li < 9; ++li)
+            for (int ri = 0; ri < 8; ++ri)
+                for (int mid = 0; mid < 2; ++mid) {
+                    ++k;
+                    const int m = LENS[li], n = m * RATIOS[ri][0] / RATIOS[ri][1];
+                    if (m != 65 && m != 500) continue;
+                    const int64_t len = m > n ? m : n, cap = qe_gen_pattern_capacity(len, 0.03, 0, 0);
+                    char* p = (char*)malloc((size_t)cap + 1); char* t = (char*)malloc((size_t)len + 1);
+                    const int64_t pm = qe_gen_pair(7000 + (uint64_t)k, 0, len, 0.03, 0, 0, p, t);
+                    char* cut = n < m ? t : p;                         /* the one that has to be the shorter */
+                    const int64_t have = n < m ? len : pm, keep = n < m ? n : m, head = mid ? keep / 2 : keep;
+                    memmove(cut + head, cut + have - (keep - head), (size_t)(keep - head));
+                    const int64_t fm = n < m ? pm : keep, fn = n < m ? keep : len;
+                    char* pp = (char*)malloc((size_t)fm); char* tt = (char*)malloc((size_t)fn);
+                    memcpy(pp, p, (size_t)fm); memcpy(tt, t, (size_t)fn);
+                    one(pp, (int)fm, tt, (int)fn, 2);
+                    free(pp); free(tt); free(p); free(t);
+                }
+    }
     /* forced deep Hirschberg recursion (qo_hirschberg with a 4 KiB split threshold) */
     {
         const int64_t len = 2500, cap = qe_gen_pattern_capacity(len, 0.08, 0, 0);

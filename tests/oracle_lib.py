@@ -255,11 +255,12 @@ def edlib_distance(pattern, text):
 
 
 # --------------------------------------------------------------------------- #
-# the compiled reference's results as recorded (tests/golden/ref_cases.json, written by tests/golden/make_ref_cases.py
-# from the same seeded inputs): what tests/test_oracle_vs_ref.py compares with where oracle/_ref was not built.  Where it
-# was, the live result is used and must still equal its record.
+# the compiled reference's results as recorded (tests/golden/ref_cases.json and ref_unequal_cases.json, written by
+# tests/golden/make_ref_cases.py from the same seeded inputs): what tests/test_oracle_vs_ref.py compares with where
+# oracle/_ref was not built.  Where it was, the live result is used and must still equal its record.
 # --------------------------------------------------------------------------- #
 REF_CASES = os.path.join(ROOT, "tests", "golden", "ref_cases.json")
+REF_UNEQUAL_CASES = os.path.join(ROOT, "tests", "golden", "ref_unequal_cases.json")      # the grid of tests/unequal_lib.py
 RECORD = None          # make_ref_cases.py sets a dict here: the live results are collected into it instead of checked
 _cases = None
 
@@ -282,30 +283,72 @@ def digest(res):
     return [st, sc, hashlib.sha256(cg.encode()).hexdigest() if cg is not None else None]
 
 
-def _expected(key, live, have):
+def _expected(key, live, have, pinned=True):
+    """pinned = False: a result the reference does not define (outside its domain): recorded, replayed, but a live run
+    need not repeat it"""
     global _cases
     if _cases is None:
         import json
-        if os.path.exists(REF_CASES):
-            with open(REF_CASES) as f:
-                _cases = json.load(f)["cases"]
-        else:
-            _cases = {}
+        _cases = {}
+        for path in (REF_CASES, REF_UNEQUAL_CASES):
+            if os.path.exists(path):
+                with open(path) as f:
+                    _cases.update(json.load(f)["cases"])
     rec = _cases.get(key)
     if have:
         got = live()
         if RECORD is not None:
             RECORD[key] = got
-        else:
-            assert rec is None or rec == got, f"tests/golden/ref_cases.json[{key}] = {rec}, the compiled reference now gives {got}"
+        elif pinned:
+            assert rec is None or rec == got, f"recorded under tests/golden: case {key} = {rec}, the compiled reference now gives {got}"
         return got
-    assert rec is not None, f"no recorded reference result for case {key}: regenerate tests/golden/ref_cases.json (make_ref_cases.py)"
+    assert rec is not None, f"no recorded reference result for case {key}: regenerate the fixtures of tests/golden (make_ref_cases.py)"
     return rec
 
 
 def ref_expected(pattern, text, **kw):
     """the reference's (status, score, cigar) for quicked_align, in digest() form"""
     return _expected(case_key("align", pattern, text, kw), lambda: digest(ref_align(pattern, text, **kw)), have_ref())
+
+
+class ReferenceDied(AssertionError):
+    """the child that ran the compiled reference did not hand a result back"""
+
+
+def ref_align_isolated(pattern, text, **kw):
+    """digest(ref_align(...)) computed in a forked child that hands it back over a pipe.  The reference ends with SIGSEGV
+    on some inputs outside its domain (tests/unequal_lib.py); a child that dies is a failed assertion naming the pair, never a
+    dead test process."""
+    import json
+    ref()                                           # loaded before the fork: the child only calls it
+    rd, wr = os.pipe()
+    pid = os.fork()
+    if pid == 0:
+        code = 1
+        try:
+            os.close(rd)
+            os.write(wr, json.dumps(digest(ref_align(pattern, text, **kw))).encode())
+            code = 0
+        finally:
+            os._exit(code)
+    os.close(wr)
+    chunks = []
+    while True:
+        b = os.read(rd, 65536)
+        if not b:
+            break
+        chunks.append(b)
+    os.close(rd)
+    _, status = os.waitpid(pid, 0)
+    if not (os.WIFEXITED(status) and os.WEXITSTATUS(status) == 0 and chunks):
+        how = f"signal {os.WTERMSIG(status)}" if os.WIFSIGNALED(status) else f"exit status {os.WEXITSTATUS(status)}"
+        raise ReferenceDied(f"the compiled reference died ({how}) on pattern x text = {len(pattern)} x {len(text)}, {kw}")
+    return json.loads(b"".join(chunks))
+
+
+def ref_expected_isolated(pattern, text, pinned=True, **kw):
+    """ref_expected with the live call in a child of its own (same key, same form; replaying a record needs no child)"""
+    return _expected(case_key("align", pattern, text, kw), lambda: ref_align_isolated(pattern, text, **kw), have_ref(), pinned)
 
 
 def ref_sam_expected(ops, show_mismatches):

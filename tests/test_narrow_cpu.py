@@ -8,8 +8,14 @@ around the floor of 65 and around multiples of 64)."""
 import os
 import re
 
+import shutil
+
+import pytest
+
+import masked_lib as ML
 import narrow_lib as NL
 import oracle_lib as O
+import unequal_lib as U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -106,3 +112,31 @@ def test_the_library_rule_is_the_modelled_rule(tmp_path):
     assert n > 1000
     with open(os.path.join(ROOT, "quicked_amd", "csrc", "qe_pool.h")) as f:
         assert '"QE_SCORE_NARROW", -1' in f.read()
+
+
+@pytest.mark.parametrize("bandwidth", [15, 40, 100])
+def test_the_walk_model_holds_on_unequal_lengths(tmp_path, bandwidth):
+    """tests/native/banded_walk.h (the CPU model of k_banded<false> that the GPU tests of the two-pass path compare with)
+    on the grid of tests/unequal_lib.py -- texts from half to twice their pattern, where the prologue, the relative cutoff and
+    the last block's place in the band take values that datagen's pairs never give them: groups of 64 in library order at
+    the full cutoff and at half of it, the union walk and the lane-relative one, with and without masked passes.  Per pair
+    the walk's score, first / last / pos_v and block advances are the oracle's own pass's (pass_plan_cpu: diffs), the -1
+    of a band below the distance included; and the oracle's pass is the one test_oracle_vs_ref.py pins to the reference."""
+    if shutil.which("g++") is None:
+        pytest.fail("g++ is needed to compile the walk for the host")
+    exe = ML.build_walk(str(tmp_path))
+    pairs = U.pairs()
+    assert len(pairs) == 144 and {-1, 1} == {(len(p) > len(t)) - (len(p) < len(t)) for p, t in pairs}
+    order = NL.library_order(pairs)
+    full = [NL.max_cutoff(len(p), len(t), bandwidth) for p, t in pairs]
+    for label, cut in (("full", full), ("half", [c // 2 for c in full])):
+        path = os.path.join(str(tmp_path), f"unequal_{bandwidth}_{label}.bin")
+        ML.write_launch(path, pairs, [(i, cut[i]) for i in order])
+        for lane_rel in (1, 0):
+            for masked in (1, 0):
+                counts, code, out = ML.walk(exe, path, lane_rel, masked)
+                print("unequal", bandwidth, label, "lane_rel", lane_rel, out.strip().splitlines()[0])
+                assert code == 0 and counts["pairs"] == 144 and counts["diffs"] == 0 and counts["rule_diffs"] == 0, out[-2000:]
+    # the pass the walk was compared with is the one behind the oracle's BANDED score-only result
+    for (p, t), c in zip(pairs, full):
+        assert NL.banded_score(p, t, c)[0] == O.oracle_align(p, t, algo=2, only_score=True, bandwidth=bandwidth)[1]

@@ -1,11 +1,12 @@
 """Oracle vs the compiled reference on seeded random inputs.  Where oracle/_ref was built (make -C oracle ref) the
-reference runs live; elsewhere its results come from tests/golden/ref_cases.json, recorded from the same inputs by
-tests/golden/make_ref_cases.py (oracle_lib.ref_expected and friends)."""
+reference runs live; elsewhere its results come from tests/golden/ref_cases.json and ref_unequal_cases.json, recorded from the
+same inputs by tests/golden/make_ref_cases.py (oracle_lib.ref_expected and friends)."""
 import ctypes as C
 
 import pytest
 
 import oracle_lib as O
+import unequal_lib as U
 from quicked_amd import datagen
 
 RUNS = [
@@ -128,3 +129,72 @@ def test_hirschberg_real_splits_against_the_compiled_reference():
             assert tr["hirschberg_splits"] > 0, (kw, gen)
             assert O.digest((st, sc, cg)) == O.ref_expected(p, t, **kw), (kw, gen, len(p), len(t))
     assert splits >= 30
+
+
+def test_a_reference_call_that_dies_is_a_failed_assertion():
+    """oracle_lib.ref_align_isolated with stand-ins for the reference: a child that is killed before it hands a result back
+    raises an AssertionError that names the pair, in this process, which lives on; a child that returns hands its digest
+    over the pipe"""
+    import os
+    import signal
+    saved = O.ref, O.ref_align
+    try:
+        O.ref = lambda: None
+        O.ref_align = lambda p, t, **kw: os.kill(os.getpid(), signal.SIGKILL)
+        with pytest.raises(O.ReferenceDied, match=r"signal 9.* 3 x 5, \{'algo': 2\}"):
+            O.ref_align_isolated(b"ACG", b"ACGTA", algo=2)
+        O.ref_align = lambda p, t, **kw: (1, len(t) - len(p), "3M2I")
+        assert O.ref_align_isolated(b"ACG", b"ACGTA", algo=2) == O.digest((1, 2, "3M2I"))
+        O.ref_align = lambda p, t, **kw: (1, 0, None)
+        assert O.ref_align_isolated(b"ACG", b"ACG") == [1, 0, None]
+    finally:
+        O.ref, O.ref_align = saved
+
+
+_EXACT = {}
+
+
+def _exact(p, t):
+    if (p, t) not in _EXACT:
+        _EXACT[(p, t)] = O.oracle().qo_exact_distance(p, len(p), t, len(t))
+    return _EXACT[(p, t)]
+
+
+@pytest.mark.parametrize("name", list(U.PARAM_SETS))
+def test_unequal_lengths_inside_the_domain(name):
+    """the grid of tests/unequal_lib.py (text from half to twice the pattern, the surplus cut from the end or out of the
+    middle): status, score and CIGAR of the oracle are the compiled reference's on every pair inside the reference's domain
+    (unequal_lib.in_domain), and the exact distance wherever the algorithm is exact there (unequal_lib.EXACT_SETS; the
+    others overshoot in the reference as they do here, and are bounded from below).  Every live call of the reference runs in
+    a child of its own (oracle_lib.ref_align_isolated): a reference that dies fails this test with the pair's lengths.
+    Outside the domain nothing is compared but what DESIGN.md 5 defines: score-only BandEd below the distance is -1 here,
+    negative there.
+
+    What keeps the domain from swallowing the grid: oracle and reference are identical on at least 90 % of ALL 144 pairs of
+    every set, the pairs outside the domain included (135 of 144 at bandwidth 15, the lowest).  The domain rule of the
+    CIGAR-producing BandEd / Hirschberg sets is the narrow one of tests/test_gpu_parity.py (distance <= cutoff) and leaves
+    35 pairs at bandwidth 15 and 108 at bandwidth 40 -- a length difference alone is a distance above the cutoff -- but the
+    two agree far beyond it: on 135 and 143 pairs."""
+    kw = U.PARAM_SETS[name]
+    cases = U.grid()
+    assert len(cases) == 144
+    inside = identical = 0
+    for k, (p, t, shape) in enumerate(cases, 1):
+        where = (name, k, shape, len(p), len(t))
+        res = O.oracle_align(p, t, **kw)
+        exact = _exact(p, t)
+        ok = U.in_domain(kw, len(p), len(t), exact, res[1])
+        ref = O.ref_expected_isolated(p, t, pinned=ok, **kw)
+        identical += O.digest(res) == ref
+        if ok:
+            inside += 1
+            assert O.digest(res) == ref, where
+            if name in U.EXACT_SETS:
+                assert res[1] == exact, where
+            else:
+                assert res[1] >= exact, where              # a heuristic's score is the cost of a path
+        elif kw.get("only_score"):
+            assert res[1] == -1 and ref[1] < 0, (where, res, ref)
+    print(name, "inside the domain", inside, "identical", identical, "of", len(cases))
+    assert inside >= U.MIN_INSIDE[name], (name, inside)
+    assert identical * 10 >= 9 * len(cases), (name, identical)
