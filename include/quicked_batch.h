@@ -215,6 +215,44 @@ quicked_status_t quicked_batch_run_search_all(quicked_batch_t* batch, int mode,
 quicked_status_t quicked_batch_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored); /* n each, either may be NULL */
 int64_t          quicked_batch_hit_total(quicked_batch_t* batch);               /* sum of stored; -1 after any other run */
 quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t* hits, int64_t* hit_off /* n + 1 */);
+/* Panel search: every text of the batch against ONE shared set of patterns -- n reads against a panel of barcodes, adapters or
+ * primers: "which panel member fits this text best, how well, where, and how far behind is the runner-up?"
+ * Texts and patterns.  The texts are the texts of the batch's pairs; the batch's own patterns are ignored and may all be empty.
+ * The panel is host ASCII, read during the call, laid out like a batch pool: member p is the panel_len[p] bytes at
+ * panel_pool + panel_off[p].
+ * Per text i and panel member p, {d, text_end} is exactly what quicked_batch_run_search defines for that pattern against that
+ * text: the same mode, the same equality, the bound clamped to m.  Member p's bound is max_dist[p] (n_patterns values), or
+ * max_dist_all where max_dist is NULL; d > bound means p is beyond for this text.
+ * Per text result.  The members within their bound are ordered by the key (score, panel index), ascending.  pattern / score are
+ * the smallest key; second_pattern / second_score are the smallest key among the other members -- a duplicate of the best, at a
+ * higher index, is the runner-up with the same score; -1 is reported where there is none.  text_end is the best member's;
+ * text_start is 0 for PREFIX, for INFIX it follows the best search's rule (the longest stretch with distance score), and it is
+ * computed for the best member only.
+ * Other getters.  quicked_batch_scores gives score per text, or -1 with QUICKED_OK when no member is within its bound;
+ * QUICKED_EMPTY_SEQUENCE is reported for an empty text only (every field of its result is -1): the batch pattern's length
+ * plays no part.
+ * QUICKED_PANEL_MATRIX, OR-ed into mode, additionally keeps every {d or -1, text_end or -1}: quicked_batch_panel_matrix copies
+ * them as [text][pattern], n * n_patterns values each (the rows of empty texts are -1).  Without the flag the matrix getter
+ * returns QUICKED_ERROR.
+ * QUICKED_SEARCH_IUPAC and QUICKED_SEARCH_IUPAC_PATTERN apply as in a search run; panel members are the "pattern" side.  ASCII
+ * and packed batches alike, with the same reading of the fifth symbol of QUICKED_WIRE_PLANES3 as in flagged search runs.
+ * QUICKED_ERROR, nothing launched: a NULL batch; a base mode that is not PREFIX or INFIX; both IUPAC flags, or an unknown bit;
+ * n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0; a negative bound; with the matrix flag, (texts) x
+ * n_patterns above 2^28 (every text of the batch has a row in the matrix, the empty ones too).
+ * QUICKED_UNIMPLEMENTED, nothing queued: a member longer than QUICKED_PANEL_MAX_LEN bases (the register form's limit); sync == 0;
+ * a batch configured with check != 0 (as for the other search runs).
+ * No alignments: the tags of quicked_batch_configure_tags are ignored; the CIGAR, tag, location and hit getters return what
+ * they return after any run that produced none of their data.  The two panel getters return QUICKED_ERROR after any run that
+ * was not a panel run.  Counters [0] and kernel_times slot [0] count the passes' block steps and launches, as for a search
+ * run. */
+enum { QUICKED_PANEL_MAX_PATTERNS = 4096, QUICKED_PANEL_MAX_LEN = 256 };
+enum { QUICKED_PANEL_MATRIX = 64 };            /* OR-ed into mode, beside the two IUPAC flags */
+typedef struct { int32_t pattern, score, text_start, text_end, second_pattern, second_score; } quicked_panel_hit_t; /* 24 bytes */
+quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode,
+                                         int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
+                                         const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all, int sync);
+quicked_status_t quicked_batch_panel_results(quicked_batch_t* batch, quicked_panel_hit_t* out /* n */);
+quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* scores, int32_t* text_ends /* n * n_patterns each, [text][pattern]; either may be NULL */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -61,12 +61,17 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_deferred_pairs", "quicked_wire_pack_pool", "quicked_wire_offsets", "quicked_wire_pack_isa", "quicked_pool_trim", "quicked_early_finish_stats",
            "quicked_batch_run_bounded", "quicked_batch_run_search", "quicked_batch_locations",
            "quicked_batch_run_search_all", "quicked_batch_hit_counts", "quicked_batch_hit_total", "quicked_batch_hits",
+           "quicked_batch_run_panel", "quicked_batch_panel_results", "quicked_batch_panel_matrix",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
 HIT_DTYPE = np.dtype([("text_start", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_hit_t
 SEARCH_PREFIX, SEARCH_INFIX = 1, 2
 SEARCH_IUPAC, SEARCH_IUPAC_PATTERN = 16, 32      # OR-ed into a search mode: IUPAC base sets on both sides / on the pattern only
+PANEL_MATRIX = 64                                # OR-ed into a panel run's mode: keep every {score, text_end}
+PANEL_MAX_PATTERNS, PANEL_MAX_LEN = 4096, 256
+PANEL_HIT_DTYPE = np.dtype([("pattern", np.int32), ("score", np.int32), ("text_start", np.int32), ("text_end", np.int32),
+                            ("second_pattern", np.int32), ("second_score", np.int32)])      # quicked_panel_hit_t
 
 _LIB = None
 
@@ -120,6 +125,12 @@ def lib():
     L.quicked_batch_hit_total.restype = C.c_int64
     L.quicked_batch_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_hits.restype = C.c_int
+    L.quicked_batch_run_panel.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int]
+    L.quicked_batch_run_panel.restype = C.c_int
+    L.quicked_batch_panel_results.argtypes = [C.c_void_p, C.c_void_p]
+    L.quicked_batch_panel_results.restype = C.c_int
+    L.quicked_batch_panel_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_panel_matrix.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -401,6 +412,53 @@ class ResidentBatch:
         if st < 0:
             raise QuickedException(st)
         return found, off, hits
+
+    def run_panel(self, mode, panel, max_dist=None, matrix=False, sync=True):
+        """quicked_batch_run_panel: every text of the batch against the panel, a list of bytes (the batch's own patterns are
+        ignored).  mode: SEARCH_PREFIX / SEARCH_INFIX, optionally | SEARCH_IUPAC or | SEARCH_IUPAC_PATTERN (the members are the
+        pattern side).  max_dist: None = no bound, one int for every member, or one bound per member.  matrix=True keeps
+        every member's {score, text_end} for panel_matrix().  Sync runs only."""
+        panel = [bytes(p) for p in panel]
+        k = len(panel)
+        pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
+        plen = np.array([len(p) for p in panel], dtype=np.int32)
+        poff = np.zeros(max(k, 1), dtype=np.int64)
+        if k > 1:
+            poff[1:k] = np.cumsum(plen[:-1], dtype=np.int64)
+        mode = int(mode) | (PANEL_MATRIX if matrix else 0)
+        if max_dist is None:
+            max_dist = 2**31 - 1
+        if np.ndim(max_dist) == 0:
+            st = self._lib.quicked_batch_run_panel(self._h, mode, k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, None, int(max_dist), 1 if sync else 0)
+        else:
+            md = np.ascontiguousarray(max_dist, dtype=np.int32)
+            if md.shape != (k,):
+                raise ValueError("max_dist: one bound per panel member")
+            st = self._lib.quicked_batch_run_panel(self._h, mode, k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, md.ctypes.data, 0, 1 if sync else 0)
+        if st not in (QUICKED_ERROR, QUICKED_UNIMPLEMENTED):
+            self._panel_k = k      # what panel_matrix() sizes its arrays with: the panel of the last run that got past the argument checks
+        return st
+
+    def panel_results(self):
+        """-> a structured array of PANEL_HIT_DTYPE, one entry per text, of the last panel run: the best member, its score and
+        located stretch text[text_start:text_end], the runner-up and its score; -1 where there is none.  QuickedException after
+        any other run"""
+        out = np.zeros(self.n, dtype=PANEL_HIT_DTYPE)
+        st = self._lib.quicked_batch_panel_results(self._h, out.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return out
+
+    def panel_matrix(self):
+        """-> (scores, text_ends), int32 [n, n_patterns], of the last panel run with matrix=True: every member's distance and
+        end in every text, -1 / -1 where the member is beyond its bound (or the text is empty).  QuickedException otherwise"""
+        k = getattr(self, "_panel_k", 0)
+        sc = np.zeros((self.n, max(k, 1)), dtype=np.int32)
+        te = np.zeros((self.n, max(k, 1)), dtype=np.int32)
+        st = self._lib.quicked_batch_panel_matrix(self._h, sc.ctypes.data, te.ctypes.data) if k > 0 else QUICKED_ERROR
+        if st < 0:
+            raise QuickedException(st)
+        return sc, te
 
     def locations(self):
         """-> (text_start, text_end) int32 arrays of the last search run: the located stretch is text[start:end]; -1 / -1 for a

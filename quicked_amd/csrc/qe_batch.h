@@ -104,9 +104,15 @@ struct quicked_batch {
         std::vector<int32_t> found;
         std::vector<int64_t> hit_off;
         std::vector<quicked_hit_t> hits;
+        // panel runs (quicked_batch_run_panel): panel_hits [n] after such a run, else empty (every field -1 for a text without
+        // a member within its bound, or an empty one); with QUICKED_PANEL_MATRIX panel_score / panel_end [n * panel_members],
+        // [text][member], else empty
+        std::vector<quicked_panel_hit_t> panel_hits;
+        std::vector<int32_t> panel_score, panel_end;
+        int32_t panel_members = 0;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -121,6 +127,8 @@ struct quicked_batch {
     int run_tags = 0;
     bool search_run = false;                      // the run in progress is a search run: its results carry locations (reset_host_results)
     bool hits_run = false;                        // ... an all-occurrences run: its results carry occurrence lists instead
+    int panel_run = 0;                            // ... a panel run: the panel's size (its results carry panel hits instead), 0: not one
+    bool panel_matrix = false;                    // ... with QUICKED_PANEL_MATRIX
     // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
     bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)
@@ -202,7 +210,10 @@ struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 // max_hits > 0: every occurrence within the bound (quicked_batch_run_search_all), at most max_hits stored per pair; fetch only
 // eq: the run's equality -- 0 the library's, 1 QUICKED_SEARCH_IUPAC (both sequences as base sets), 2 QUICKED_SEARCH_IUPAC_PATTERN
 // (the pattern as base sets, a text byte that is not A C G T U the empty set); mode is the base mode, without the flags
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; };
+// panel != nullptr: a panel run (quicked_batch_run_panel): the batch's texts against the panel's members; max_dist then has one
+// value per MEMBER; fetch only
+struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; const int32_t* len; bool matrix; };
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; };
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr, const SearchRun* sr = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "qe_batch.h"
+#include "qe_panel.h"
 
 #define QE_API extern "C" __attribute__((visibility("default")))
 
@@ -292,6 +293,51 @@ QE_API quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t
     const auto& R = batch->res[batch->vis];
     if (hits && !R.hits.empty()) memcpy(hits, R.hits.data(), R.hits.size() * sizeof(quicked_hit_t));
     if (hit_off) memcpy(hit_off, R.hit_off.data(), ((size_t)batch->n + 1) * sizeof(int64_t));
+    return QUICKED_OK;
+}
+
+// Panel search: the arguments are checked before anything touches the device
+static_assert(sizeof(quicked_panel_hit_t) == 24, "quicked_panel_hit_t is six int32 (k_panel_reduce writes it as such)");
+static_assert((int)QUICKED_PANEL_MAX_PATTERNS == (int)PANEL_MAX_PATTERNS && (int)QUICKED_PANEL_MAX_LEN == (int)PANEL_MAX_LEN, "the panel limits are qe_panel.h's");
+QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
+                                                const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
+                                                int32_t max_dist_all, int sync) {
+    const int eq = search_mode_eq(mode & ~QUICKED_PANEL_MATRIX);
+    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    if (n_patterns < 1 || n_patterns > QUICKED_PANEL_MAX_PATTERNS || !panel_pool || !panel_off || !panel_len) return QUICKED_ERROR;
+    bool too_long = false;
+    for (int32_t p = 0; p < n_patterns; ++p) {
+        if (panel_len[p] <= 0 || (max_dist && max_dist[p] < 0)) return QUICKED_ERROR;
+        too_long = too_long || panel_len[p] > QUICKED_PANEL_MAX_LEN;
+    }
+    PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, (mode & QUICKED_PANEL_MATRIX) != 0};
+    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, 0, eq, &pr}, too_long, sync};
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        // the room for the matrix: a row per text of the batch, the empty ones' included (they read -1)
+        if (x->sr.panel->matrix && B->n * (int64_t)x->sr.panel->n_patterns > ((int64_t)1 << 28)) return QUICKED_ERROR;
+        if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
+        if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
+        if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the results are reduced and read at the run's end
+        quicked_params_t p = quicked_default_params();
+        p.algo = BANDED;
+        p.only_score = true;
+        return run_batch(*B, p, true, nullptr, &x->sr);
+    }, &arg);
+}
+
+QE_API quicked_status_t quicked_batch_panel_results(quicked_batch_t* batch, quicked_panel_hit_t* out) {
+    if (!batch || !out || batch->n == 0 || batch->res[batch->vis].panel_hits.size() != (size_t)batch->n) return QUICKED_ERROR;
+    memcpy(out, batch->res[batch->vis].panel_hits.data(), (size_t)batch->n * sizeof(quicked_panel_hit_t));
+    return QUICKED_OK;
+}
+
+QE_API quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* scores, int32_t* text_ends) {
+    if (!batch || batch->n == 0) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (R.panel_hits.size() != (size_t)batch->n || R.panel_members < 1 || R.panel_score.size() != (size_t)batch->n * (size_t)R.panel_members) return QUICKED_ERROR;
+    if (scores) memcpy(scores, R.panel_score.data(), R.panel_score.size() * sizeof(int32_t));
+    if (text_ends) memcpy(text_ends, R.panel_end.data(), R.panel_end.size() * sizeof(int32_t));
     return QUICKED_OK;
 }
 

@@ -34,6 +34,7 @@
 #include "qe_batch.h"
 #include "qe_bounded.h"
 #include "qe_search.h"
+#include "qe_panel.h"
 #include "qe_tags.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
 // without a GPU names tests/native/hip_stub/qe_kernels_stub.h here -- tests/test_host_sanitizers.py; never set in the product)
@@ -706,7 +707,8 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     for (const auto& q : C.pool_a2) pools_held += q.cap;
     size_t need_mat = B.last_mat_bytes, need_fixed = B.last_fixed_bytes;
     int need_groups = B.last_groups;
-    if (sr) need_fixed += search_iupac_bytes(B, sr->eq, sr->mode);      // a flagged search run packs its four planes into its pool
+    if (sr && sr->panel) need_fixed += panel_fixed_bytes(B, C, *sr);    // a panel run: its panel, partials, start-pass arrays, matrix, four-plane texts
+    else if (sr) need_fixed += search_iupac_bytes(B, sr->eq, sr->mode);      // a flagged search run packs its four planes into its pool
     if (need_groups == 0 && !p.only_score && p.algo != WINDOWED) {
         // first CIGAR run of this batch: leaves as wide as the bandwidth cutoff allows (QuickEd's bounds are tighter)
         for (int64_t i = 0; i < B.n; ++i) {
@@ -805,8 +807,10 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     }
     B.only_score_run = p.only_score;
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
-    B.search_run = sr != nullptr && sr->max_hits == 0;
+    B.search_run = sr != nullptr && sr->max_hits == 0 && !sr->panel;
     B.hits_run = sr != nullptr && sr->max_hits > 0;
+    B.panel_run = (sr && sr->panel) ? sr->panel->n_patterns : 0;
+    B.panel_matrix = sr && sr->panel && sr->panel->matrix;
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -858,14 +862,34 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     std::vector<int32_t> beyond;
     TaskList L, Ld, Lg;
     SearchLists SLs;
-    if (sr) search_pairs(B, *sr, SLs); else if (bd) bounded_pairs(B, *bd, beyond, Ld, Lg); else L = all_pairs(B, p);
+    bool no_panel_task = true;
+    if (sr && sr->panel) { for (int64_t i = 0; i < B.n && no_panel_task; ++i) no_panel_task = B.t_len[(size_t)i] == 0; }
+    else if (sr) search_pairs(B, *sr, SLs); else if (bd) bounded_pairs(B, *bd, beyond, Ld, Lg); else L = all_pairs(B, p);
     QE_TRACE_POINT("task list");
     bool no_search_task = true;
     for (const TaskList& l : SLs.L) no_search_task = no_search_task && l.pair.empty();
-    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
+    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task && no_panel_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
     StageResult R;
 
-    if (sr && sr->max_hits > 0) {
+    if (sr && sr->panel) {
+        // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every
+        // {d, text_end}, in one read-back
+        enter_a();
+        const PanelOut PO = run_search_panel(B, C, *sr);
+        const size_t n = (size_t)B.n, nk = n * (size_t)sr->panel->n_patterns;
+        std::vector<u32> adv, adv2;
+        {
+            FetchBatch fb(C);
+            fb.add_bytes(B.wr->panel_hits.data(), PO.d_hits, n * sizeof(quicked_panel_hit_t));
+            fb.add(adv, (const u32*)PO.d_adv, PO.text.size());
+            if (PO.d_adv2) fb.add(adv2, (const u32*)PO.d_adv2, PO.text.size());
+            if (PO.d_mscore) { fb.add_bytes(B.wr->panel_score.data(), PO.d_mscore, nk * sizeof(int32_t)); fb.add_bytes(B.wr->panel_end.data(), PO.d_mend, nk * sizeof(int32_t)); }
+            fb.sync();
+        }
+        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
+        for (const int32_t pr : PO.text) if (pr >= 0) { B.wr->score[pr] = B.wr->panel_hits[(size_t)pr].score; B.wr->status[pr] = QUICKED_OK; }
+        ret = QUICKED_OK;
+    } else if (sr && sr->max_hits > 0) {
         // All-occurrences run (sync only): found / smallest score / offsets per pair and the stored occurrences, already in the
         // order of the pairs, in one read-back
         enter_a();
@@ -1116,6 +1140,7 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     C.phase_u();
     B.search_run = F.search;
     B.hits_run = false;                        // (all-occurrences runs are never queued)
+    B.panel_run = 0; B.panel_matrix = false;   // (nor are panel runs)
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {

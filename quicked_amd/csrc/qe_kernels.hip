@@ -31,6 +31,7 @@
 #include "qe_types.h"
 #include "qe_bounded.h"
 #include "qe_search.h"
+#include "qe_panel.h"
 #include "qe_tags.h"
 #include "qe_check.h"
 
@@ -1604,6 +1605,65 @@ __global__ __launch_bounds__(256) void k_hits_finish(int64_t total, const int32_
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
     hits[3 * j] = o_start[j] < 0 ? -1 : hits[3 * j] + o_start[j];
+}
+
+// ===========================================================================
+// Panel search (qe_panel.h; quicked_batch_run_panel): every text of the batch against one shared set of
+// patterns.  One lane per text, 64 texts per wave in the batch's length order; blockIdx.y is the panel slice, and the wave
+// loops over the members of its slice (panel_text).  The member index comes from blockIdx and kernel arguments only, so
+// everything about a member -- length, bound, block count, row bit, the plane words -- is wave-uniform and read through
+// uniform addresses: it lives in scalar registers, and the dispatch on the block count is a uniform branch.  A lane holds
+// its text's chunk words, {Pv, Mv, S} of up to four blocks, the SearchLane and the keeper.  A member's chunk loop is each
+// lane's own (search_run): the wave leaves it at its longest text, or when every lane has its answer.  Written: one partial
+// keeper per (slice, text), [field][slice][slot] so that a wave's stores are contiguous rows, and with the matrix wanted every
+// member's {score, end}.  No workspace, no task list.
+// ===========================================================================
+#define QE_HAVE_K_SEARCH_PANEL 1
+template <class Eq>
+__global__ __launch_bounds__(256) void k_search_panel(PanelArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    const bool matrix = A.m_score != nullptr && pair >= 0;
+    int32_t* ms = matrix ? A.m_score + (int64_t)pair * A.n_members : nullptr;
+    int32_t* me = matrix ? A.m_end + (int64_t)pair * A.n_members : nullptr;
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelKeeper keep;
+    keep.init();
+    u32 steps = 0;
+    panel_text<Eq>(P, p0, p1, tp, n, A.mode, keep, steps, ms, me);
+    if (pair >= 0) panel_store_part(A, nslices, slice, slot, keep, steps);
+}
+template __global__ void k_search_panel<SearchEq3>(PanelArgs);
+template __global__ void k_search_panel<SearchEqIupac>(PanelArgs);
+
+// The panel's three planes for a PACKED batch: k_pack's base codes are A 0, C 1, T 2, G 3 (two bits of the ASCII byte), the wire
+// formats' A 0, C 1, G 2, T 3 -- within a batch either is as good, but a panel packed from ASCII meets texts that came as wire
+// words.  Code bit 0 of every base with code bit 1 set is flipped; a not-ACGT base has both bits zero and stays.  One thread
+// per 64-base row.
+__global__ __launch_bounds__(256) void k_panel_wire_codes(u64* __restrict__ planes, int64_t rows) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < rows) planes[3 * r] ^= planes[3 * r + 1];
+}
+
+// one thread per text slot: the slices' keepers merged (any grouping gives the same two keys: PanelKeeper::merge), the
+// text's quicked_panel_hit_t, and -- INFIX -- its task of the start pass (PanelReduceArgs)
+__global__ __launch_bounds__(256) void k_panel_reduce(PanelReduceArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_reduce_slot(A, t);
+}
+// the start pass's o_start is relative to the best member's window
+__global__ __launch_bounds__(256) void k_panel_finish(int nslots, const int32_t* __restrict__ text, const int32_t* __restrict__ o_pair,
+                                                      const int32_t* __restrict__ o_start, int32_t* __restrict__ hits) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < nslots) panel_finish_slot(t, text, o_pair, o_start, hits);
 }
 
 

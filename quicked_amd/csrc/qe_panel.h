@@ -1,0 +1,169 @@
+// qe_panel.h -- panel search: every text of a batch against one shared set of patterns (quicked_batch_run_panel; DESIGN.md
+// 4.14).  Plain C++ with no HIP dependency, like qe_search.h: k_search_panel (qe_kernels.hip) runs it one lane per text, the
+// host stand-ins of the stub build run it text by text, and the CPU suite compiles the very same source with g++
+// (tests/native/search_panel_cpu.cpp) and checks it against the per-pair brute force (tests/panel_lib.py).
+//
+// The definition.  Per text and panel member p, {d, text_end} is what qe_search.h defines for that pattern against that text
+// (mode, equality, the bound clamped to m); d > bound: p is beyond for this text.  The members within their bound are ordered
+// by the key (score, panel index), ascending: the smallest is the text's best, the smallest of the others its runner-up.
+//
+// The keeper holds the two smallest keys seen.  take() compares keys, never arrival order, and merge() takes the two smallest
+// of the union of two keepers -- the runner-up of a keeper can never be the best of a union that holds that keeper's best --
+// so merging is associative and commutative: a panel may be cut into slices that are searched in any order and merged in any
+// grouping.
+//
+// Why one lane per text.  Everything about a member is the same for every text: its planes, length, block count, row bit
+// and bound are wave-uniform, read through uniform addresses (scalar registers on the device), and the dispatch on the
+// block count is a uniform branch.  A lane keeps the text side only: the chunk's words, {Pv, Mv, S} of up to four blocks,
+// the SearchLane and the keeper.
+#pragma once
+#include <stdint.h>
+
+#include "qe_search.h"
+
+namespace qe {
+
+enum : int { PANEL_MAX_PATTERNS = 4096, PANEL_MAX_LEN = 256 };                   // QUICKED_PANEL_MAX_PATTERNS / _MAX_LEN
+
+struct PanelKeeper {
+    int32_t p1, s1, e1;      // the smallest key (score s1, member p1) and that member's text_end; p1 < 0: none
+    int32_t p2, s2;          // the smallest key among the others; p2 < 0: none
+    QE_S_HD void init() { p1 = -1; s1 = -1; e1 = -1; p2 = -1; s2 = -1; }
+    static QE_S_HD bool less(int32_t sa, int32_t pa, int32_t sb, int32_t pb) { return sa < sb || (sa == sb && pa < pb); }
+    // member p is within its bound at distance `score`, ending at `end` (p < 0: nothing)
+    QE_S_HD void take(int32_t p, int32_t score, int32_t end) {
+        // (selects, not branches around stores: the five fields stay five registers on the device)
+        const bool first = p >= 0 && (p1 < 0 || less(score, p, s1, p1));
+        const bool second = p >= 0 && !first && (p2 < 0 || less(score, p, s2, p2));
+        p2 = first ? p1 : (second ? p : p2); s2 = first ? s1 : (second ? score : s2);
+        p1 = first ? p : p1; s1 = first ? score : s1; e1 = first ? end : e1;
+    }
+    QE_S_HD void merge(const PanelKeeper& o) { take(o.p1, o.s1, o.e1); take(o.p2, o.s2, -1); }
+};
+
+// The panel as a pass reads it: member p has len[p] bases, the caller's bound bound[p] (>= 0; clamped to len[p] by
+// search_lane_init) and its planes -- Eq::W words per 64 bases, two rows of zeros behind -- at word Eq::offset(off[p]) of pl
+// (off: three-plane word offsets, as a batch's)
+struct PanelView {
+    const uint64_t* pl;
+    const int64_t* off;
+    const int32_t* len;
+    const int32_t* bound;
+};
+
+// one member of NB blocks at the most against one text (n columns from the start of its planes tp): the register form
+template <int NB, class Eq>
+QE_S_HD void panel_member(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int mode, int32_t& score, int32_t& end, uint32_t& steps) {
+    SearchLane L;
+    search_lane_init(L, m, n, mode, bound, 0);
+    SearchRegStore<NB, Eq> R;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.load(pp, m);
+    search_run<NB>(R, L, tp, 0);
+    search_answer(L, score, end);
+    steps += L.steps;
+}
+
+// One text (planes tp, n >= 0 columns) against the members [p0, p1): the keeper takes every member within its bound;
+// m_score / m_end (null: not kept) get every member's {d or -1, text_end or -1} at index p; steps: block steps, added to
+template <class Eq>
+QE_S_HD void panel_text(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelKeeper& keep, uint32_t& steps,
+                        int32_t* m_score, int32_t* m_end) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        int32_t score = -1, end = -1;
+        if (nb <= 1) panel_member<1, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        else if (nb == 2) panel_member<2, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        if (m_score) { m_score[p] = score; m_end[p] = end; }
+        keep.take(score >= 0 ? p : -1, score, end);
+    }
+}
+
+// The start-pass task of a text's best member (INFIX): member of m bases found at distance `score` ending at `end` in a text
+// of n bases.  The pass -- k_search<4, Eq> in PREFIX mode with SEARCH_LARGEST_END over the member's reversed planes and the
+// text's reversed planes, SearchArgs::in_score = score, in_end -- walks the window of min(end, m + score) columns that ends
+// at text_end and leaves o_start relative to it: text_start = base + o_start
+QE_S_HD void panel_start_task(int m, int n, int end, int score, int32_t& task_n, int32_t& in_end, int32_t& base) {
+    search_hit_task(m, n, end, score, task_n, in_end, base);
+}
+
+// ---- the kernels' argument blocks, and what the kernels and their host stand-ins do per text slot
+// Panel search (k_search_panel<Eq>, qe_panel.h; quicked_batch_run_panel): one lane per text, grid = text groups x panel slices.
+// Text slot t (nslots of them, a multiple of 64) is pair text[t] of the batch (-1: an empty slot); slice s searches the members
+// [s per_slice, min(n_members, (s + 1) per_slice)).  The panel: member p has m_len[p] bases, bound m_bound[p] and its planes at
+// word Eq::offset(m_off[p]) of pl_m (three-plane offsets, as a batch's).  Per (slice, slot) one partial keeper and the lane's
+// block steps: field f of {p1, s1, e1, p2, s2, steps} at part[(f nslices + s) nslots + t].  m_score / m_end (null: not kept):
+// every member's {d or -1, text_end or -1} at [pair n_members + p].
+struct PanelArgs {
+    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
+    int32_t n_members, per_slice;
+    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
+    int32_t nslots;  const int32_t* text;
+    int32_t mode;                            // SEARCH_PREFIX / SEARCH_INFIX
+    int32_t* part;
+    int32_t* m_score;  int32_t* m_end;
+};
+// One thread per text slot (k_panel_reduce): the slices' keepers merged into hits[pair] = quicked_panel_hit_t as {pattern,
+// score, text_start, text_end, second_pattern, second_score} and o_adv[t] = the slot's block steps.  text_start: PREFIX 0;
+// INFIX the base of the start pass's window, and the slot's task of that pass (panel_start_task) goes to o_pair / o_m / o_n /
+// o_score / o_end [t] (o_pair -1: no member within its bound) with the offset of the best member's planes at o_plp_off[pair];
+// k_panel_finish then adds the pass's o_start (or leaves -1).
+struct PanelReduceArgs {
+    int32_t nslots, nslices, infix;
+    const int32_t* text;  const int32_t* part;
+    const int32_t* m_len;  const int64_t* m_off;  const int32_t* t_len;
+    int32_t* hits;  uint32_t* o_adv;
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;  int64_t* o_plp_off;
+};
+
+// a lane's partial keeper and block steps to their places: field f at part[(f nslices + slice) nslots + slot]
+QE_S_HD void panel_store_part(const PanelArgs& A, int nslices, int slice, int slot, const PanelKeeper& keep, uint32_t steps) {
+    const int64_t stride = (int64_t)nslices * A.nslots;
+    int32_t* q = A.part + (int64_t)slice * A.nslots + slot;
+    q[0] = keep.p1; q[stride] = keep.s1; q[2 * stride] = keep.e1; q[3 * stride] = keep.p2; q[4 * stride] = keep.s2;
+    q[5 * stride] = (int32_t)steps;
+}
+// k_panel_reduce's slot t: the slices' keepers merged (any grouping gives the same two keys), the text's quicked_panel_hit_t
+// and -- INFIX -- its task of the start pass
+QE_S_HD void panel_reduce_slot(const PanelReduceArgs& A, int t) {
+    const int pair = A.text[t];
+    if (A.infix) A.o_pair[t] = -1;
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots;
+    PanelKeeper keep;
+    keep.init();
+    uint32_t steps = 0;
+    for (int s = 0; s < A.nslices; ++s) {
+        const int32_t* q = A.part + (int64_t)s * A.nslots + t;
+        PanelKeeper o;
+        o.p1 = q[0]; o.s1 = q[stride]; o.e1 = q[2 * stride]; o.p2 = q[3 * stride]; o.s2 = q[4 * stride];
+        keep.merge(o);
+        steps += (uint32_t)q[5 * stride];
+    }
+    int32_t* h = A.hits + 6 * (int64_t)pair;
+    int32_t start = keep.p1 >= 0 ? 0 : -1;
+    if (A.infix && keep.p1 >= 0) {
+        const int m = A.m_len[keep.p1];
+        int32_t task_n, in_end, base;
+        panel_start_task(m, A.t_len[pair], keep.e1, keep.s1, task_n, in_end, base);
+        start = base;
+        A.o_pair[t] = pair; A.o_m[t] = m; A.o_n[t] = task_n; A.o_score[t] = keep.s1; A.o_end[t] = in_end;
+        A.o_plp_off[pair] = A.m_off[keep.p1];
+    }
+    h[0] = keep.p1; h[1] = keep.s1; h[2] = start; h[3] = keep.e1; h[4] = keep.p2; h[5] = keep.s2;
+    A.o_adv[t] = steps;
+}
+// k_panel_finish's slot t: the start pass's o_start is relative to the best member's window
+QE_S_HD void panel_finish_slot(int t, const int32_t* text, const int32_t* o_pair, const int32_t* o_start, int32_t* hits) {
+    const int pair = text[t];
+    if (pair < 0 || o_pair[t] < 0) return;
+    int32_t* h = hits + 6 * (int64_t)pair;
+    h[2] = o_start[t] < 0 ? -1 : h[2] + o_start[t];
+}
+
+}  // namespace qe

@@ -1401,6 +1401,230 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
     return O;
 }
 
+// ---------------------------------------------------------------------------
+// Panel runs (quicked_batch_run_panel; qe_panel.h): every text of the batch against one shared set of patterns.
+// ---------------------------------------------------------------------------
+#ifndef QE_HAVE_K_SEARCH_PANEL
+// a kernels header without them (the host-only build's stand-ins): the per-slot functions of qe_panel.h that the device
+// kernels call, run slot by slot and slice by slice with the arguments of the device forms
+template <class Eq>
+static void k_search_panel(PanelArgs A) {
+    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    for (int slice = 0; slice < nslices; ++slice)
+        for (int slot = 0; slot < A.nslots; ++slot) {
+            const int pair = A.text[slot];
+            if (pair < 0) continue;
+            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
+            PanelKeeper keep;
+            keep.init();
+            u32 steps = 0;
+            panel_text<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, keep, steps,
+                           A.m_score ? A.m_score + (int64_t)pair * A.n_members : nullptr, A.m_score ? A.m_end + (int64_t)pair * A.n_members : nullptr);
+            panel_store_part(A, nslices, slice, slot, keep, steps);
+        }
+}
+static void k_panel_wire_codes(u64* planes, int64_t rows) { for (int64_t r = 0; r < rows; ++r) planes[3 * r] ^= planes[3 * r + 1]; }
+static void k_panel_reduce(PanelReduceArgs A) { for (int t = 0; t < A.nslots; ++t) panel_reduce_slot(A, t); }
+static void k_panel_finish(int nslots, const int32_t* text, const int32_t* o_pair, const int32_t* o_start, int32_t* hits) {
+    for (int t = 0; t < nslots; ++t) panel_finish_slot(t, text, o_pair, o_start, hits);
+}
+#endif
+
+// Slices of the panel, chosen on the host: one while the text groups alone fill the chip (two waves on every SIMD); else enough
+// that groups x slices reach about twice the resident wave slots -- the last waves of a launch then have company --, never more
+// than the panel has members.  QE_PANEL_SLICES forces a count (clamped to 1 .. K).
+static int panel_slices(const Context& C, size_t ngroups, int K) {
+    if (sw_set(Sw::PanelSlices)) return (int)std::max<long long>(1, std::min<long long>(K, sw_ll(Sw::PanelSlices)));
+    const size_t slots = chip(C.device).slots2();
+    if (ngroups >= slots) return 1;
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)K, (2 * slots + ngroups - 1) / std::max<size_t>(1, ngroups)));
+}
+// the three-plane words of the panel's members, two rows of zeros behind each (k_pack's layout)
+static size_t panel_plane_words(const PanelRun& pr) {
+    size_t w = 0;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) w += 3 * ((size_t)(pr.len[p] + 63) / 64 + 2);
+    return w;
+}
+// what a panel run takes from its pool (the planner's fixed needs): the panel's bytes, tables and planes (forward and, INFIX,
+// reversed), the slice partials at the most slices the host would choose, the start-pass arrays, the matrix, and a flagged
+// run's four-plane words of the texts
+static size_t panel_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    size_t texts = 0;                                             // the slots are the non-empty texts', as in run_search_panel
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    const size_t n = (size_t)B.n, K = (size_t)pr.n_patterns, nslots = (texts + 63) / 64 * 64, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
+    size_t pool = 0;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
+    size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
+    b += 6 * (size_t)panel_slices(C, nslots / 64, pr.n_patterns) * nslots * sizeof(int32_t);
+    b += nslots * 4 + n * 24 + nslots * 8 * 4 + n * 8;
+    if (pr.matrix) b += 2 * n * K * sizeof(int32_t);
+    if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
+    return b + 16 * 512;
+}
+// The text planes a panel pass reads: the batch's own under the library's equality; a flagged run packs the four membership
+// planes of the TEXTS into its pool, as search_planes does for both sides -- the batch's patterns play no part
+static const u64* panel_text_planes(quicked_batch& B, Context& C, int eq, bool reversed) {
+    if (!eq) return pair_view(B, reversed).pl_t;
+    if (B.packed && reversed && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    const PairView v = pair_view(B, reversed);
+    u64* pl_t = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_t_words) + 8);
+    const int blocks = (int)((B.n + 3) / 4);
+    if (B.packed) {
+        IupacPlanesArgs a;
+        a.nseq = (int32_t)B.n;
+        a.src = v.pl_t; a.dst = pl_t; a.pl_off = B.d_plt_off; a.len = B.d_t_len; a.n_empty = eq == 2 ? 1 : 0;
+        hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+    } else {
+        IupacPackArgs a;
+        a.nseq = (int32_t)B.n; a.reverse = reversed ? 1 : 0;
+        a.asc = B.d_asc_t; a.asc_off = B.d_t_off; a.len = B.d_t_len; a.planes = pl_t; a.pl_off = B.d_plt_off; a.acgt_only = eq == 2 ? 1 : 0;
+        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    return pl_t;
+}
+
+// The run: the panel's bytes and tables go up in one block and are packed on the device by the batch's own packers (k_pack
+// with null flags, and k_panel_wire_codes behind it where the batch is a packed one; k_pack_iupac for a flagged run), forward
+// and -- INFIX -- reversed; k_search_panel over text groups x slices
+// leaves the partial keepers; k_panel_reduce merges them into the texts' results and, INFIX, the tasks of the start pass,
+// which is the unchanged k_search<4, Eq> in its start-pass form (PREFIX, SEARCH_LARGEST_END, SearchArgs::in_score) over a
+// PairView whose pattern side is the reversed panel planes with a per-text offset array: every member has at most four blocks
+// and pattern_rows gives zero planes for the absent ones.  No per-pair task list: the one array that goes up per text is its
+// slot's pair index.  Both passes are timed as kind 0.
+struct PanelOut {
+    std::vector<int32_t> text;                     // slot -> pair, -1 in the padding
+    int32_t *d_hits = nullptr, *d_mscore = nullptr, *d_mend = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
+};
+static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    const int K = pr.n_patterns, eq = sr.eq;
+    const bool infix = sr.mode == SEARCH_INFIX;
+    PanelOut O;
+    for (int64_t i = 0; i < B.n; ++i) { const int p = B.order[(size_t)i]; if (B.t_len[(size_t)p] > 0) O.text.push_back(p); }
+    if (O.text.empty()) return O;
+    while (O.text.size() % 64) O.text.push_back(-1);
+    const size_t n = (size_t)B.n, nslots = O.text.size(), ngroups = nslots / 64;
+    // ---- the panel: one host block {asc_off | pl_off | len | bound | bytes}, one upload
+    const size_t words3 = panel_plane_words(pr);
+    size_t pool_bytes = 0;
+    for (int p = 0; p < K; ++p) pool_bytes += (size_t)pr.len[p];
+    const size_t tab_bytes = (size_t)K * (8 + 8 + 4 + 4), blk_bytes = (tab_bytes + pool_bytes + 15) & ~(size_t)15;
+    static thread_local std::vector<uint8_t> host;
+    host.assign(blk_bytes, 0);
+    int64_t* h_asc_off = (int64_t*)host.data();
+    int64_t* h_pl_off = h_asc_off + K;
+    int32_t* h_len = (int32_t*)(h_pl_off + K);
+    int32_t* h_bound = h_len + K;
+    uint8_t* h_pool = (uint8_t*)(h_bound + K);
+    {
+        int64_t at = 0, w = 0;
+        for (int p = 0; p < K; ++p) {
+            h_asc_off[p] = at; h_pl_off[p] = w; h_len[p] = pr.len[p];
+            h_bound[p] = sr.max_dist ? sr.max_dist[p] : sr.max_dist_all;
+            memcpy(h_pool + at, pr.pool + pr.off[p], (size_t)pr.len[p]);
+            at += pr.len[p]; w += 3 * ((int64_t)(pr.len[p] + 63) / 64 + 2);
+        }
+    }
+    uint8_t* d_blk = C.scratch_p->take<uint8_t>(blk_bytes + 16);
+    h2d_bytes(d_blk, host.data(), blk_bytes, C.stream);
+    const int64_t* d_asc_off = (const int64_t*)d_blk;
+    const int64_t* d_pl_off = d_asc_off + K;
+    const int32_t* d_len = (const int32_t*)(d_pl_off + K);
+    const int32_t* d_bound = d_len + K;
+    const uint8_t* d_pool = (const uint8_t*)(d_bound + K);
+    int32_t* d_text = C.scratch_p->take<int32_t>(nslots);
+    h2d(d_text, O.text, C.stream);
+    const size_t plane_words = (size_t)(eq ? iupac_offset((int64_t)words3) : (int64_t)words3) + 8;
+    auto panel_planes = [&](bool reversed) {
+        u64* pl = C.scratch_p->take<u64>(plane_words);
+        const int blocks = (K + 3) / 4;
+        if (eq) {
+            IupacPackArgs a;
+            a.nseq = K; a.reverse = reversed ? 1 : 0; a.acgt_only = 0;
+            a.asc = d_pool; a.asc_off = d_asc_off; a.len = d_len; a.planes = pl; a.pl_off = d_pl_off;
+            hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+        } else {
+            PackArgs a;
+            a.nseq = K; a.reverse = reversed ? 1 : 0; a.flags = nullptr;
+            a.asc = d_pool; a.asc_off = d_asc_off; a.len = d_len; a.planes = pl; a.pl_off = d_pl_off;
+            hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
+            // a packed batch's texts carry the wire formats' base codes, not k_pack's
+            if (B.packed) hipLaunchKernelGGL(k_panel_wire_codes, dim3((unsigned)((words3 / 3 + 255) / 256)), dim3(256), 0, C.stream, pl, (int64_t)(words3 / 3));
+        }
+        HIP_CHECK(hipGetLastError());
+        return (const u64*)pl;
+    };
+    // ---- the forward pass
+    const int want = panel_slices(C, ngroups, K), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    PanelArgs a{};
+    a.pl_m = panel_planes(false); a.m_off = d_pl_off; a.m_len = d_len; a.m_bound = d_bound;
+    a.n_members = K; a.per_slice = per_slice;
+    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
+    a.nslots = (int32_t)nslots; a.text = d_text; a.mode = sr.mode;
+    a.part = C.scratch_p->take<int32_t>(6 * (size_t)nslices * nslots);
+    if (pr.matrix) {
+        O.d_mscore = C.scratch_p->take<int32_t>(2 * n * (size_t)K);
+        O.d_mend = O.d_mscore + n * (size_t)K;
+        HIP_CHECK(hipMemsetAsync(O.d_mscore, 0xFF, 2 * n * (size_t)K * sizeof(int32_t), C.stream));
+        a.m_score = O.d_mscore; a.m_end = O.d_mend;
+    }
+    O.d_hits = C.scratch_p->take<int32_t>(6 * n);
+    HIP_CHECK(hipMemsetAsync(O.d_hits, 0xFF, 6 * n * sizeof(int32_t), C.stream));
+    O.d_adv = C.scratch_p->take<u32>(nslots);
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nslots * sizeof(u32), C.stream));
+    auto* ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    {
+        // four text groups per workgroup, one per SIMD of its CU, and launch_groups' claim on the CU's LDS: at most two of
+        // these workgroups share a CU, whichever slices they belong to
+        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
+        if (eq) hipLaunchKernelGGL(k_search_panel<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+        else hipLaunchKernelGGL(k_search_panel<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    // ---- the reduction, and the start pass's tasks
+    PanelReduceArgs r{};
+    r.nslots = (int32_t)nslots; r.nslices = nslices; r.infix = infix ? 1 : 0;
+    r.text = d_text; r.part = a.part; r.m_len = d_len; r.m_off = d_pl_off; r.t_len = B.d_t_len;
+    r.hits = O.d_hits; r.o_adv = O.d_adv;
+    int32_t* o_start = nullptr;
+    if (infix) {
+        int32_t* q = C.scratch_p->take<int32_t>(6 * nslots);
+        r.o_pair = q; r.o_m = q + nslots; r.o_n = q + 2 * nslots; r.o_score = q + 3 * nslots; r.o_end = q + 4 * nslots; o_start = q + 5 * nslots;
+        HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
+        r.o_plp_off = C.scratch_p->take<int64_t>(n);
+        HIP_CHECK(hipMemsetAsync(r.o_plp_off, 0, n * sizeof(int64_t), C.stream));
+        O.d_adv2 = C.scratch_p->take<u32>(nslots);
+        HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nslots * sizeof(u32), C.stream));
+    }
+    hipLaunchKernelGGL(k_panel_reduce, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, r);
+    HIP_CHECK(hipGetLastError());
+    if (!infix) return O;
+    // ---- the start pass: one lane per text over the window that ends at its best member's text_end, reversed
+    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    PairView PV = pair_view(B, true);
+    PV.pl_p = panel_planes(true); PV.pl_p_off = r.o_plp_off;
+    PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = B.d_plt_off;
+    SearchArgs s{};
+    s.P = PV;
+    s.T.ntasks = (int32_t)nslots; s.T.pair = r.o_pair; s.T.m = r.o_m; s.T.n = r.o_n; s.T.cutoff = r.o_score;
+    s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
+    s.in_score = r.o_score; s.in_end = r.o_end; s.o_start = o_start; s.o_adv = O.d_adv2;
+    ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    launch_search(C, eq, 3, s, ngroups);
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    hipLaunchKernelGGL(k_panel_finish, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, (int)nslots, (const int32_t*)d_text,
+                       (const int32_t*)r.o_pair, (const int32_t*)o_start, O.d_hits);
+    HIP_CHECK(hipGetLastError());
+    return O;
+}
+
 // One wave per alignment wherever the strings are more than a few runs long, else one lane per alignment.  Decided before the
 // traceback runs: the wave form wants every task's runs in a stretch of their own (TraceArgs::runs_by_task).  Round 5: the
 // wave form used to be kept for few alignments or very long reads; measured per read length and batch size
@@ -1756,6 +1980,11 @@ static void reset_host_results(quicked_batch& B) {
     if (B.hits_run) { B.wr->found.assign((size_t)B.n, 0); B.wr->hit_off.assign((size_t)B.n + 1, 0); }
     else { B.wr->found.clear(); B.wr->hit_off.clear(); }
     B.wr->hits.clear();
+    static const quicked_panel_hit_t no_panel_hit = {-1, -1, -1, -1, -1, -1};
+    if (B.panel_run) B.wr->panel_hits.assign((size_t)B.n, no_panel_hit); else B.wr->panel_hits.clear();
+    B.wr->panel_members = B.panel_run;
+    if (B.panel_run && B.panel_matrix) { B.wr->panel_score.assign((size_t)B.n * (size_t)B.panel_run, -1); B.wr->panel_end.assign((size_t)B.n * (size_t)B.panel_run, -1); }
+    else { B.wr->panel_score.clear(); B.wr->panel_end.clear(); }
     B.wr->deferred_pairs = 0;
 }
 
