@@ -253,6 +253,44 @@ quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode,
                                          const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all, int sync);
 quicked_status_t quicked_batch_panel_results(quicked_batch_t* batch, quicked_panel_hit_t* out /* n */);
 quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* scores, int32_t* text_ends /* n * n_patterns each, [text][pattern]; either may be NULL */);
+
+/* Panel search, every occurrence: per text, every occurrence of every panel member -- both primers of an amplicon with start and
+ * end, an adapter that occurs twice in a chimeric read, a 5' and a 3' barcode from one panel.
+ *
+ * Texts, the panel, the modes, both IUPAC flags and packed batches are exactly those of quicked_batch_run_panel (the reading of
+ * the fifth symbol of PLANES3 and "the batch's own patterns are ignored" included).  A member's bound is max_dist[p] or
+ * max_dist_all, clamped to m.  For text i and member p the occurrences are exactly those quicked_batch_run_search_all defines
+ * for that pattern against that text with that bound: the valley rule, plateaus, text_start by the best search's rule, 0 for
+ * PREFIX.  A text's occurrences are ordered by (pattern, text_end), ascending.  found[i] is their exact number over all members,
+ * whatever the cap; stored[i] = min(found[i], max_hits), and the stored ones are the first in that order, at
+ * hits[hit_off[i] .. hit_off[i + 1]).  quicked_batch_scores after such a run gives the smallest score among all found
+ * occurrences of the text, stored or not, and -1 with QUICKED_OK when there are none.  An empty text keeps
+ * QUICKED_EMPTY_SEQUENCE and has no occurrences.
+ *
+ * Two consequences (tests/test_gpu_panel_hits.py checks both):
+ *  1. the smallest key (score, pattern) among a text's occurrences, with the first occurrence that has it, is {pattern, score,
+ *     text_start, text_end} of quicked_batch_run_panel for the same panel and bounds; the smallest key among the occurrences of
+ *     the other members is its {second_pattern, second_score};
+ *  2. member p's smallest score, and the first end that has it, is the QUICKED_PANEL_MATRIX entry [i][p].
+ *
+ * QUICKED_ERROR, nothing launched: a NULL batch; a base mode that is not PREFIX or INFIX; both IUPAC flags or any other bit
+ * (QUICKED_PANEL_MATRIX too: it has no meaning here); n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0;
+ * a negative bound; max_hits outside 1 .. 4096; (non-empty texts) x max_hits above 2^26.
+ * QUICKED_UNIMPLEMENTED, nothing queued: a member longer than QUICKED_PANEL_MAX_LEN bases; sync == 0 (the host reads the total
+ * between the passes); a batch configured with check != 0.
+ * The three getters below return QUICKED_ERROR (the total: -1) after any run that was not of this kind;
+ * quicked_batch_panel_results, quicked_batch_panel_matrix, quicked_batch_hits, quicked_batch_hit_counts,
+ * quicked_batch_locations and the CIGAR and tag getters return what they return after any run that produced none of their
+ * data.  Tags are ignored.  Counters [0] and kernel_times slot [0] count both passes, as for the other search runs.  A reload
+ * clears the results.  Not built: queued runs, members over 256 bases, alignments of occurrences. */
+typedef struct { int32_t pattern, text_start, text_end, score; } quicked_panel_occ_t;   /* 16 bytes */
+quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode,
+                                             int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
+                                             const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all,
+                                             int32_t max_hits, int sync);
+quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored /* n each; either may be NULL */);
+int64_t          quicked_batch_panel_hit_total(quicked_batch_t* batch);   /* the sum of stored; -1 after any other run */
+quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_occ_t* hits, int64_t* hit_off /* n + 1 */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -62,6 +62,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_run_bounded", "quicked_batch_run_search", "quicked_batch_locations",
            "quicked_batch_run_search_all", "quicked_batch_hit_counts", "quicked_batch_hit_total", "quicked_batch_hits",
            "quicked_batch_run_panel", "quicked_batch_panel_results", "quicked_batch_panel_matrix",
+           "quicked_batch_run_panel_all", "quicked_batch_panel_hit_counts", "quicked_batch_panel_hit_total", "quicked_batch_panel_hits",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -72,6 +73,7 @@ PANEL_MATRIX = 64                                # OR-ed into a panel run's mode
 PANEL_MAX_PATTERNS, PANEL_MAX_LEN = 4096, 256
 PANEL_HIT_DTYPE = np.dtype([("pattern", np.int32), ("score", np.int32), ("text_start", np.int32), ("text_end", np.int32),
                             ("second_pattern", np.int32), ("second_score", np.int32)])      # quicked_panel_hit_t
+PANEL_OCC_DTYPE = np.dtype([("pattern", np.int32), ("text_start", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_panel_occ_t
 
 _LIB = None
 
@@ -131,6 +133,14 @@ def lib():
     L.quicked_batch_panel_results.restype = C.c_int
     L.quicked_batch_panel_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_panel_matrix.restype = C.c_int
+    L.quicked_batch_run_panel_all.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int]
+    L.quicked_batch_run_panel_all.restype = C.c_int
+    L.quicked_batch_panel_hit_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_panel_hit_counts.restype = C.c_int
+    L.quicked_batch_panel_hit_total.argtypes = [C.c_void_p]
+    L.quicked_batch_panel_hit_total.restype = C.c_int64
+    L.quicked_batch_panel_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.quicked_batch_panel_hits.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -459,6 +469,51 @@ class ResidentBatch:
         if st < 0:
             raise QuickedException(st)
         return sc, te
+
+    def run_panel_all(self, mode, panel, max_dist=None, max_hits=16, sync=True):
+        """quicked_batch_run_panel_all: every occurrence of every panel member in every text, at most max_hits (1 .. 4096) stored
+        per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag).  Sync runs only."""
+        panel = [bytes(p) for p in panel]
+        k = len(panel)
+        pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
+        plen = np.array([len(p) for p in panel], dtype=np.int32)
+        poff = np.zeros(max(k, 1), dtype=np.int64)
+        if k > 1:
+            poff[1:k] = np.cumsum(plen[:-1], dtype=np.int64)
+        if max_dist is None:
+            max_dist = 2**31 - 1
+        if np.ndim(max_dist) == 0:
+            return self._lib.quicked_batch_run_panel_all(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, None, int(max_dist),
+                                                         int(max_hits), 1 if sync else 0)
+        md = np.ascontiguousarray(max_dist, dtype=np.int32)
+        if md.shape != (k,):
+            raise ValueError("max_dist: one bound per panel member")
+        return self._lib.quicked_batch_run_panel_all(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, md.ctypes.data, 0,
+                                                     int(max_hits), 1 if sync else 0)
+
+    def panel_hit_counts(self):
+        """-> (found, stored) int32 arrays of the last all-occurrences panel run: found[i] occurrences of all members in text i
+        (exact whatever the cap), stored[i] = min(found[i], max_hits).  QuickedException after any other run"""
+        found = np.zeros(self.n, dtype=np.int32)
+        stored = np.zeros(self.n, dtype=np.int32)
+        st = self._lib.quicked_batch_panel_hit_counts(self._h, found.ctypes.data, stored.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return found, stored
+
+    def panel_hits(self):
+        """-> (hit_off, hits) of the last all-occurrences panel run: the stored occurrences of text i are
+        hits[hit_off[i]:hit_off[i + 1]], a structured array of PANEL_OCC_DTYPE ordered by (pattern, text_end).
+        QuickedException after any other run"""
+        total = self._lib.quicked_batch_panel_hit_total(self._h)
+        if total < 0:
+            raise QuickedException(QUICKED_ERROR)
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        hits = np.zeros(total, dtype=PANEL_OCC_DTYPE)
+        st = self._lib.quicked_batch_panel_hits(self._h, hits.ctypes.data, off.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return off, hits
 
     def locations(self):
         """-> (text_start, text_end) int32 arrays of the last search run: the located stretch is text[start:end]; -1 / -1 for a

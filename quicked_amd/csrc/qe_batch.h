@@ -110,9 +110,14 @@ struct quicked_batch {
         std::vector<quicked_panel_hit_t> panel_hits;
         std::vector<int32_t> panel_score, panel_end;
         int32_t panel_members = 0;
+        // all-occurrences panel runs (quicked_batch_run_panel_all): panel_found [n] and panel_occ_off [n + 1] after such a run,
+        // else empty; the stored occurrences of text i are panel_occ[panel_occ_off[i] .. panel_occ_off[i + 1])
+        std::vector<int32_t> panel_found;
+        std::vector<int64_t> panel_occ_off;
+        std::vector<quicked_panel_occ_t> panel_occ;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; panel_found.clear(); panel_occ_off.clear(); panel_occ.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -129,6 +134,7 @@ struct quicked_batch {
     bool hits_run = false;                        // ... an all-occurrences run: its results carry occurrence lists instead
     int panel_run = 0;                            // ... a panel run: the panel's size (its results carry panel hits instead), 0: not one
     bool panel_matrix = false;                    // ... with QUICKED_PANEL_MATRIX
+    bool panel_all_run = false;                   // ... an all-occurrences panel run: its results carry the texts' occurrence lists instead
     // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
     bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)
@@ -210,6 +216,7 @@ struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 // max_hits > 0: every occurrence within the bound (quicked_batch_run_search_all), at most max_hits stored per pair; fetch only
 // eq: the run's equality -- 0 the library's, 1 QUICKED_SEARCH_IUPAC (both sequences as base sets), 2 QUICKED_SEARCH_IUPAC_PATTERN
 // (the pattern as base sets, a text byte that is not A C G T U the empty set); mode is the base mode, without the flags
+// panel != nullptr and max_hits > 0: an all-occurrences panel run (quicked_batch_run_panel_all), at most max_hits stored per text;
 // panel != nullptr: a panel run (quicked_batch_run_panel): the batch's texts against the panel's members; max_dist then has one
 // value per MEMBER; fetch only
 struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; const int32_t* len; bool matrix; };

@@ -341,6 +341,58 @@ QE_API quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32
     return QUICKED_OK;
 }
 
+// Panel search, every occurrence: the arguments are checked before anything touches the device
+static_assert(sizeof(quicked_panel_occ_t) == 16, "quicked_panel_occ_t is four int32 (k_panel_hits_expand writes it as such)");
+QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
+                                                    const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
+                                                    int32_t max_dist_all, int32_t max_hits, int sync) {
+    const int eq = search_mode_eq(mode);                                            // (QUICKED_PANEL_MATRIX is "any other bit" here)
+    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
+    if (n_patterns < 1 || n_patterns > QUICKED_PANEL_MAX_PATTERNS || !panel_pool || !panel_off || !panel_len) return QUICKED_ERROR;
+    if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
+    bool too_long = false;
+    for (int32_t p = 0; p < n_patterns; ++p) {
+        if (panel_len[p] <= 0 || (max_dist && max_dist[p] < 0)) return QUICKED_ERROR;
+        too_long = too_long || panel_len[p] > QUICKED_PANEL_MAX_LEN;
+    }
+    PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
+    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr}, too_long, sync};
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        int64_t texts = 0;
+        for (int64_t i = 0; i < B->n; ++i) texts += B->t_len[(size_t)i] > 0;
+        if (texts * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;      // the room for the stored occurrences
+        if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
+        if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
+        if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the start pass is sized from a total the host reads
+        quicked_params_t p = quicked_default_params();
+        p.algo = BANDED;
+        p.only_score = true;
+        return run_batch(*B, p, true, nullptr, &x->sr);
+    }, &arg);
+}
+
+QE_API quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (found) memcpy(found, R.panel_found.data(), (size_t)batch->n * sizeof(int32_t));
+    if (stored) for (int64_t i = 0; i < batch->n; ++i) stored[i] = (int32_t)(R.panel_occ_off[(size_t)i + 1] - R.panel_occ_off[(size_t)i]);
+    return QUICKED_OK;
+}
+
+QE_API int64_t quicked_batch_panel_hit_total(quicked_batch_t* batch) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return -1;
+    return batch->res[batch->vis].panel_occ_off[(size_t)batch->n];
+}
+
+QE_API quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_occ_t* hits, int64_t* hit_off) {
+    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return QUICKED_ERROR;
+    const auto& R = batch->res[batch->vis];
+    if (hits && !R.panel_occ.empty()) memcpy(hits, R.panel_occ.data(), R.panel_occ.size() * sizeof(quicked_panel_occ_t));
+    if (hit_off) memcpy(hit_off, R.panel_occ_off.data(), ((size_t)batch->n + 1) * sizeof(int64_t));
+    return QUICKED_OK;
+}
+
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {
     return guard(batch, [](quicked_batch* B, void*) {
         tl_device = B->device;

@@ -707,7 +707,8 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     for (const auto& q : C.pool_a2) pools_held += q.cap;
     size_t need_mat = B.last_mat_bytes, need_fixed = B.last_fixed_bytes;
     int need_groups = B.last_groups;
-    if (sr && sr->panel) need_fixed += panel_fixed_bytes(B, C, *sr);    // a panel run: its panel, partials, start-pass arrays, matrix, four-plane texts
+    if (sr && sr->panel && sr->max_hits > 0) need_fixed += panel_hits_fixed_bytes(B, C, *sr);      // ... every occurrence: its panel, partials, raw buffer, per-pair arrays
+    else if (sr && sr->panel) need_fixed += panel_fixed_bytes(B, C, *sr);    // a panel run: its panel, partials, start-pass arrays, matrix, four-plane texts
     else if (sr) need_fixed += search_iupac_bytes(B, sr->eq, sr->mode);      // a flagged search run packs its four planes into its pool
     if (need_groups == 0 && !p.only_score && p.algo != WINDOWED) {
         // first CIGAR run of this batch: leaves as wide as the bandwidth cutoff allows (QuickEd's bounds are tighter)
@@ -808,9 +809,10 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     B.only_score_run = p.only_score;
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
     B.search_run = sr != nullptr && sr->max_hits == 0 && !sr->panel;
-    B.hits_run = sr != nullptr && sr->max_hits > 0;
-    B.panel_run = (sr && sr->panel) ? sr->panel->n_patterns : 0;
-    B.panel_matrix = sr && sr->panel && sr->panel->matrix;
+    B.hits_run = sr != nullptr && sr->max_hits > 0 && !sr->panel;
+    B.panel_all_run = sr != nullptr && sr->max_hits > 0 && sr->panel;
+    B.panel_run = (sr && sr->panel && !B.panel_all_run) ? sr->panel->n_patterns : 0;
+    B.panel_matrix = B.panel_run && sr->panel->matrix;
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -871,7 +873,27 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task && no_panel_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
     StageResult R;
 
-    if (sr && sr->panel) {
+    if (sr && sr->panel && sr->max_hits > 0) {
+        // All-occurrences panel run (sync only): found / smallest score / offsets per text and the stored occurrences, already in
+        // the order of the texts and (pattern, text_end) within a text, in one read-back
+        enter_a();
+        const PanelHitsOut HO = run_search_panel_hits(B, C, *sr);
+        const size_t n = (size_t)B.n, nh = (size_t)HO.total;
+        std::vector<int32_t> best; std::vector<u32> adv, adv2;
+        B.wr->panel_occ.resize(nh);
+        {
+            FetchBatch fb(C);
+            fb.add(B.wr->panel_found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
+            fb.add(B.wr->panel_occ_off, (const int64_t*)HO.d_off, n + 1);
+            fb.add(adv, (const u32*)HO.d_adv, HO.text.size());
+            if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
+            fb.add_bytes(B.wr->panel_occ.data(), HO.d_hits, nh * sizeof(quicked_panel_occ_t));
+            fb.sync();
+        }
+        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
+        for (const int32_t pr : HO.text) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+        ret = QUICKED_OK;
+    } else if (sr && sr->panel) {
         // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every
         // {d, text_end}, in one read-back
         enter_a();
@@ -1140,7 +1162,7 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     C.phase_u();
     B.search_run = F.search;
     B.hits_run = false;                        // (all-occurrences runs are never queued)
-    B.panel_run = 0; B.panel_matrix = false;   // (nor are panel runs)
+    B.panel_run = 0; B.panel_matrix = false; B.panel_all_run = false;      // (nor are panel runs)
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {

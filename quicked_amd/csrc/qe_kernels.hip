@@ -1666,6 +1666,51 @@ __global__ __launch_bounds__(256) void k_panel_finish(int nslots, const int32_t*
     if (t < nslots) panel_finish_slot(t, text, o_pair, o_start, hits);
 }
 
+// Every occurrence of every member (qe_panel.h; quicked_batch_run_panel_all): k_search_panel's grid, slots
+// and launch shape, with the all-occurrences scan (SearchHitScanOf over a PanelHitSink) in the place of the keeper.  The member
+// index still comes from blockIdx.y and a loop counter only, so a member's length, bound, block count, row bit and plane words
+// stay wave-uniform and the dispatch on the block count a uniform branch; a lane holds its chunk's text words, {Pv, Mv, S} of
+// up to four blocks, the SearchLane, the scan state and its sink.  The bound stays for the whole text and no lane leaves early.
+// A lane stores only when row m rises out of a valley: one 12-byte record into the stretch of its own (slice, slot), never
+// past max_hits of them; a lane without a text has cap 0 and a null sink.  No workspace, no task list.
+#define QE_HAVE_K_PANEL_HITS 1
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_hits(PanelHitsArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelHitScan H;
+    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    u32 steps = 0;
+    panel_text_hits<Eq>(P, p0, p1, tp, n, A.mode, H, steps);
+    if (pair >= 0) panel_hits_store_part(A, nslices, slice, slot, H, steps);
+}
+template __global__ void k_panel_hits<SearchEq3>(PanelHitsArgs);
+template __global__ void k_panel_hits<SearchEqIupac>(PanelHitsArgs);
+
+// one thread per text slot: the slices' counts merged (PanelHitsCountArgs), then -- behind k_scan_offsets -- the slot's stored
+// occurrences to their places and, INFIX, their tasks of the start pass (PanelHitsExpandArgs)
+__global__ __launch_bounds__(256) void k_panel_hits_count(PanelHitsCountArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_hits_count_slot(A, t);
+}
+__global__ __launch_bounds__(256) void k_panel_hits_expand(PanelHitsExpandArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_hits_expand_slot(A, t);
+}
+__global__ __launch_bounds__(256) void k_panel_hits_finish(int64_t total, const int32_t* __restrict__ o_start, int32_t* __restrict__ hits) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < total) panel_hits_finish_one(j, o_start, hits);
+}
+
 
 // ===========================================================================
 // BandEd score-only, cooperative form: G adjacent lanes share one alignment.

@@ -16,6 +16,9 @@
 // and bound are wave-uniform, read through uniform addresses (scalar registers on the device), and the dispatch on the
 // block count is a uniform branch.  A lane keeps the text side only: the chunk's words, {Pv, Mv, S} of up to four blocks,
 // the SearchLane and the keeper.
+//
+// The second half of the file is the all-occurrences run (quicked_batch_run_panel_all): the same lanes and
+// slices with qe_search.h's valley scan in the keeper's place.
 #pragma once
 #include <stdint.h>
 
@@ -164,6 +167,145 @@ QE_S_HD void panel_finish_slot(int t, const int32_t* text, const int32_t* o_pair
     if (pair < 0 || o_pair[t] < 0) return;
     int32_t* h = hits + 6 * (int64_t)pair;
     h[2] = o_start[t] < 0 ? -1 : h[2] + o_start[t];
+}
+
+// ---- every occurrence of every member (quicked_batch_run_panel_all)
+// Per text and member p the occurrences are what qe_search.h defines for that pattern against that text with that bound
+// (SearchHitScanOf: the valley rule, decided there and nowhere else); a text's occurrences are ordered by (member, text_end).
+// A lane keeps ONE scan across the members of its slice: found, the smallest score and the sink run on, begin() starts a
+// member at column 0 with no candidate.  The sink records the member beside {end, score}: the lane's stretch then holds its
+// slice's occurrences in (member, text_end) order already, and the first `cap` of them.
+struct PanelRawHit { int32_t pattern, end, score; };
+struct PanelHitSink {
+    PanelRawHit* out; int32_t cap, count, member;
+    QE_S_HD void put(int32_t end, int32_t score) {
+        if (count < cap) { out[count] = PanelRawHit{member, end, score}; ++count; }
+    }
+};
+typedef SearchHitScanOf<PanelHitSink> PanelHitScan;
+QE_S_HD void panel_hit_scan_init(PanelHitScan& H, PanelRawHit* out, int32_t cap) {
+    H.prev = 0; H.pend_end = -1; H.pend_val = 0; H.found = 0; H.best = -1;
+    H.sink.out = out; H.sink.cap = cap; H.sink.count = 0; H.sink.member = -1;
+}
+
+// one member of NB blocks at the most against one text: the register form, the bound kept for the whole text, no early exit
+template <int NB, class Eq>
+QE_S_HD void panel_member_hits(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int mode, PanelHitScan& H, uint32_t& steps) {
+    SearchLane L;
+    search_lane_init(L, m, n, mode, bound, 0);
+    SearchRegStore<NB, Eq> R;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.load(pp, m);
+    H.begin(L);
+    search_run_hits<NB>(R, L, H, tp, 0);
+    steps += L.steps;
+}
+
+// One text (planes tp, n >= 0 columns) against the members [p0, p1): every occurrence goes to H's sink, H.found / H.best run
+// on over the members; steps: block steps, added to
+template <class Eq>
+QE_S_HD void panel_text_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelHitScan& H, uint32_t& steps) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        H.sink.member = p;
+        if (nb <= 1) panel_member_hits<1, Eq>(pp, m, bound, tp, n, mode, H, steps);
+        else if (nb == 2) panel_member_hits<2, Eq>(pp, m, bound, tp, n, mode, H, steps);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_hits<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, H, steps);
+    }
+}
+
+// k_panel_hits<Eq>: k_search_panel's grid and slots (PanelArgs above), the members' occurrences instead of the two best keys.
+// Per (slice s, slot t): field f of {found, stored, best, steps} at part[(f nslices + s) nslots + t], and the stored
+// occurrences -- at most max_hits, the slice's first in (member, text_end) order -- as PanelRawHit number i at
+// raw[(s nslots + t) max_hits + i].  A slot without a text writes nothing.
+struct PanelHitsArgs {
+    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
+    int32_t n_members, per_slice;
+    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
+    int32_t nslots;  const int32_t* text;
+    int32_t mode, max_hits;
+    int32_t* part;
+    PanelRawHit* raw;
+};
+// One thread per text slot (k_panel_hits_count): the slices' counts merged into found[pair], best[pair] (the smallest score
+// among all found occurrences, -1: none) and len[pair] = stored - 1, stored = min(found, max_hits) -- what k_scan_offsets adds
+// 1 to --, and o_adv[t] = the slot's block steps.  Every slice stores its first min(found_s, max_hits), so the first
+// `stored` of the slices' stretches in slice order are all there.
+struct PanelHitsCountArgs {
+    int32_t nslots, nslices, max_hits;
+    const int32_t* text;  const int32_t* part;
+    int32_t* found;  int32_t* best;  int32_t* len;  uint32_t* o_adv;
+};
+// One thread per text slot (k_panel_hits_expand): the slot's stored occurrences to hits[off[pair] + i] = quicked_panel_occ_t as
+// {pattern, text_start, text_end, score}, in slice order and in stored order within a slice -- slices are ascending member
+// ranges, so that is (pattern, text_end) order.  text_start: PREFIX 0; INFIX the base of the start pass's window, and
+// occurrence j's task of that pass (search_hit_task) goes to o_pair / o_m / o_n / o_score / o_end [j] with o_pair[j] = j:
+// the pass reads a task's pair only to index its two plane offsets, which are o_plp_off[j] (the member's, into the reversed
+// panel planes) and o_plt_off[j] (the text's).  k_panel_hits_finish then adds the pass's o_start (or leaves -1).
+struct PanelHitsExpandArgs {
+    int32_t nslots, nslices, max_hits, infix;
+    const int32_t* text;  const int32_t* part;  const PanelRawHit* raw;
+    const int64_t* off;
+    const int32_t* m_len;  const int64_t* m_off;  const int32_t* t_len;  const int64_t* t_off;
+    int32_t* hits;
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;  int64_t* o_plp_off;  int64_t* o_plt_off;
+};
+
+QE_S_HD void panel_hits_store_part(const PanelHitsArgs& A, int nslices, int slice, int slot, const PanelHitScan& H, uint32_t steps) {
+    const int64_t stride = (int64_t)nslices * A.nslots;
+    int32_t* q = A.part + (int64_t)slice * A.nslots + slot;
+    q[0] = H.found; q[stride] = H.sink.count; q[2 * stride] = H.best; q[3 * stride] = (int32_t)steps;
+}
+QE_S_HD void panel_hits_count_slot(const PanelHitsCountArgs& A, int t) {
+    const int pair = A.text[t];
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots;
+    int32_t found = 0, stored = 0, best = -1;
+    uint32_t steps = 0;
+    for (int s = 0; s < A.nslices; ++s) {
+        const int32_t* q = A.part + (int64_t)s * A.nslots + t;
+        const int32_t b = q[2 * stride];
+        found += q[0];
+        stored = stored + q[stride] < A.max_hits ? stored + q[stride] : A.max_hits;
+        best = (b >= 0 && (best < 0 || b < best)) ? b : best;
+        steps += (uint32_t)q[3 * stride];
+    }
+    A.found[pair] = found; A.best[pair] = best; A.len[pair] = stored - 1;
+    A.o_adv[t] = steps;
+}
+QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) {
+    const int pair = A.text[t];
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots;
+    const int n = A.t_len[pair];
+    int64_t j = A.off[pair];
+    int left = A.max_hits;
+    for (int s = 0; s < A.nslices && left > 0; ++s) {
+        const int32_t have = A.part[(int64_t)s * A.nslots + t + stride];
+        const PanelRawHit* raw = A.raw + ((int64_t)s * A.nslots + t) * A.max_hits;
+        for (int i = 0; i < have && left > 0; ++i, ++j, --left) {
+            const PanelRawHit h = raw[i];
+            int32_t* o = A.hits + 4 * j;
+            int32_t start = 0;
+            if (A.infix) {
+                const int m = A.m_len[h.pattern];
+                int32_t task_n, in_end, base;
+                search_hit_task(m, n, h.end, h.score, task_n, in_end, base);
+                start = base;
+                A.o_pair[j] = (int32_t)j; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = h.score; A.o_end[j] = in_end;
+                A.o_plp_off[j] = A.m_off[h.pattern]; A.o_plt_off[j] = A.t_off[pair];
+            }
+            o[0] = h.pattern; o[1] = start; o[2] = h.end; o[3] = h.score;
+        }
+    }
+}
+// k_panel_hits_finish's occurrence j: the start pass's o_start is relative to the occurrence's window
+QE_S_HD void panel_hits_finish_one(int64_t j, const int32_t* o_start, int32_t* hits) {
+    hits[4 * j + 1] = o_start[j] < 0 ? -1 : hits[4 * j + 1] + o_start[j];
 }
 
 }  // namespace qe

@@ -274,20 +274,33 @@ QE_S_HD void search_chunk(Store& st, SearchLane& L, uint64_t T0, uint64_t T1, ui
 
 // ---- every occurrence.  Where a lane's occurrences go: {end, score} number i at out[i * stride], the first `cap` of them
 struct SearchHit { int32_t end, score; };
-struct SearchHitSink { SearchHit* out; int64_t stride; int32_t cap, count; };
+struct SearchHitSink {
+    SearchHit* out; int64_t stride; int32_t cap, count;
+    QE_S_HD void put(int32_t end, int32_t score) {
+        if (count < cap) { out[(int64_t)count * stride] = SearchHit{end, score}; ++count; }
+    }
+};
 // what a lane carries besides SearchLane: w of the previous column, the candidate -- the first column of a plateau that was
-// reached by a descent and has not risen yet (end < 0: none) --, the occurrences so far and the smallest score among them
-struct SearchHitScan {
+// reached by a descent and has not risen yet (end < 0: none) --, the occurrences so far and the smallest score among them.
+// Sink: where an occurrence goes, put(end, score) -- the one thing a caller may vary; what an occurrence is is decided here
+// and nowhere else.  A scan may serve several patterns against one text in turn (a panel lane: qe_panel.h): begin() starts a
+// pattern -- column 0, no candidate --, found / best / the sink run on.
+template <class Sink = SearchHitSink>
+struct SearchHitScanOf {
     int32_t prev, pend_end, pend_val, found, best;
-    SearchHitSink sink;
-    QE_S_HD void init(const SearchLane& L, SearchHit* out, int64_t stride, int32_t cap) {
+    Sink sink;
+    QE_S_HD void begin(const SearchLane& L) {
         prev = L.k + 1;                              // column 0: higher than every value that counts
-        pend_end = -1; pend_val = 0; found = 0; best = -1;
+        pend_end = -1; pend_val = 0;
+    }
+    QE_S_HD void init(const SearchLane& L, SearchHit* out, int64_t stride, int32_t cap) {
+        begin(L);
+        found = 0; best = -1;
         sink.out = out; sink.stride = stride; sink.cap = cap; sink.count = 0;
     }
     QE_S_HD void emit() {                            // the row has risen, or the text is over: the candidate is a valley
         if (pend_end < 0) return;
-        if (sink.count < sink.cap) { sink.out[(int64_t)sink.count * sink.stride] = SearchHit{pend_end, pend_val}; ++sink.count; }
+        sink.put(pend_end, pend_val);
         ++found;
         if (best < 0 || pend_val < best) best = pend_val;
         pend_end = -1;
@@ -311,6 +324,7 @@ struct SearchHitScan {
     QE_S_HD void no_row(SearchLane& L) { emit(); prev = L.k + 1; }
     QE_S_HD void finish() { emit(); }                // a plateau that reaches the end of the text counts
 };
+typedef SearchHitScanOf<> SearchHitScan;
 
 // before the first chunk: the live blocks hold column 0
 template <int NBT, class Store>
@@ -376,8 +390,8 @@ QE_S_HD void search_run(Store& st, SearchLane& L, const uint64_t* tp, int64_t tb
 }
 
 // One task of an all-occurrences run: the bound stays, the lane walks the whole text.  flags: 0 or SEARCH_ALL_LIVE
-template <int NBT, class Store>
-QE_S_HD void search_run_hits(Store& st, SearchLane& L, SearchHitScan& H, const uint64_t* tp, int64_t tbit) {
+template <int NBT, class Store, class Scan>
+QE_S_HD void search_run_hits(Store& st, SearchLane& L, Scan& H, const uint64_t* tp, int64_t tbit) {
     search_store_init<NBT>(st, L);
     for (int col0 = 0; col0 < L.n; col0 += 64) {
         const int ncols = L.n - col0 < 64 ? L.n - col0 : 64;

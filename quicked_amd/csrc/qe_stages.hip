@@ -1431,6 +1431,29 @@ static void k_panel_finish(int nslots, const int32_t* text, const int32_t* o_pai
     for (int t = 0; t < nslots; ++t) panel_finish_slot(t, text, o_pair, o_start, hits);
 }
 #endif
+#ifndef QE_HAVE_K_PANEL_HITS
+// ... and of the all-occurrences panel kernels (PanelHitsArgs, PanelHitsCountArgs, PanelHitsExpandArgs)
+template <class Eq>
+static void k_panel_hits(PanelHitsArgs A) {
+    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    for (int slice = 0; slice < nslices; ++slice)
+        for (int slot = 0; slot < A.nslots; ++slot) {
+            const int pair = A.text[slot];
+            if (pair < 0) continue;
+            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
+            PanelHitScan H;
+            panel_hit_scan_init(H, A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits, A.max_hits);
+            u32 steps = 0;
+            panel_text_hits<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, H, steps);
+            panel_hits_store_part(A, nslices, slice, slot, H, steps);
+        }
+}
+static void k_panel_hits_count(PanelHitsCountArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_count_slot(A, t); }
+static void k_panel_hits_expand(PanelHitsExpandArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_expand_slot(A, t); }
+static void k_panel_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) { for (int64_t j = 0; j < total; ++j) panel_hits_finish_one(j, o_start, hits); }
+#endif
 
 // Slices of the panel, chosen on the host: one while the text groups alone fill the chip (two waves on every SIMD); else enough
 // that groups x slices reach about twice the resident wave slots -- the last waves of a launch then have company --, never more
@@ -1499,17 +1522,23 @@ struct PanelOut {
     std::vector<int32_t> text;                     // slot -> pair, -1 in the padding
     int32_t *d_hits = nullptr, *d_mscore = nullptr, *d_mend = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
 };
-static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& sr) {
+// The panel and the text slots on the device, shared by the panel runs: one host block {asc_off | pl_off | len | bound |
+// bytes} in one upload, and slot -> pair in the batch's length order (the non-empty texts, padded to whole waves with -1)
+struct PanelDev {
+    std::vector<int32_t> text;                     // slot -> pair, -1 in the padding; empty: no text to search
+    size_t nslots = 0, ngroups = 0, words3 = 0;
+    const int64_t *d_asc_off = nullptr, *d_pl_off = nullptr;  const int32_t *d_len = nullptr, *d_bound = nullptr;  const uint8_t* d_pool = nullptr;
+    int32_t* d_text = nullptr;
+};
+static PanelDev panel_upload(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
-    const int K = pr.n_patterns, eq = sr.eq;
-    const bool infix = sr.mode == SEARCH_INFIX;
-    PanelOut O;
-    for (int64_t i = 0; i < B.n; ++i) { const int p = B.order[(size_t)i]; if (B.t_len[(size_t)p] > 0) O.text.push_back(p); }
-    if (O.text.empty()) return O;
-    while (O.text.size() % 64) O.text.push_back(-1);
-    const size_t n = (size_t)B.n, nslots = O.text.size(), ngroups = nslots / 64;
-    // ---- the panel: one host block {asc_off | pl_off | len | bound | bytes}, one upload
-    const size_t words3 = panel_plane_words(pr);
+    const int K = pr.n_patterns;
+    PanelDev D;
+    for (int64_t i = 0; i < B.n; ++i) { const int p = B.order[(size_t)i]; if (B.t_len[(size_t)p] > 0) D.text.push_back(p); }
+    if (D.text.empty()) return D;
+    while (D.text.size() % 64) D.text.push_back(-1);
+    D.nslots = D.text.size(); D.ngroups = D.nslots / 64;
+    D.words3 = panel_plane_words(pr);
     size_t pool_bytes = 0;
     for (int p = 0; p < K; ++p) pool_bytes += (size_t)pr.len[p];
     const size_t tab_bytes = (size_t)K * (8 + 8 + 4 + 4), blk_bytes = (tab_bytes + pool_bytes + 15) & ~(size_t)15;
@@ -1531,33 +1560,49 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     }
     uint8_t* d_blk = C.scratch_p->take<uint8_t>(blk_bytes + 16);
     h2d_bytes(d_blk, host.data(), blk_bytes, C.stream);
-    const int64_t* d_asc_off = (const int64_t*)d_blk;
-    const int64_t* d_pl_off = d_asc_off + K;
-    const int32_t* d_len = (const int32_t*)(d_pl_off + K);
-    const int32_t* d_bound = d_len + K;
-    const uint8_t* d_pool = (const uint8_t*)(d_bound + K);
-    int32_t* d_text = C.scratch_p->take<int32_t>(nslots);
-    h2d(d_text, O.text, C.stream);
-    const size_t plane_words = (size_t)(eq ? iupac_offset((int64_t)words3) : (int64_t)words3) + 8;
-    auto panel_planes = [&](bool reversed) {
-        u64* pl = C.scratch_p->take<u64>(plane_words);
-        const int blocks = (K + 3) / 4;
-        if (eq) {
-            IupacPackArgs a;
-            a.nseq = K; a.reverse = reversed ? 1 : 0; a.acgt_only = 0;
-            a.asc = d_pool; a.asc_off = d_asc_off; a.len = d_len; a.planes = pl; a.pl_off = d_pl_off;
-            hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
-        } else {
-            PackArgs a;
-            a.nseq = K; a.reverse = reversed ? 1 : 0; a.flags = nullptr;
-            a.asc = d_pool; a.asc_off = d_asc_off; a.len = d_len; a.planes = pl; a.pl_off = d_pl_off;
-            hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
-            // a packed batch's texts carry the wire formats' base codes, not k_pack's
-            if (B.packed) hipLaunchKernelGGL(k_panel_wire_codes, dim3((unsigned)((words3 / 3 + 255) / 256)), dim3(256), 0, C.stream, pl, (int64_t)(words3 / 3));
-        }
-        HIP_CHECK(hipGetLastError());
-        return (const u64*)pl;
-    };
+    D.d_asc_off = (const int64_t*)d_blk;
+    D.d_pl_off = D.d_asc_off + K;
+    D.d_len = (const int32_t*)(D.d_pl_off + K);
+    D.d_bound = D.d_len + K;
+    D.d_pool = (const uint8_t*)(D.d_bound + K);
+    D.d_text = C.scratch_p->take<int32_t>(D.nslots);
+    h2d(D.d_text, D.text, C.stream);
+    return D;
+}
+// the panel's planes, packed on the device by the batch's own packers: forward, or reversed for a start pass
+static const u64* panel_planes(quicked_batch& B, Context& C, const PanelDev& D, int K, int eq, bool reversed) {
+    const size_t plane_words = (size_t)(eq ? iupac_offset((int64_t)D.words3) : (int64_t)D.words3) + 8;
+    u64* pl = C.scratch_p->take<u64>(plane_words);
+    const int blocks = (K + 3) / 4;
+    if (eq) {
+        IupacPackArgs a;
+        a.nseq = K; a.reverse = reversed ? 1 : 0; a.acgt_only = 0;
+        a.asc = D.d_pool; a.asc_off = D.d_asc_off; a.len = D.d_len; a.planes = pl; a.pl_off = D.d_pl_off;
+        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
+    } else {
+        PackArgs a;
+        a.nseq = K; a.reverse = reversed ? 1 : 0; a.flags = nullptr;
+        a.asc = D.d_pool; a.asc_off = D.d_asc_off; a.len = D.d_len; a.planes = pl; a.pl_off = D.d_pl_off;
+        hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
+        // a packed batch's texts carry the wire formats' base codes, not k_pack's
+        if (B.packed) hipLaunchKernelGGL(k_panel_wire_codes, dim3((unsigned)((D.words3 / 3 + 255) / 256)), dim3(256), 0, C.stream, pl, (int64_t)(D.words3 / 3));
+    }
+    HIP_CHECK(hipGetLastError());
+    return (const u64*)pl;
+}
+static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    const int K = pr.n_patterns, eq = sr.eq;
+    const bool infix = sr.mode == SEARCH_INFIX;
+    PanelOut O;
+    const PanelDev D = panel_upload(B, C, sr);
+    O.text = D.text;
+    if (O.text.empty()) return O;
+    const size_t n = (size_t)B.n, nslots = D.nslots, ngroups = D.ngroups;
+    const int64_t* d_pl_off = D.d_pl_off;
+    const int32_t *d_len = D.d_len, *d_bound = D.d_bound;
+    int32_t* d_text = D.d_text;
+    auto panel_planes = [&](bool reversed) { return qe::panel_planes(B, C, D, K, eq, reversed); };
     // ---- the forward pass
     const int want = panel_slices(C, ngroups, K), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
     PanelArgs a{};
@@ -1621,6 +1666,134 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
     hipLaunchKernelGGL(k_panel_finish, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, (int)nslots, (const int32_t*)d_text,
                        (const int32_t*)r.o_pair, (const int32_t*)o_start, O.d_hits);
+    HIP_CHECK(hipGetLastError());
+    return O;
+}
+
+// Every occurrence of every member (quicked_batch_run_panel_all): the panel upload and pack of a panel run,
+// k_panel_hits over text groups x slices -- per (slice, slot) its counts and up to max_hits raw records --, k_panel_hits_count
+// (found / smallest score / stored per pair), the offset scan over the stored counts in the order of the pairs and -- the one
+// thing the host reads in between -- their total, which sizes the rest: k_panel_hits_expand puts the stored occurrences in
+// their places and, INFIX, writes one start-pass task per occurrence; the pass is the unchanged k_search<4, Eq> in its
+// start-pass form with task j's pair = j and two arrays of `total` plane offsets (the member's into the reversed panel planes,
+// the text's); k_panel_hits_finish adds its o_start.  Both passes are timed as kind 0.
+//
+// The raw buffer is nslices x nslots x max_hits records of 12 bytes: the slice count is lowered until that fits
+// QE_PANEL_HITS_RAW_KB (1 GiB unset; one slice always fits it under the 2^26 rule of the entry point).
+static int panel_hits_slices(const Context& C, size_t nslots, int K, int max_hits) {
+    const size_t budget = (size_t)std::max<long long>(1, sw_ll(Sw::PanelHitsRawKb)) << 10;
+    const size_t per_slice_bytes = nslots * (size_t)max_hits * sizeof(PanelRawHit);
+    const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(1, per_slice_bytes));
+    return (int)std::min<size_t>((size_t)panel_slices(C, nslots / 64, K), fit);
+}
+// what such a run takes from its pool before the total is known (the planner's fixed needs): the panel's bytes, tables and
+// planes, the slice partials and the raw buffer at the slices the host would choose, the per-pair arrays, and a flagged run's
+// four-plane words of the texts.  The arrays sized by the total (16 bytes per stored occurrence, 60 with the start pass) are
+// not known before the run and are not planned, as in an all-occurrences search run
+static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    size_t texts = 0;
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    const size_t n = (size_t)B.n, K = (size_t)pr.n_patterns, nslots = (texts + 63) / 64 * 64, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
+    size_t pool = 0;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
+    size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
+    const size_t nslices = (size_t)panel_hits_slices(C, nslots, pr.n_patterns, sr.max_hits);
+    b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
+    b += nslots * 8 + n * 12 + (n + 1) * 8;
+    if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
+    return b + 16 * 512;
+}
+struct PanelHitsOut {
+    std::vector<int32_t> text;                     // slot -> pair, -1 in the padding
+    int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
+    int64_t total = 0;
+};
+static PanelHitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
+    const bool infix = sr.mode == SEARCH_INFIX;
+    PanelHitsOut O;
+    const PanelDev D = panel_upload(B, C, sr);
+    O.text = D.text;
+    if (O.text.empty()) return O;
+    const size_t n = (size_t)B.n, nslots = D.nslots, ngroups = D.ngroups;
+    // ---- the forward pass
+    const int want = panel_hits_slices(C, nslots, K, max_hits), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    PanelHitsArgs a{};
+    a.pl_m = panel_planes(B, C, D, K, eq, false); a.m_off = D.d_pl_off; a.m_len = D.d_len; a.m_bound = D.d_bound;
+    a.n_members = K; a.per_slice = per_slice;
+    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
+    a.nslots = (int32_t)nslots; a.text = D.d_text; a.mode = sr.mode; a.max_hits = max_hits;
+    a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
+    a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
+    int32_t* blk = C.scratch_p->take<int32_t>(3 * n);
+    O.d_found = blk; O.d_best = blk + n;
+    int32_t* d_plen = blk + 2 * n;
+    HIP_CHECK(hipMemsetAsync(O.d_found, 0, n * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(O.d_best, 0xFF, 2 * n * sizeof(int32_t), C.stream));
+    O.d_adv = C.scratch_p->take<u32>(nslots);
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nslots * sizeof(u32), C.stream));
+    O.d_off = C.scratch_p->take<int64_t>(n + 1);
+    auto* ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    {
+        // k_search_panel's launch shape: four text groups per workgroup and launch_groups' claim on the CU's LDS
+        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
+        if (eq) hipLaunchKernelGGL(k_panel_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+        else hipLaunchKernelGGL(k_panel_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    // ---- counts per pair, offsets in the order of the pairs (a pair without a slot has -1 + 1 = 0 stored), the total
+    PanelHitsCountArgs c{};
+    c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits; c.text = D.d_text; c.part = a.part;
+    c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.o_adv = O.d_adv;
+    hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
+    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, (const int32_t*)d_plen, (const int32_t*)B.d_t_len, O.d_off, O.d_off + n, (int)n);
+    HIP_CHECK(hipGetLastError());
+    {
+        std::vector<int64_t> tot;
+        FetchBatch fb(C);
+        fb.add(tot, (const int64_t*)(O.d_off + n), 1);
+        fb.sync();
+        O.total = tot[0];
+    }
+    if (O.total <= 0) return O;
+    const size_t nh = (size_t)O.total;
+    O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
+    PanelHitsExpandArgs e{};
+    e.nslots = (int32_t)nslots; e.nslices = nslices; e.max_hits = max_hits; e.infix = infix ? 1 : 0;
+    e.text = D.d_text; e.part = a.part; e.raw = a.raw; e.off = O.d_off;
+    e.m_len = D.d_len; e.m_off = D.d_pl_off; e.t_len = B.d_t_len; e.t_off = B.d_plt_off; e.hits = O.d_hits;
+    int32_t* o_start = nullptr;
+    if (infix) {
+        int32_t* q = C.scratch_p->take<int32_t>(6 * nh);
+        e.o_pair = q; e.o_m = q + nh; e.o_n = q + 2 * nh; e.o_score = q + 3 * nh; e.o_end = q + 4 * nh; o_start = q + 5 * nh;
+        HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
+        e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
+        e.o_plt_off = e.o_plp_off + nh;
+        O.d_adv2 = C.scratch_p->take<u32>(nh);
+        HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
+    }
+    hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
+    HIP_CHECK(hipGetLastError());
+    if (!infix) return O;
+    // ---- the start pass: one lane per stored occurrence over its window, reversed
+    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    PairView PV = pair_view(B, true);
+    PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
+    PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
+    SearchArgs s{};
+    s.P = PV;
+    s.T.ntasks = (int32_t)nh; s.T.pair = e.o_pair; s.T.m = e.o_m; s.T.n = e.o_n; s.T.cutoff = e.o_score;
+    s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
+    s.in_score = e.o_score; s.in_end = e.o_end; s.o_start = o_start; s.o_adv = O.d_adv2;
+    ke = C.kernel_events(0);
+    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    launch_search(C, eq, 3, s, (nh + 63) / 64);
+    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
     HIP_CHECK(hipGetLastError());
     return O;
 }
@@ -1985,6 +2158,9 @@ static void reset_host_results(quicked_batch& B) {
     B.wr->panel_members = B.panel_run;
     if (B.panel_run && B.panel_matrix) { B.wr->panel_score.assign((size_t)B.n * (size_t)B.panel_run, -1); B.wr->panel_end.assign((size_t)B.n * (size_t)B.panel_run, -1); }
     else { B.wr->panel_score.clear(); B.wr->panel_end.clear(); }
+    if (B.panel_all_run) { B.wr->panel_found.assign((size_t)B.n, 0); B.wr->panel_occ_off.assign((size_t)B.n + 1, 0); }
+    else { B.wr->panel_found.clear(); B.wr->panel_occ_off.clear(); }
+    B.wr->panel_occ.clear();
     B.wr->deferred_pairs = 0;
 }
 

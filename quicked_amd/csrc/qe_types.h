@@ -165,7 +165,8 @@ struct HitExpandArgs {
     int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;
 };
 
-// (the argument blocks of the panel kernels, PanelArgs and PanelReduceArgs, are in qe_panel.h: plain C++, next to the
+// (the argument blocks of the panel kernels -- PanelArgs and PanelReduceArgs, and PanelHitsArgs, PanelHitsCountArgs and
+// PanelHitsExpandArgs of the all-occurrences run -- are in qe_panel.h: plain C++, next to the
 // per-slot functions that the kernels and their host stand-ins share)
 
 // BandEd score-only, G lanes per alignment (cooperative form of k_banded<false>)
