@@ -159,6 +159,9 @@ def lib():
     L.quicked_batch_md_bytes.argtypes = [C.c_void_p]
     L.quicked_batch_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_debug_tag_launches.argtypes = [C.c_void_p]
+    if hasattr(L, "quicked_debug_pack"):
+        L.quicked_debug_pack.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.quicked_wire_words.restype = C.c_int64
     L.quicked_wire_words.argtypes = [C.c_int32, C.c_int]
     L.quicked_wire_pack.argtypes = [C.c_char_p, C.c_int32, C.c_int, C.c_void_p]
@@ -199,6 +202,34 @@ def tag_launches():
     v = np.zeros(2, dtype=np.int64)
     lib().quicked_debug_tag_launches(v.ctypes.data)
     return int(v[0]), int(v[1])
+
+
+def debug_pack(patterns, texts, reverse=False):
+    """k_pack's planes of two sets of byte strings of equal count, through the one launch that packs both; a test hook ->
+    (pattern words, pattern word offsets, text words, text word offsets, flags per pair); words: uint64, 3 per 64 bases
+    {code bit 0, code bit 1, not ACGT} and two rows of zeros behind every sequence"""
+    assert len(patterns) == len(texts)
+    n = len(patterns)
+
+    def pool_of(seqs):
+        length = np.array([len(s) for s in seqs], dtype=np.int32)
+        off = np.zeros(n, dtype=np.int64)
+        if n:
+            off[1:] = np.cumsum(length[:-1], dtype=np.int64)
+        pool = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy()
+        return pool, off, length, int(sum(3 * ((int(v) + 63) // 64 + 2) for v in length))
+
+    pp, po, pl, pw = pool_of(patterns)
+    tp, to, tl, tw = pool_of(texts)
+    p_words, t_words = np.zeros(pw + 1, dtype=np.uint64), np.zeros(tw + 1, dtype=np.uint64)
+    p_off, t_off = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    flags = np.zeros(n + 1, dtype=np.uint32)
+    st = lib().quicked_debug_pack(n, pp.ctypes.data, po.ctypes.data, pl.ctypes.data, tp.ctypes.data, to.ctypes.data, tl.ctypes.data,
+                                  1 if reverse else 0, p_words.ctypes.data, pw, p_off.ctypes.data, t_words.ctypes.data, tw,
+                                  t_off.ctypes.data, flags.ctypes.data)
+    if st < 0:
+        raise QuickedException(st)
+    return p_words[:pw], p_off[:n], t_words[:tw], t_off[:n], flags[:n]
 
 
 def pool_trim():

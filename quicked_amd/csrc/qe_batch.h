@@ -237,6 +237,10 @@ void batch_quiesce(quicked_batch* B);
 void finisher_retire();
 // device-side cigar_check_alignment of caller-provided strings against the batch's resident pairs (quicked_batch_validate)
 quicked_status_t batch_validate(quicked_batch* B, Context& C, const char* cigar_pool, int64_t pool_bytes, const int64_t* cigar_off, int32_t* ok_out);
+// the planes (with the padding rows, at the library's own word offsets) and the flags k_pack leaves for the batch's sequences
+// (quicked_debug_pack)
+quicked_status_t batch_debug_pack(quicked_batch* B, Context& C, bool reversed, uint64_t* p_planes, uint64_t* t_planes,
+                                  int64_t* p_pl_off, int64_t* t_pl_off, uint32_t* flags);
 void early_finish_stats(int64_t stats_out[4]);
 // count passes of the alignment-tag kernels launched so far: form 0 = one lane per alignment, 1 = one wave (test hook)
 int64_t tag_launches(int form);

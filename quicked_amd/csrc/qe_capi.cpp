@@ -545,6 +545,31 @@ QE_API quicked_status_t quicked_debug_tag_launches(int64_t out[2]) {
     return QUICKED_OK;
 }
 
+// Test hook, not in the public header: the planes of n patterns and n texts exactly as k_pack lays them out -- 3 words per
+// 64 bases and two rows of zeros behind every sequence, sequence i of a set at word *_pl_off[i] as the library computes it --
+// forward or reversed, through the one launch that packs both sets, and flags[i] = the OR of the flags of pattern i and
+// text i.  A set's planes take the sum over its sequences of 3 * ((len + 63) / 64 + 2) words; p_words / t_words = the room
+// the caller has made (QUICKED_ERROR if it is less).  tests/test_gpu_pack_planes.py and nothing else.
+QE_API quicked_status_t quicked_debug_pack(int64_t n, const char* pattern_pool, const int64_t* pattern_off, const int32_t* pattern_len,
+                                           const char* text_pool, const int64_t* text_off, const int32_t* text_len, int reversed,
+                                           uint64_t* p_planes, int64_t p_words, int64_t* p_pl_off,
+                                           uint64_t* t_planes, int64_t t_words, int64_t* t_pl_off, uint32_t* flags) {
+    if (n < 0 || !p_planes || !t_planes || !p_pl_off || !t_pl_off || !flags) return QUICKED_ERROR;
+    quicked_batch_t* b = quicked_batch_create(n, pattern_pool, pattern_off, pattern_len, text_pool, text_off, text_len);
+    if (!b) return QUICKED_ERROR;
+    struct Arg { int rev; uint64_t* pp; int64_t pw; int64_t* po; uint64_t* tp; int64_t tw; int64_t* to; uint32_t* fl; }
+        arg{reversed, p_planes, p_words, p_pl_off, t_planes, t_words, t_pl_off, flags};
+    const quicked_status_t st = guard(b, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        if ((int64_t)B->pl_p_words > x->pw || (int64_t)B->pl_t_words > x->tw) return QUICKED_ERROR;
+        tl_device = B->device;
+        Context& C = ctx();
+        return batch_debug_pack(B, C, x->rev != 0, x->pp, x->tp, x->po, x->to, x->fl);
+    }, &arg);
+    quicked_batch_destroy(b);
+    return st;
+}
+
 // Test hook, not in the public header: parses the QE_* switches again (qe_pool.h: switches_reload).  The in-process test
 // suites change switches between runs and reach it through capi.reload_env().
 QE_API quicked_status_t quicked_debug_reload_env(void) {

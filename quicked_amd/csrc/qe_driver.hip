@@ -1882,4 +1882,30 @@ quicked_status_t batch_validate(quicked_batch* B, Context& C, const char* cigar_
     C.pool_w.release(mk);
     return QUICKED_OK;
 }
+
+// The planes and flags k_pack leaves for the batch's sequences, as launch_pack launches it (quicked_debug_pack): plane set 0
+quicked_status_t batch_debug_pack(quicked_batch* B, Context& C, bool reversed, uint64_t* p_planes, uint64_t* t_planes,
+                                  int64_t* p_pl_off, int64_t* t_pl_off, uint32_t* flags) {
+    if (B->packed) return QUICKED_UNIMPLEMENTED;
+    C.sync_all();
+    C.phase_u();
+    B->parity = 0;
+    const size_t n = (size_t)B->n;
+    if (n == 0) return QUICKED_OK;
+    u64* const d_p = reversed ? B->d_pl_pr[0] : B->d_pl_p[0];
+    u64* const d_t = reversed ? B->d_pl_tr[0] : B->d_pl_t[0];
+    // what the kernel does not write shows: the planes start as all-ones
+    HIP_CHECK(hipMemsetAsync(d_p, 0xFF, B->pl_p_words * sizeof(u64), C.stream));
+    HIP_CHECK(hipMemsetAsync(d_t, 0xFF, B->pl_t_words * sizeof(u64), C.stream));
+    HIP_CHECK(hipMemsetAsync(B->d_flags[0], 0, n * sizeof(u32), C.stream));
+    launch_pack(*B, C, reversed, true);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(p_planes, d_p, B->pl_p_words * sizeof(u64), hipMemcpyDeviceToHost, C.stream));
+    HIP_CHECK(hipMemcpyAsync(t_planes, d_t, B->pl_t_words * sizeof(u64), hipMemcpyDeviceToHost, C.stream));
+    HIP_CHECK(hipMemcpyAsync(flags, B->d_flags[0], n * sizeof(u32), hipMemcpyDeviceToHost, C.stream));
+    HIP_CHECK(hipStreamSynchronize(C.stream));
+    memcpy(p_pl_off, B->plp_off.data(), n * sizeof(int64_t));
+    memcpy(t_pl_off, B->plt_off.data(), n * sizeof(int64_t));
+    return QUICKED_OK;
+}
 }  // namespace qe

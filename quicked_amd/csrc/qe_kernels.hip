@@ -32,6 +32,7 @@
 #include "qe_bounded.h"
 #include "qe_search.h"
 #include "qe_panel.h"
+#include "qe_pack.h"
 #include "qe_tags.h"
 #include "qe_check.h"
 
@@ -799,92 +800,105 @@ __device__ __forceinline__ int plane_code(const u64* __restrict__ base, int pos)
 // ===========================================================================
 // pack: ASCII -> planes.  One wave per sequence; a lane takes 16 consecutive
 // bases with one 16-byte load (a wave reads 1 KB = 16 rows per load instruction)
-// and classifies them four at a time in 32-bit SWAR:
-//   (c >> 1) & 3 is an injective 2-bit code of A, C, G, T in either case
-//   (A 0, C 1, T 2, G 3; any injective code works) and indexes a 4-byte table of
-//   the upper-case letters (v_perm_b32); the base is ACGT iff the table byte
-//   equals its upper-cased self, anything else is the reference's code 4
-//   (dna_text.c:41-46).
-// Per-byte flags live in bit 7 of their byte; three shift-ors gather the four
-// flags of a word into a nibble.  Four neighbouring lanes make one 64-base row.
+// and classifies them with pack_classify16 (qe_pack.h: the v_perm_b32 table, the
+// SWAR non-zero-byte test, the planes' bits gathered eight at a time with two
+// shift-ors).  Four neighbouring lanes make one 64-base row: two DPP quad
+// exchanges, lane 0 of the quad stores.  A span that lies wholly inside the sequence -- a test the
+// wave makes once -- is loaded with no guard per lane; the spans behind them
+// (the ragged one, the padding rows) take the guarded forms.  Flags are lazy:
+// one wave-level test of pack_classify16's hint per span, and only a span
+// that has a candidate byte in some lane looks at which symbol it was.
 // ===========================================================================
-__device__ __forceinline__ u32 gather_msb4(u32 x) {        // flags at bits 7, 15, 23, 31 -> bits 28..31
-    u32 t = (x << 7) | x;
-    t = (x << 14) | t;
-    return (x << 21) | t;
+static_assert(PACK_HAS_N == FLAG_HAS_N && PACK_NONCANON == FLAG_NONCANON, "qe_pack.h's flag bits are the batch's");
+template <int CTRL> __device__ __forceinline__ u32 quad_perm(u32 x) {      // lane l of every quad <- lane (CTRL >> 2 l) & 3 of it
+    return (u32)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);      // every lane has a source: nothing of the old value is kept
 }
 
-__global__ __launch_bounds__(256) void k_pack(PackArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (seq >= A.nseq) return;
-    const int len = A.len[seq];
-    const uint8_t* __restrict__ src = A.asc + A.asc_off[seq];
-    u64* __restrict__ dst = A.planes + A.pl_off[seq];
+// one span of a wave: this lane's 16 bytes -> its share of the 16 rows at `span`; rows: the sequence's rows (guarded: the
+// span may reach past them)
+template <bool GUARDED>
+__device__ __forceinline__ void pack_span(const uint4& x, u64* __restrict__ dst, int span, int lane, int nrows, bool want_flags, u32& fl) {
+    const u32 w[4] = {x.x, x.y, x.z, x.w};
+    u32 a, b, n, hint;
+    pack_classify16(w, a, b, n, hint);
+    if (want_flags && __any(hint != 0)) fl |= pack_flags16(w);
+    // 16-bit masks of this lane's 16 bases -> 64-bit row words on every fourth lane
+    const u32 ab = a | (b << 16);
+    const u32 ab1 = quad_perm<0xF5>(ab), n1 = quad_perm<0xF5>(n);                         // lanes 0 / 2 <- lanes 1 / 3
+    const u32 a32 = __builtin_amdgcn_perm(ab1, ab, 0x05040100u), b32 = __builtin_amdgcn_perm(ab1, ab, 0x07060302u), n32 = n | (n1 << 16);
+    const u32 a32h = quad_perm<0xAA>(a32), b32h = quad_perm<0xAA>(b32), n32h = quad_perm<0xAA>(n32);      // lane 0 <- lane 2
+    const int row = span * 16 + (lane >> 2);
+    if ((lane & 3) == 0 && (!GUARDED || row < nrows)) {
+        u64* q = dst + 3 * (int64_t)row;
+        q[0] = mk64(a32, a32h); q[1] = mk64(b32, b32h); q[2] = mk64(n32, n32h);
+    }
+}
+template <bool REVERSE> __device__ __forceinline__ uint4 pack_load16(const uint8_t* p) {      // 16 bytes in string order, or back to front
+    uint4 y; __builtin_memcpy(&y, p, 16);
+    if (REVERSE) y = make_uint4(__builtin_bswap32(y.w), __builtin_bswap32(y.z), __builtin_bswap32(y.y), __builtin_bswap32(y.x));
+    return y;
+}
+
+// one sequence, by one wave: len bytes at src -> its rows at dst; -> the lane's flags
+template <bool REVERSE>
+__device__ __forceinline__ u32 pack_sequence(const uint8_t* __restrict__ src, int len, u64* __restrict__ dst, int lane, bool want_flags) {
     const int nrows = ((len + 63) >> 6) + 2;                 // two zero rows of padding (funnel-shift over-read)
     const int nspan = (nrows + 15) >> 4;
+    const int nfull = len >> 10;                             // spans of 1024 bases that lie wholly inside the sequence
     u32 fl = 0;
     constexpr int UNR = 4;                                    // 16-byte loads in flight per lane
-    constexpr u32 ALL_A = 0x41414141u;                        // filler past the end: 'A' packs to all-zero planes
-    for (int s0 = 0; s0 < nspan; s0 += UNR) {
+    int s0 = 0;
+    // the lane's bytes of span s: forward at src + 1024 s + 16 lane, reversed at src + len - 1024 (s + 1) + (1008 - 16 lane):
+    // a base the wave shares and an offset of the lane's that never changes
+    const u32 lane_off = REVERSE ? 1008u - 16u * (u32)lane : 16u * (u32)lane;
+    for (; s0 + UNR <= nfull; s0 += UNR) {
+        uint4 raw[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const uint8_t* base = src + (REVERSE ? len - 1024 * (s0 + u + 1) : 1024 * (s0 + u));
+            raw[u] = pack_load16<REVERSE>(base + lane_off);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) pack_span<false>(raw[u], dst, s0 + u, lane, nrows, want_flags, fl);
+    }
+    for (; s0 < nspan; s0 += UNR) {
         uint4 raw[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int pos = (s0 + u) * 1024 + 16 * lane;
-            uint4 x = make_uint4(ALL_A, ALL_A, ALL_A, ALL_A);
-            if (pos + 16 <= len) {
-                if (A.reverse) {
-                    uint4 y; __builtin_memcpy(&y, src + (len - 16 - pos), 16);
-                    x = make_uint4(__builtin_bswap32(y.w), __builtin_bswap32(y.z), __builtin_bswap32(y.y), __builtin_bswap32(y.x));
-                } else {
-                    __builtin_memcpy(&x, src + pos, 16);
-                }
-            } else if (pos < len) {                           // the one ragged lane of a sequence
-                u32 wv[4] = {ALL_A, ALL_A, ALL_A, ALL_A};
-                for (int i = 0; i < len - pos; ++i) {
-                    const u32 c = A.reverse ? src[len - 1 - pos - i] : src[pos + i];
-                    wv[i >> 2] = (wv[i >> 2] & ~(0xFFu << (8 * (i & 3)))) | (c << (8 * (i & 3)));
-                }
+            uint4 x = make_uint4(PACK_FILL, PACK_FILL, PACK_FILL, PACK_FILL);
+            if (pos + 16 <= len) x = pack_load16<REVERSE>(src + (REVERSE ? len - 16 - pos : pos));
+            else if (pos < len) {                             // the one ragged lane of a sequence
+                u32 wv[4];
+                pack_fetch16(src, len, pos, REVERSE, wv);
                 x = make_uint4(wv[0], wv[1], wv[2], wv[3]);
             }
             raw[u] = x;
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const int span = s0 + u;
-            if (span >= nspan) break;
-            const u32 wv[4] = {raw[u].x, raw[u].y, raw[u].z, raw[u].w};
-            u32 accA = 0, accB = 0, accN = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u32 w = wv[k];
-                const u32 want = __builtin_amdgcn_perm(0u, 0x47544341u, (w >> 1) & 0x03030303u);   // 'A','C','T','G'
-                const u32 y = want ^ (w & 0xDFDFDFDFu);                                              // case-insensitive (dna_text.c:44-45)
-                const u32 z = ((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y;                                 // bit 7 of a byte set <=> not ACGT
-                const u32 ok = ~z & 0x80808080u, bad = z & 0x80808080u;
-                accA = (accA >> 4) | (gather_msb4((w << 6) & ok) & 0xF0000000u);                     // code bit 0 = ASCII bit 1
-                accB = (accB >> 4) | (gather_msb4((w << 5) & ok) & 0xF0000000u);                     // code bit 1 = ASCII bit 2
-                accN = (accN >> 4) | (gather_msb4(bad) & 0xF0000000u);
-                if ((w << 2) & ok) fl |= FLAG_NONCANON;                                              // lower-case base: raw != encoded compare
-                if (bad) {
-                    fl |= FLAG_HAS_N;
-                    for (int i = 0; i < 4; ++i)
-                        if (((bad >> (8 * i + 7)) & 1) && ((w >> (8 * i)) & 0xFF) != 'N') fl |= FLAG_NONCANON;   // IUPAC and the rest
-                }
-            }
-            // 16-bit masks of this lane's 16 bases -> 64-bit row words on every fourth lane
-            const u32 ab = (accA >> 16) | (accB & 0xFFFF0000u), nn = accN >> 16;
-            const u32 ab1 = __shfl_down(ab, 1), nn1 = __shfl_down(nn, 1);
-            const u32 a32 = (ab & 0xFFFFu) | (ab1 << 16), b32 = (ab >> 16) | (ab1 & 0xFFFF0000u), n32 = nn | (nn1 << 16);
-            const u32 a32h = __shfl_down(a32, 2), b32h = __shfl_down(b32, 2), n32h = __shfl_down(n32, 2);
-            const int row = span * 16 + (lane >> 2);
-            if ((lane & 3) == 0 && row < nrows) {
-                u64* q = dst + 3 * (int64_t)row;
-                q[0] = mk64(a32, a32h); q[1] = mk64(b32, b32h); q[2] = mk64(n32, n32h);
-            }
+            if (s0 + u >= nspan) break;
+            pack_span<true>(raw[u], dst, s0 + u, lane, nrows, want_flags, fl);
         }
     }
-    if (A.flags && __any(fl != 0)) {
+    return fl;
+}
+
+__global__ __launch_bounds__(256) void k_pack(PackArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int per_set = (A.nseq + 3) >> 2;                    // blocks
+    const bool second = (int)blockIdx.x >= per_set;           // wave-uniform, as everything but the lane's own offset
+    const int seq = ((int)blockIdx.x - (second ? per_set : 0)) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (seq >= A.nseq) return;
+    const int32_t* __restrict__ lens = second ? A.set[1].len : A.set[0].len;
+    const int64_t* __restrict__ asc_off = second ? A.set[1].asc_off : A.set[0].asc_off;
+    const int64_t* __restrict__ pl_off = second ? A.set[1].pl_off : A.set[0].pl_off;
+    const int len = lens[seq];
+    const uint8_t* __restrict__ src = (second ? A.set[1].asc : A.set[0].asc) + asc_off[seq];
+    u64* __restrict__ dst = (second ? A.set[1].planes : A.set[0].planes) + pl_off[seq];
+    const bool want_flags = A.flags != nullptr;
+    const u32 fl = A.reverse ? pack_sequence<true>(src, len, dst, lane, want_flags) : pack_sequence<false>(src, len, dst, lane, want_flags);
+    if (want_flags && __any(fl != 0)) {
         u32 f = fl;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) f |= __shfl_xor(f, o);

@@ -48,7 +48,8 @@ static void launch_groups(Context& C, Kernel kernel, const Args& args, size_t ng
     HIP_CHECK(hipGetLastError());             // a rejected launch (block shape, LDS) must not pass for zeroed results
 }
 
-static void launch_pack(quicked_batch& B, Context& C, bool reversed) {
+// flags_of_reversed: the reversed pack ORs the flags in as the forward one does (quicked_debug_pack; no run asks for it)
+static void launch_pack(quicked_batch& B, Context& C, bool reversed, bool flags_of_reversed = false) {
     if (B.packed) {                       // forward planes are the input; reversed ones come from them
         if (!reversed) return;
         const int blocks = (int)((B.n + 3) / 4);
@@ -61,18 +62,16 @@ static void launch_pack(quicked_batch& B, Context& C, bool reversed) {
         for (bool& h : B.have_rev) h = true;    // every set aliases the same buffers
         return;
     }
+    // patterns and texts in ONE launch (PackArgs): two launches are two kernels that each wait for CUs next to the band walk
     PackArgs a;
     a.nseq = (int32_t)B.n;
     a.reverse = reversed ? 1 : 0;
     const int q = B.parity;
-    a.flags = reversed ? nullptr : B.d_flags[q];
+    a.flags = (reversed && !flags_of_reversed) ? nullptr : B.d_flags[q];
     const int blocks = (int)((B.n + 3) / 4);
-    a.asc = B.d_asc_p; a.asc_off = B.d_p_off; a.len = B.d_p_len;
-    a.planes = reversed ? B.d_pl_pr[q] : B.d_pl_p[q]; a.pl_off = B.d_plp_off;
-    hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
-    a.asc = B.d_asc_t; a.asc_off = B.d_t_off; a.len = B.d_t_len;
-    a.planes = reversed ? B.d_pl_tr[q] : B.d_pl_t[q]; a.pl_off = B.d_plt_off;
-    hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
+    a.set[0] = PackSet{B.d_asc_p, B.d_p_off, B.d_p_len, reversed ? B.d_pl_pr[q] : B.d_pl_p[q], B.d_plp_off};
+    a.set[1] = PackSet{B.d_asc_t, B.d_t_off, B.d_t_len, reversed ? B.d_pl_tr[q] : B.d_pl_t[q], B.d_plt_off};
+    hipLaunchKernelGGL(k_pack, dim3(2 * blocks), dim3(256), 0, C.stream, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1582,7 +1581,8 @@ static const u64* panel_planes(quicked_batch& B, Context& C, const PanelDev& D, 
     } else {
         PackArgs a;
         a.nseq = K; a.reverse = reversed ? 1 : 0; a.flags = nullptr;
-        a.asc = D.d_pool; a.asc_off = D.d_asc_off; a.len = D.d_len; a.planes = pl; a.pl_off = D.d_pl_off;
+        a.set[0] = PackSet{D.d_pool, D.d_asc_off, D.d_len, pl, D.d_pl_off};
+        a.set[1] = a.set[0];                  // (one set's blocks: never read)
         hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, C.stream, a);
         // a packed batch's texts carry the wire formats' base codes, not k_pack's
         if (B.packed) hipLaunchKernelGGL(k_panel_wire_codes, dim3((unsigned)((D.words3 / 3 + 255) / 256)), dim3(256), 0, C.stream, pl, (int64_t)(D.words3 / 3));

@@ -45,11 +45,16 @@ struct TaskView {
     const int32_t* tfin;     // text_finish_pos (score-only passes)
 };
 
-// pack: ASCII -> planes (+ flags).  reverse != 0 packs the reversed string.
-struct PackArgs {
-    int32_t nseq;
+// pack: ASCII -> planes (+ flags).  reverse != 0 packs the reversed string.  One launch packs one set of nseq sequences
+// or two of them (a batch's patterns and its texts): the grid has (nseq + 3) / 4 blocks per set, the block index picks
+// the set, and sequence i of either set ORs its flags into flags[i] -- a pair's flags are those of both its sequences.
+struct PackSet {
     const uint8_t* asc;  const int64_t* asc_off;  const int32_t* len;
     u64* planes;  const int64_t* pl_off;
+};
+struct PackArgs {
+    int32_t nseq;        // sequences per set
+    PackSet set[2];      // set[1] is read only by a grid of two sets' blocks
     u32* flags;          // OR-ed into (may be null)
     int32_t reverse;
 };

@@ -6,10 +6,12 @@ def F3(i): d=40+(i%NREG); return f"v_bitop3_b32 v{d}, v{88+i%4}, v{92+i%4}, v{96
 def F2(i): d=40+(i%NREG); return f"v_xor_b32 v{d}, v{88+i%4}, v{92+i%4}"
 def S(i): d=40+2*(i%(NREG//2)); return f"v_lshl_add_u64 v[{d}:{d+1}], v[{88+2*(i%2)}:{89+2*(i%2)}], 1, v[{92+2*(i%2)}:{93+2*(i%2)}]"
 def SB(i): d=40+(i%NREG); return f"v_bfe_u32 v{d}, v{88+i%4}, 3, 1"
+def DT(i): d=40+(i%NREG); return f"v_dot4_u32_u8 v{d}, v{88+i%4}, v{92+i%4}, v{96+i%4}"      # k_pack's gather (qe_pack.h)
+def AN(i): d=40+(i%NREG); return f"v_and_b32 v{d}, v{88+i%4}, v{92+i%4}"
 def stream(pattern, n=640):
     out=[]; i=0
     for kind in itertools.islice(itertools.cycle(pattern), n):
-        out.append({'F':F3,'f':F2,'S':S,'b':SB}[kind](i)); i+=1
+        out.append({'F':F3,'f':F2,'S':S,'b':SB,'d':DT,'a':AN}[kind](i)); i+=1
     return out
 variants=[("all fast VOP3 (bitop3)", "F"),
           ("all fast VOP2 (xor e32)", "f"),
@@ -21,7 +23,10 @@ variants=[("all fast VOP3 (bitop3)", "F"),
           ("F f alternating", "Ff"),
           ("F F f f S mix like the pass", "FFffS"),
           ("F S alternating", "FS"),
-          ("F F F F b interleaved (bfe)", "FFFFb")]
+          ("F F F F b interleaved (bfe)", "FFFFb"),
+          ("all v_dot4_u32_u8", "d"),
+          ("all v_and_b32 (e32)", "a"),
+          ("d a alternating", "da")]
 src=['#include <hip/hip_runtime.h>','#include <cstdio>','#include <cstdint>','#include <vector>','#include <algorithm>',
 'struct Stamp { uint64_t cyc, real; };',
 'template <int V> __global__ __launch_bounds__(256) void k(unsigned* out, Stamp* st, int iters) {',

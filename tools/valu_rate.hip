@@ -9,7 +9,7 @@
 // Part B  the block-step loops of qe_kernels.hip (the production code, included) on register-resident state, no memory
 //         in the loop: cycles per block-column per SIMD for the 1-, 2- and 4-slot forms and for experimental variants.
 //
-//   hipcc --offload-arch=gfx950 -O3 tools/valu_rate.hip -o tools/bin/valu_rate && tools/bin/valu_rate [A|B|AB]
+//   hipcc --offload-arch=gfx950 -O3 tools/valu_rate.hip -o tools/bin/valu_rate && tools/bin/valu_rate [A|B|C|D|P ...]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,11 +24,11 @@ using qe::u32;
 using qe::u64;
 
 enum Op { XOR, OR, AND, ADD, SUB, LSHR, LSHL, ASHR, MOV, BITOP3, ALIGNBIT, BFE_U, BFE_I, LSHL_OR, OR3, AND_OR, ADD3, BCNT, BFREV,
-          PERM, CNDMASK, LSHL_ADD_U64, ADD_CO_PAIR, LSHL_B64, NOPS };
+          PERM, CNDMASK, DOT4, DOT4_AND, LSHL_ADD_U64, ADD_CO_PAIR, LSHL_B64, NOPS };
 static const char* const OP_NAME[] = {"v_xor_b32", "v_or_b32", "v_and_b32", "v_add_u32", "v_sub_u32", "v_lshrrev_b32", "v_lshlrev_b32",
                                       "v_ashrrev_i32", "v_mov_b32", "v_bitop3_b32", "v_alignbit_b32", "v_bfe_u32", "v_bfe_i32",
                                       "v_lshl_or_b32", "v_or3_b32", "v_and_or_b32", "v_add3_u32", "v_bcnt_u32_b32", "v_bfrev_b32",
-                                      "v_perm_b32", "v_cndmask_b32", "v_lshl_add_u64", "v_add_co+v_addc_co", "v_lshlrev_b64"};
+                                      "v_perm_b32", "v_cndmask_b32", "v_dot4_u32_u8", "v_and+v_dot4 (1:1)", "v_lshl_add_u64", "v_add_co+v_addc_co", "v_lshlrev_b64"};
 
 // one instruction of a chain: r = f(r, x, y); x and y are never written (no dependency through them)
 template <int OP> __device__ __forceinline__ void op32(u32& r, u32 x, u32 y) {
@@ -53,6 +53,8 @@ template <int OP> __device__ __forceinline__ void op32(u32& r, u32 x, u32 y) {
     if (OP == BFREV) asm volatile("v_bfrev_b32 %0, %0" : "+v"(r));
     if (OP == PERM) asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(r) : "v"(x), "v"(y));
     if (OP == CNDMASK) asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(r) : "v"(x));
+    if (OP == DOT4) asm volatile("v_dot4_u32_u8 %0, %1, %2, %0" : "+v"(r) : "v"(x), "v"(y));                 // k_pack's gather (qe_pack.h)
+    if (OP == DOT4_AND) asm volatile("v_and_b32 %0, %0, %1\n\tv_dot4_u32_u8 %0, %0, %2, %0" : "+v"(r) : "v"(x), "v"(y));
 }
 template <int OP> __device__ __forceinline__ void op64(u64& r, u64 x) {
     if (OP == LSHL_ADD_U64) asm volatile("v_lshl_add_u64 %0, %0, 1, %1" : "+v"(r) : "v"(x));
@@ -120,7 +122,7 @@ template <int OP, int D> static void rate_row(int wps, int iters) {
         hipLaunchKernelGGL((k_rate<OP, D>), dim3(blocks), dim3(256), lds, 0, g_out, g_stamps, warm ? 8 : iters);
     };
     const Result r = measure(launch, wps);
-    const double instr = (double)iters * 64 * (OP == ADD_CO_PAIR ? 2 : 1);
+    const double instr = (double)iters * 64 * ((OP == ADD_CO_PAIR || OP == DOT4_AND) ? 2 : 1);
     const double per_wave = r.cyc_wave / instr;
     // per SIMD: from the wave's own cycles (exact while all w waves are resident together) and from the wall clock of the
     // whole launch at the measured clock (includes launch ramp and tail; the honest figure when w is large)
@@ -264,6 +266,73 @@ template <int MODE> static void bank_row(const char* name, int wps) {
            r.wall_ms * 1e-3 * r.clock_ghz * 1e9 / (instr * wps), r.clock_ghz);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Part P: k_pack's span classifier on registers, no memory in the loop.  VAR 0: pack_classify16 (qe_pack.h: eight flags
+// per gather, two shift-ors), 1: the same classification with the gather of four flags it replaced (three shift-ors, a
+// mask and a shift-merge per word and plane), 2: with v_dot4_u32_u8 (four flag bytes . the weights 1, 2, 4, 8 = the
+// nibble; two accumulators per plane).  All with the one hint per span.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 gather_msb4_shift_or(u32 x) {        // flags at bits 7, 15, 23, 31 -> bits 28..31
+    u32 t = (x << 7) | x;
+    t = (x << 14) | t;
+    return (x << 21) | t;
+}
+__device__ __forceinline__ u32 dot4(u32 x, u32 y, u32 acc) { return __builtin_amdgcn_udot4(x, y, acc, false); }
+template <int VAR> __device__ __forceinline__ void classify_var(const u32 (&w)[4], u32& a, u32& b, u32& n, u32& hint) {
+    if (VAR == 0) { qe::pack_classify16(w, a, b, n, hint); return; }
+    if (VAR == 2) {
+        constexpr u32 W_LO = 0x08040201u, W_HI = 0x80402010u;
+        const u32 a0 = dot4(w[1] & 0x02020202u, W_HI, dot4(w[0] & 0x02020202u, W_LO, 0u)), a1 = dot4(w[3] & 0x02020202u, W_HI, dot4(w[2] & 0x02020202u, W_LO, 0u));
+        const u32 b0 = dot4(w[1] & 0x04040404u, W_HI, dot4(w[0] & 0x04040404u, W_LO, 0u)), b1 = dot4(w[3] & 0x04040404u, W_HI, dot4(w[2] & 0x04040404u, W_LO, 0u));
+        const u32 n0 = dot4(qe::pack_not_acgt(w[1]), W_HI, dot4(qe::pack_not_acgt(w[0]), W_LO, 0u)), n1 = dot4(qe::pack_not_acgt(w[3]), W_HI, dot4(qe::pack_not_acgt(w[2]), W_LO, 0u));
+        n = (n0 >> 7) | (n1 << 1);
+        a = ((a0 >> 1) | (a1 << 7)) & ~n;
+        b = ((b0 >> 2) | (b1 << 6)) & ~n;
+        hint = ((w[0] | w[1] | w[2] | w[3]) & 0x20202020u) | n;
+        return;
+    }
+    u32 accA = 0, accB = 0, accN = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const u32 bad = qe::pack_not_acgt(w[k]), ok = ~bad & 0x80808080u;
+        accA = (accA >> 4) | (gather_msb4_shift_or((w[k] << 6) & ok) & 0xF0000000u);
+        accB = (accB >> 4) | (gather_msb4_shift_or((w[k] << 5) & ok) & 0xF0000000u);
+        accN = (accN >> 4) | (gather_msb4_shift_or(bad) & 0xF0000000u);
+    }
+    a = accA >> 16; b = accB >> 16; n = accN >> 16;
+    hint = ((w[0] | w[1] | w[2] | w[3]) & 0x20202020u) | n;
+}
+template <int VAR>
+__global__ __launch_bounds__(256) void k_classify(u32* out, Stamp* stamps, int iters) {
+    extern __shared__ uint4 pin[];
+    u32 w[4] = {0x41434754u + threadIdx.x, 0x54474341u ^ (threadIdx.x << 8), 0x43434747u + blockIdx.x, 0x41544154u};
+    u32 acc = 0;
+    const uint64_t c0 = __builtin_amdgcn_s_memtime(), t0 = __builtin_amdgcn_s_memrealtime();
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            u32 a, b, n, hint;
+            classify_var<VAR>(w, a, b, n, hint);
+            acc ^= a ^ (b << 16) ^ n ^ hint;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w[k] += 0x01020408u;          // the next span's bytes: one instruction per word in both variants
+        }
+    }
+    const uint64_t c1 = __builtin_amdgcn_s_memtime(), t1 = __builtin_amdgcn_s_memrealtime();
+    out[blockIdx.x * blockDim.x + threadIdx.x] = acc;
+    if ((threadIdx.x & 63) == 0) stamps[blockIdx.x * 4 + (threadIdx.x >> 6)] = Stamp{c1 - c0, t1 - t0};
+}
+template <int VAR> static void classify_row(const char* name, int wps, int iters) {
+    auto launch = [&](int blocks, size_t lds, bool warm) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_classify<VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL((k_classify<VAR>), dim3(blocks), dim3(256), lds, 0, g_out, g_stamps, warm ? 4 : iters);
+    };
+    const Result r = measure(launch, wps);
+    const double spans = (double)iters * 8;
+    printf("%-40s w=%d  %6.1f cyc / span / SIMD (one wave: %6.1f)   clock %.2f GHz  (%.2f ms)\n", name, wps,
+           r.wall_ms * 1e-3 * r.clock_ghz * 1e9 / (spans * wps), r.cyc_wave / spans, r.clock_ghz, r.wall_ms);
+}
+
 int main(int argc, char** argv) {
     const char* what = argc > 1 ? argv[1] : "ABC";
     hipMalloc(&g_out, (size_t)CUS * 8 * 256 * 4);
@@ -275,6 +344,18 @@ int main(int argc, char** argv) {
         rate_op<ASHR>(false); rate_op<MOV>(false); rate_op<ALIGNBIT>(false); rate_op<BFE_U>(false); rate_op<BFE_I>(false);
         rate_op<LSHL_OR>(false); rate_op<OR3>(false); rate_op<AND_OR>(false); rate_op<ADD3>(false); rate_op<BCNT>(false);
         rate_op<BFREV>(false); rate_op<PERM>(false); rate_op<CNDMASK>(false); rate_op<LSHL_B64>(false);
+    }
+    if (strchr(what, 'D')) {
+        printf("# Part D: v_dot4_u32_u8 alone and 1 : 1 with v_and_b32, next to v_and_b32 alone (8 chains; 2 and 8 waves per SIMD)\n");
+        for (int w : {2, 8}) { rate_row<AND, 8>(w, 3000); rate_row<DOT4, 8>(w, 3000); rate_row<DOT4_AND, 8>(w, 3000); }
+    }
+    if (strchr(what, 'P')) {
+        printf("# Part P: k_pack's classifier of one 16-base span on registers (no loads, no quad merge, no stores)\n");
+        for (int w : {1, 2, 4, 8}) {
+            classify_row<0>("pack_classify16 (8 flags, 2 shift-ors)", w, 2000);
+            classify_row<1>("4 flags, 3 shift-ors (the parent's)", w, 2000);
+            classify_row<2>("v_dot4_u32_u8 gather", w, 2000);
+        }
     }
     if (strchr(what, 'C')) {
         printf("# Part C: VGPR banks of the sources (8 independent chains, physical registers)\n");
