@@ -130,11 +130,11 @@ struct quicked_batch {
     // ... of the run in progress: `tags` for a sync != 0 run that aligns, else 0 (run_batch) -- what format_segments and the
     // host-driven flows of that run read, whatever the caller configures meanwhile
     int run_tags = 0;
-    bool search_run = false;                      // the run in progress is a search run: its results carry locations (reset_host_results)
-    bool hits_run = false;                        // ... an all-occurrences run: its results carry occurrence lists instead
-    int panel_run = 0;                            // ... a panel run: the panel's size (its results carry panel hits instead), 0: not one
-    bool panel_matrix = false;                    // ... with QUICKED_PANEL_MATRIX
-    bool panel_all_run = false;                   // ... an all-occurrences panel run: its results carry the texts' occurrence lists instead
+    // the kind of search run in progress, i.e. what its results carry (reset_host_results): locations / occurrence lists / panel
+    // hits / the texts' occurrence lists; None: not a search run.  Set by run_batch and fetch_pending
+    enum class SearchKind { None, Best, All, Panel, PanelAll } search_kind = SearchKind::None;
+    int panel_members = 0;                        // Panel: the panel's size
+    bool panel_matrix = false;                    // ... and QUICKED_PANEL_MATRIX
     // whether a run formats and downloads CIGAR strings: the one place want_cigar / want_strings is derived
     bool want_strings(bool only_score) const { return !only_score && !(run_tags & QUICKED_TAG_NO_CIGAR); }
     int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // of the run being queued / fetched (copied to wr->counters at its end)

@@ -200,6 +200,14 @@ QE_API quicked_status_t quicked_batch_run(quicked_batch_t* batch, const quicked_
     }, &arg);
 }
 
+// the parameter block of the runs that take none from the caller (bounded, search, panel): BANDED at the defaults
+static quicked_params_t banded_params(bool only_score) {
+    quicked_params_t p = quicked_default_params();
+    p.algo = BANDED;
+    p.only_score = only_score;
+    return p;
+}
+
 // Bounded distances: the arguments are checked before anything touches the device
 QE_API quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const int32_t* max_dist, int32_t max_dist_all,
                                                   int only_score, int sync) {
@@ -209,10 +217,7 @@ QE_API quicked_status_t quicked_batch_run_bounded(quicked_batch_t* batch, const 
         Arg* x = (Arg*)a;
         if (x->bd.max_dist) for (int64_t i = 0; i < B->n; ++i) if (x->bd.max_dist[i] < 0) return QUICKED_ERROR;
         if (!x->only_score && !x->sync) return QUICKED_UNIMPLEMENTED;      // CIGARs need the distances on the host first
-        quicked_params_t p = quicked_default_params();
-        p.algo = BANDED;
-        p.only_score = x->only_score != 0;
-        return run_batch(*B, p, x->sync != 0, &x->bd);
+        return run_batch(*B, banded_params(x->only_score != 0), x->sync != 0, &x->bd);
     }, &arg);
 }
 
@@ -236,10 +241,7 @@ QE_API quicked_status_t quicked_batch_run_search(quicked_batch_t* batch, int mod
         if (B->check) return QUICKED_UNIMPLEMENTED;                         // the in-run validator walks the text from its origin
         if (!x->only_score && !x->sync) return QUICKED_UNIMPLEMENTED;      // CIGARs need the locations on the host first
         if (!x->only_score && x->sr.eq) return QUICKED_UNIMPLEMENTED;      // the traceback compares raw bytes: its edit count would not be d
-        quicked_params_t p = quicked_default_params();
-        p.algo = BANDED;
-        p.only_score = x->only_score != 0;
-        return run_batch(*B, p, x->sync != 0, nullptr, &x->sr);
+        return run_batch(*B, banded_params(x->only_score != 0), x->sync != 0, nullptr, &x->sr);
     }, &arg);
 }
 
@@ -268,48 +270,67 @@ QE_API quicked_status_t quicked_batch_run_search_all(quicked_batch_t* batch, int
         if (tasks * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;      // the room for the stored occurrences
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
         if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the start pass is sized from a total the host reads
-        quicked_params_t p = quicked_default_params();
-        p.algo = BANDED;
-        p.only_score = true;
-        return run_batch(*B, p, true, nullptr, &x->sr);
+        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
     }, &arg);
 }
 
+// The getters of an all-occurrences run, pairs or panel: one implementation over the result fields named -- the counts found
+// [n], the offsets [n + 1], the stored occurrences.  -> the visible results if `found` says they are such a run's, else null
+using HostResults = quicked_batch::HostResults;
+static const HostResults* hit_results(quicked_batch_t* batch, std::vector<int32_t> HostResults::*found) {
+    if (!batch || batch->n == 0 || (batch->res[batch->vis].*found).size() != (size_t)batch->n) return nullptr;
+    return &batch->res[batch->vis];
+}
+static quicked_status_t hit_counts(quicked_batch_t* batch, std::vector<int32_t> HostResults::*found, std::vector<int64_t> HostResults::*off, int32_t* o_found, int32_t* o_stored) {
+    const HostResults* R = hit_results(batch, found);
+    if (!R) return QUICKED_ERROR;
+    if (o_found) memcpy(o_found, (R->*found).data(), (size_t)batch->n * sizeof(int32_t));
+    if (o_stored) for (int64_t i = 0; i < batch->n; ++i) o_stored[i] = (int32_t)((R->*off)[(size_t)i + 1] - (R->*off)[(size_t)i]);
+    return QUICKED_OK;
+}
+static int64_t hit_total(quicked_batch_t* batch, std::vector<int32_t> HostResults::*found, std::vector<int64_t> HostResults::*off) {
+    const HostResults* R = hit_results(batch, found);
+    return R ? (R->*off)[(size_t)batch->n] : -1;
+}
+template <class Occ>
+static quicked_status_t hit_lists(quicked_batch_t* batch, std::vector<int32_t> HostResults::*found, std::vector<int64_t> HostResults::*off, std::vector<Occ> HostResults::*occ,
+                                  Occ* o_hits, int64_t* o_off) {
+    const HostResults* R = hit_results(batch, found);
+    if (!R) return QUICKED_ERROR;
+    if (o_hits && !(R->*occ).empty()) memcpy(o_hits, (R->*occ).data(), (R->*occ).size() * sizeof(Occ));
+    if (o_off) memcpy(o_off, (R->*off).data(), ((size_t)batch->n + 1) * sizeof(int64_t));
+    return QUICKED_OK;
+}
+
 QE_API quicked_status_t quicked_batch_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return QUICKED_ERROR;
-    const auto& R = batch->res[batch->vis];
-    if (found) memcpy(found, R.found.data(), (size_t)batch->n * sizeof(int32_t));
-    if (stored) for (int64_t i = 0; i < batch->n; ++i) stored[i] = (int32_t)(R.hit_off[(size_t)i + 1] - R.hit_off[(size_t)i]);
-    return QUICKED_OK;
+    return hit_counts(batch, &HostResults::found, &HostResults::hit_off, found, stored);
 }
-
-QE_API int64_t quicked_batch_hit_total(quicked_batch_t* batch) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return -1;
-    return batch->res[batch->vis].hit_off[(size_t)batch->n];
-}
-
+QE_API int64_t quicked_batch_hit_total(quicked_batch_t* batch) { return hit_total(batch, &HostResults::found, &HostResults::hit_off); }
 QE_API quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t* hits, int64_t* hit_off) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].found.size() != (size_t)batch->n) return QUICKED_ERROR;
-    const auto& R = batch->res[batch->vis];
-    if (hits && !R.hits.empty()) memcpy(hits, R.hits.data(), R.hits.size() * sizeof(quicked_hit_t));
-    if (hit_off) memcpy(hit_off, R.hit_off.data(), ((size_t)batch->n + 1) * sizeof(int64_t));
-    return QUICKED_OK;
+    return hit_lists(batch, &HostResults::found, &HostResults::hit_off, &HostResults::hits, hits, hit_off);
 }
 
 // Panel search: the arguments are checked before anything touches the device
 static_assert(sizeof(quicked_panel_hit_t) == 24, "quicked_panel_hit_t is six int32 (k_panel_reduce writes it as such)");
 static_assert((int)QUICKED_PANEL_MAX_PATTERNS == (int)PANEL_MAX_PATTERNS && (int)QUICKED_PANEL_MAX_LEN == (int)PANEL_MAX_LEN, "the panel limits are qe_panel.h's");
+// what both panel entry points check of their arguments alike -> false: QUICKED_ERROR; too_long: a member beyond the register form
+static bool panel_args_ok(const quicked_batch_t* batch, int eq, int32_t n_patterns, const char* panel_pool, const int64_t* panel_off,
+                          const int32_t* panel_len, const int32_t* max_dist, int32_t max_dist_all, bool& too_long) {
+    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return false;
+    if (n_patterns < 1 || n_patterns > QUICKED_PANEL_MAX_PATTERNS || !panel_pool || !panel_off || !panel_len) return false;
+    too_long = false;
+    for (int32_t p = 0; p < n_patterns; ++p) {
+        if (panel_len[p] <= 0 || (max_dist && max_dist[p] < 0)) return false;
+        too_long = too_long || panel_len[p] > QUICKED_PANEL_MAX_LEN;
+    }
+    return true;
+}
 QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
                                                 const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
                                                 int32_t max_dist_all, int sync) {
     const int eq = search_mode_eq(mode & ~QUICKED_PANEL_MATRIX);
-    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
-    if (n_patterns < 1 || n_patterns > QUICKED_PANEL_MAX_PATTERNS || !panel_pool || !panel_off || !panel_len) return QUICKED_ERROR;
     bool too_long = false;
-    for (int32_t p = 0; p < n_patterns; ++p) {
-        if (panel_len[p] <= 0 || (max_dist && max_dist[p] < 0)) return QUICKED_ERROR;
-        too_long = too_long || panel_len[p] > QUICKED_PANEL_MAX_LEN;
-    }
+    if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, (mode & QUICKED_PANEL_MATRIX) != 0};
     struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, 0, eq, &pr}, too_long, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
@@ -319,10 +340,7 @@ QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
         if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the results are reduced and read at the run's end
-        quicked_params_t p = quicked_default_params();
-        p.algo = BANDED;
-        p.only_score = true;
-        return run_batch(*B, p, true, nullptr, &x->sr);
+        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
     }, &arg);
 }
 
@@ -347,14 +365,9 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
                                                     const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
                                                     int32_t max_dist_all, int32_t max_hits, int sync) {
     const int eq = search_mode_eq(mode);                                            // (QUICKED_PANEL_MATRIX is "any other bit" here)
-    if (!batch || eq < 0 || (!max_dist && max_dist_all < 0)) return QUICKED_ERROR;
-    if (n_patterns < 1 || n_patterns > QUICKED_PANEL_MAX_PATTERNS || !panel_pool || !panel_off || !panel_len) return QUICKED_ERROR;
-    if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     bool too_long = false;
-    for (int32_t p = 0; p < n_patterns; ++p) {
-        if (panel_len[p] <= 0 || (max_dist && max_dist[p] < 0)) return QUICKED_ERROR;
-        too_long = too_long || panel_len[p] > QUICKED_PANEL_MAX_LEN;
-    }
+    if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
+    if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
     struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr}, too_long, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
@@ -365,32 +378,16 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
         if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the start pass is sized from a total the host reads
-        quicked_params_t p = quicked_default_params();
-        p.algo = BANDED;
-        p.only_score = true;
-        return run_batch(*B, p, true, nullptr, &x->sr);
+        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
     }, &arg);
 }
 
 QE_API quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return QUICKED_ERROR;
-    const auto& R = batch->res[batch->vis];
-    if (found) memcpy(found, R.panel_found.data(), (size_t)batch->n * sizeof(int32_t));
-    if (stored) for (int64_t i = 0; i < batch->n; ++i) stored[i] = (int32_t)(R.panel_occ_off[(size_t)i + 1] - R.panel_occ_off[(size_t)i]);
-    return QUICKED_OK;
+    return hit_counts(batch, &HostResults::panel_found, &HostResults::panel_occ_off, found, stored);
 }
-
-QE_API int64_t quicked_batch_panel_hit_total(quicked_batch_t* batch) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return -1;
-    return batch->res[batch->vis].panel_occ_off[(size_t)batch->n];
-}
-
+QE_API int64_t quicked_batch_panel_hit_total(quicked_batch_t* batch) { return hit_total(batch, &HostResults::panel_found, &HostResults::panel_occ_off); }
 QE_API quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_occ_t* hits, int64_t* hit_off) {
-    if (!batch || batch->n == 0 || batch->res[batch->vis].panel_found.size() != (size_t)batch->n) return QUICKED_ERROR;
-    const auto& R = batch->res[batch->vis];
-    if (hits && !R.panel_occ.empty()) memcpy(hits, R.panel_occ.data(), R.panel_occ.size() * sizeof(quicked_panel_occ_t));
-    if (hit_off) memcpy(hit_off, R.panel_occ_off.data(), ((size_t)batch->n + 1) * sizeof(int64_t));
-    return QUICKED_OK;
+    return hit_lists(batch, &HostResults::panel_found, &HostResults::panel_occ_off, &HostResults::panel_occ, hits, hit_off);
 }
 
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {

@@ -37,7 +37,8 @@
 #include "qe_panel.h"
 #include "qe_tags.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
-// without a GPU names tests/native/hip_stub/qe_kernels_stub.h here -- tests/test_host_sanitizers.py; never set in the product)
+// without a GPU names tests/native/hip_stub/qe_kernels_stub.h here, which holds every host stand-in of a kernel -- none lives
+// in the product's sources; tests/native_build.py: build_host; never set in the product)
 #ifndef QE_KERNELS_HEADER
 #define QE_KERNELS_HEADER "qe_kernels.hip"
 #endif
@@ -280,7 +281,7 @@ static void quicked_classic(quicked_batch& B, Context& C, const quicked_params_t
         for (size_t t : idx2) B.note_pair(L.pair[t], 6, 1);
         if (!idx2.empty()) {
             L2.pad();
-            if (!B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+            ensure_reversed(B, C);
             StageResult F, V;
             const int W = (int)p.window_size, O = (int)p.overlap_size;
             qe_timer_start(tl_timers.windowed_l);
@@ -669,6 +670,26 @@ static int rotation_depth(int64_t n, int floor_sets = 5) {
 
 static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 
+// The one read-back of an all-occurrences run, pairs or panel: found / offsets / the stored occurrences into the result vectors
+// named, the smallest score as every searched pair's score, the block steps of both passes into counter 0
+template <class Occ>
+static void fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
+    const size_t n = (size_t)B.n, nh = (size_t)HO.total;
+    std::vector<int32_t> best; std::vector<u32> adv, adv2;
+    occ.resize(nh);
+    {
+        FetchBatch fb(C);
+        fb.add(found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
+        fb.add(off, (const int64_t*)HO.d_off, n + 1);
+        fb.add(adv, (const u32*)HO.d_adv, HO.task_pair.size());
+        if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
+        fb.add_bytes(occ.data(), HO.d_hits, nh * sizeof(Occ));
+        fb.sync();
+    }
+    B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
+    for (const int32_t pr : HO.task_pair) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+}
+
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd, const SearchRun* sr) {
     double tr_last = now_ms();
     tl_device = B.device;
@@ -808,11 +829,11 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     }
     B.only_score_run = p.only_score;
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
-    B.search_run = sr != nullptr && sr->max_hits == 0 && !sr->panel;
-    B.hits_run = sr != nullptr && sr->max_hits > 0 && !sr->panel;
-    B.panel_all_run = sr != nullptr && sr->max_hits > 0 && sr->panel;
-    B.panel_run = (sr && sr->panel && !B.panel_all_run) ? sr->panel->n_patterns : 0;
-    B.panel_matrix = B.panel_run && sr->panel->matrix;
+    using Kind = quicked_batch::SearchKind;
+    const Kind kind = !sr ? Kind::None : sr->panel ? (sr->max_hits > 0 ? Kind::PanelAll : Kind::Panel) : (sr->max_hits > 0 ? Kind::All : Kind::Best);
+    B.search_kind = kind;
+    B.panel_members = kind == Kind::Panel ? sr->panel->n_patterns : 0;
+    B.panel_matrix = kind == Kind::Panel && sr->panel->matrix;
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -877,21 +898,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // All-occurrences panel run (sync only): found / smallest score / offsets per text and the stored occurrences, already in
         // the order of the texts and (pattern, text_end) within a text, in one read-back
         enter_a();
-        const PanelHitsOut HO = run_search_panel_hits(B, C, *sr);
-        const size_t n = (size_t)B.n, nh = (size_t)HO.total;
-        std::vector<int32_t> best; std::vector<u32> adv, adv2;
-        B.wr->panel_occ.resize(nh);
-        {
-            FetchBatch fb(C);
-            fb.add(B.wr->panel_found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
-            fb.add(B.wr->panel_occ_off, (const int64_t*)HO.d_off, n + 1);
-            fb.add(adv, (const u32*)HO.d_adv, HO.text.size());
-            if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
-            fb.add_bytes(B.wr->panel_occ.data(), HO.d_hits, nh * sizeof(quicked_panel_occ_t));
-            fb.sync();
-        }
-        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
-        for (const int32_t pr : HO.text) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+        fetch_hits(B, C, run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
         ret = QUICKED_OK;
     } else if (sr && sr->panel) {
         // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every
@@ -915,21 +922,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // All-occurrences run (sync only): found / smallest score / offsets per pair and the stored occurrences, already in the
         // order of the pairs, in one read-back
         enter_a();
-        const SearchHitsOut HO = run_search_hits(B, C, SLs, sr->mode, sr->max_hits, sr->eq);
-        const size_t n = (size_t)B.n, nh = (size_t)HO.total;
-        std::vector<int32_t> best; std::vector<u32> adv, adv2;
-        B.wr->hits.resize(nh);
-        {
-            FetchBatch fb(C);
-            fb.add(B.wr->found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
-            fb.add(B.wr->hit_off, (const int64_t*)HO.d_off, n + 1);
-            fb.add(adv, (const u32*)HO.d_adv, HO.task_pair.size());
-            if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
-            fb.add_bytes(B.wr->hits.data(), HO.d_hits, nh * sizeof(quicked_hit_t));
-            fb.sync();
-        }
-        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
-        for (const int32_t pr : HO.task_pair) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+        fetch_hits(B, C, run_search_hits(B, C, SLs, sr->mode, sr->max_hits, sr->eq), B.wr->found, B.wr->hit_off, B.wr->hits);
         ret = QUICKED_OK;
     } else if (sr) {
         // Search run: the forward pass and -- INFIX -- the start pass leave {d, text_start, text_end} per task on the device;
@@ -1160,9 +1153,7 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     B.pending_fetch.reset();
     HIP_CHECK(B.done_sync(F.parity));
     C.phase_u();
-    B.search_run = F.search;
-    B.hits_run = false;                        // (all-occurrences runs are never queued)
-    B.panel_run = 0; B.panel_matrix = false; B.panel_all_run = false;      // (nor are panel runs)
+    B.search_kind = F.search ? quicked_batch::SearchKind::Best : quicked_batch::SearchKind::None;      // (all-occurrences and panel runs are never queued)
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
     if (F.kind == 1) {

@@ -979,7 +979,6 @@ __global__ __launch_bounds__(256) void k_reverse_planes(RevArgs A) {
 // lanes make one 64-base row -- with every byte classified through the 32-entry nibble table of iupac_mask (two 64-bit
 // constants).  The filler past a sequence's end is byte 0: the empty set, zero planes.
 // ===========================================================================
-#define QE_HAVE_K_SEARCH_IUPAC 1
 __global__ __launch_bounds__(256) void k_pack_iupac(IupacPackArgs A) {
     const int lane = threadIdx.x & 63;
     const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1106,7 +1105,7 @@ __device__ __forceinline__ GroupWs group_ws(uint8_t* ws, int64_t off, int ns, in
 // LDS (score-only, the first launch of a two-pass run whose bands fit: launch_banded_narrow): Pv, Mv and scores[] of a wave
 // live in its slice of the workgroup's LDS instead of the group workspace -- scores[] as a ring (qe_types.h: score_lds_*).
 // Same walk, same values; the kernel then has global loads only (the planes), and nothing waits behind a store.
-#define QE_HAVE_K_BANDED_LDS 1
+constexpr bool QE_K_BANDED_LDS = true;                // the LDS form below exists (the host-only build's kernels header says false)
 template <bool FILL, bool LDS = false>
 __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
     static_assert(!(FILL && LDS), "the fill's state stays in the group workspace");
@@ -1388,7 +1387,6 @@ template __global__ void k_banded<false, true>(BandedArgs);
 // A lane whose tracked value has passed its bound is decided (values along a diagonal never decrease) and stops; the wave
 // leaves the column loop when all its lanes are decided or done.  Whole pairs only (p0 = t0 = 0).
 // ===========================================================================
-#define QE_HAVE_K_BOUNDED_DIAG 1
 __global__ __launch_bounds__(256) void k_bounded_diag(BoundedArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
     if (g * 64 >= A.T.ntasks) return;
@@ -1453,7 +1451,6 @@ __global__ __launch_bounds__(256) void k_bounded_threshold(int nt, const int32_t
 // ===========================================================================
 // Eq: the equality (qe_search.h) -- SearchEq3 over the batch's three planes, or SearchEqIupac over the four membership planes
 // a flagged run packs (A.P.pl_p / pl_t then point at those; the offsets stay the three-plane ones, Eq::offset maps them).
-#define QE_HAVE_K_SEARCH 1
 template <int NB, class Eq = SearchEq3>
 __global__ __launch_bounds__(256) void k_search(SearchArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
@@ -1534,7 +1531,6 @@ template __global__ void k_search<4, SearchEqIupac>(SearchArgs);
 // the end-position scan -- the same stores, the same group layout, the bound kept for the whole text, no early exit.  A lane
 // emits an occurrence when row m rises out of a valley (rarely more than a few per text): one 8-byte store into its own
 // stretch of `raw`, never past max_hits entries (SearchHitSink::cap); a lane without a valid task has cap 0 and a null sink.
-#define QE_HAVE_K_SEARCH_HITS 1
 template <int NB, class Eq = SearchEq3>
 __global__ __launch_bounds__(256) void k_search_hits(SearchHitsArgs X) {
     const SearchArgs& A = X.S;
@@ -1632,7 +1628,6 @@ __global__ __launch_bounds__(256) void k_hits_finish(int64_t total, const int32_
 // keeper per (slice, text), [field][slice][slot] so that a wave's stores are contiguous rows, and with the matrix wanted every
 // member's {score, end}.  No workspace, no task list.
 // ===========================================================================
-#define QE_HAVE_K_SEARCH_PANEL 1
 template <class Eq>
 __global__ __launch_bounds__(256) void k_search_panel(PanelArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
@@ -1687,7 +1682,6 @@ __global__ __launch_bounds__(256) void k_panel_finish(int nslots, const int32_t*
 // up to four blocks, the SearchLane, the scan state and its sink.  The bound stays for the whole text and no lane leaves early.
 // A lane stores only when row m rises out of a valley: one 12-byte record into the stretch of its own (slice, slot), never
 // past max_hits of them; a lane without a text has cap 0 and a null sink.  No workspace, no task list.
-#define QE_HAVE_K_PANEL_HITS 1
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_hits(PanelHitsArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
@@ -4662,7 +4656,6 @@ __global__ __launch_bounds__(256) void k_apply_cutoffs(int nt, int32_t* cutoff, 
 // BandEd score-only in two passes (NarrowArgs, qe_types.h): what runs between and around the two k_banded<false> launches.
 // Blocks of 256 threads = four waves; every wave takes part as a whole (no early return before the ballots).
 // ===========================================================================
-#define QE_HAVE_K_NARROW 1
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -5106,7 +5099,6 @@ __global__ __launch_bounds__(64) void k_check_segs(SegCheckArgs C) {
 // and the MD string from the traceback's runs.  WRITE = false counts -- statistics and every string's length, which
 // k_scan_offsets turns into offsets --, WRITE = true writes the strings.  Statistics alone are one pass.
 // ===========================================================================
-#define QE_HAVE_K_TAGS 1
 // the count pass's verdict on one alignment (lane form: its lane; wave form: lane 0)
 __device__ __forceinline__ void tags_store_counts(const SegTagArgs& T, int i, bool bad, const TagStats& s, int64_t md_len, int m) {
     tag_store_counts(T.want_stats ? T.o_stats + i : nullptr, T.want_md ? T.o_md_len + i : nullptr, T.o_md_bad, bad, s, md_len, m);

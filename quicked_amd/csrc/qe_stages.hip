@@ -2,7 +2,8 @@
 // Launch shape of the lane-per-alignment kernels, task lists and per-group workspace layouts, and the stage runners --
 // BandEd score-only in its three forms (one lane / G lanes / one wave per alignment), WindowEd, the CIGAR formatter, and
 // the align step (bpm_compute_matrix_hirschberg, bpm_hirschberg.c:33-270) as a level-by-level work list.  Every runner
-// returns with its kernels enqueued on C.stream.
+// returns with its kernels enqueued on C.stream.  Every k_* named here is the kernels header's: qe_kernels.hip, or, in the
+// host-only test build, the stand-ins of tests/native/hip_stub/qe_kernels_stub.h.
 #pragma once
 
 namespace qe {
@@ -48,6 +49,19 @@ static void launch_groups(Context& C, Kernel kernel, const Args& args, size_t ng
     HIP_CHECK(hipGetLastError());             // a rejected launch (block shape, LDS) must not pass for zeroed results
 }
 
+// The launches between the construction and end() are timed as one stretch of `kind` (Context::kernel_events,
+// quicked_batch_kernel_times) on the stream current at the construction; kind < 0, or no event pair left: the launches alone
+struct TimedLaunches {
+    hipStream_t s; hipEvent_t last = nullptr;
+    TimedLaunches(Context& C, int kind) : s(C.stream) {
+        auto* ke = kind >= 0 ? C.kernel_events(kind) : nullptr;
+        if (!ke) return;
+        HIP_CHECK(hipEventRecord(ke->first, s));
+        last = ke->second;
+    }
+    void end() { if (last) HIP_CHECK(hipEventRecord(last, s)); }
+};
+
 // flags_of_reversed: the reversed pack ORs the flags in as the forward one does (quicked_debug_pack; no run asks for it)
 static void launch_pack(quicked_batch& B, Context& C, bool reversed, bool flags_of_reversed = false) {
     if (B.packed) {                       // forward planes are the input; reversed ones come from them
@@ -72,6 +86,13 @@ static void launch_pack(quicked_batch& B, Context& C, bool reversed, bool flags_
     a.set[0] = PackSet{B.d_asc_p, B.d_p_off, B.d_p_len, reversed ? B.d_pl_pr[q] : B.d_pl_p[q], B.d_plp_off};
     a.set[1] = PackSet{B.d_asc_t, B.d_t_off, B.d_t_len, reversed ? B.d_pl_tr[q] : B.d_pl_t[q], B.d_plt_off};
     hipLaunchKernelGGL(k_pack, dim3(2 * blocks), dim3(256), 0, C.stream, a);
+}
+
+// the reversed planes of the run's plane set, packed once per parity
+static void ensure_reversed(quicked_batch& B, Context& C) {
+    if (B.have_rev[B.parity]) return;
+    launch_pack(B, C, true);
+    B.have_rev[B.parity] = true;
 }
 
 // ---------------------------------------------------------------------------
@@ -278,10 +299,9 @@ static ScoreLaunch launch_banded_score(quicked_batch& B, Context& C, const TaskL
     BandedArgs a = score_args(B, S, reversed);
     a.lane_rel = sw(Sw::LaneRel);
     a.fill_geom = fill_geom ? 1 : 0;
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     return S;
 }
 
@@ -376,53 +396,6 @@ static void narrow_report(Context* C, int cls, const std::vector<unsigned long l
     if (paid) C->narrow_off[cls] = 0; else C->narrow_off[cls].compare_exchange_strong(unknown, 1);
 }
 
-#ifndef QE_HAVE_K_NARROW
-// a kernels header without it (the host-only build's stand-ins): the same phases on the host
-static void k_narrow(NarrowArgs A) {
-    const int nt = A.T.ntasks;
-    if (A.phase == 0) {
-        for (int q = 0; q < QE_NARROW_STAT; ++q) A.stat[q] = 0;
-        for (int g = 0; g < nt; g += 64) {
-            int sg = 0;
-            if (A.q > 0)
-                for (int t = g; t < std::min(nt, g + 64); ++t)
-                    if (A.T.pair[t] >= 0) sg = std::max(sg, narrow_fit_slots(A.T.m[t], A.T.n[t], A.T.cutoff[t], narrow_rhat(A.q, A.T.cutoff[t])));
-            for (int t = g; t < std::min(nt, g + 64); ++t) {
-                A.q_pair[t] = -1;
-                A.cut1[t] = (A.T.pair[t] >= 0) ? narrow_fit_lane(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.q, sg) : A.T.cutoff[t];
-                if (A.prune1) A.prune1[t] = (A.T.pair[t] >= 0) ? narrow_prune(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.cut1[t], A.qp) : A.cut1[t];
-            }
-        }
-    } else if (A.phase == 1) {
-        for (int t = 0; t < nt; ++t) {
-            if (A.T.pair[t] < 0 || A.cut1[t] == A.T.cutoff[t]) continue;
-            A.stat[1] += A.adv[t]; ++A.stat[3];
-            if (narrow_accepts_pruned(A.T.m[t], A.T.n[t], A.cut1[t], A.T.cutoff[t], A.prune1 ? A.prune1[t] : A.cut1[t], A.score[t])) {
-                A.stat[4] = std::max(A.stat[4], (unsigned long long)std::max(0, narrow_ratio(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.score[t])));
-                continue;
-            }
-            const int j = (int)A.stat[0]++;
-            A.q_pair[j] = A.T.pair[t]; A.q_p0[j] = A.T.p0[t]; A.q_m[j] = A.T.m[t]; A.q_t0[j] = A.T.t0[t]; A.q_n[j] = A.T.n[t];
-            A.q_cutoff[j] = A.T.cutoff[t]; A.q_tfin[j] = A.T.tfin[t]; A.q_src[j] = t;
-        }
-    } else if (A.phase == 2) {
-        for (int j = 0; j < (int)A.stat[0]; ++j) {
-            A.score[A.q_src[j]] = A.q_score[j]; A.adv[A.q_src[j]] += A.q_adv[j]; A.stat[2] += A.q_adv[j];
-            const int ratio = narrow_ratio(A.q_m[j], A.q_n[j], A.q_cutoff[j], A.q_score[j]);
-            if (ratio >= 0) { ++A.stat[5]; A.stat[4] = std::max(A.stat[4], (unsigned long long)ratio); }
-        }
-    } else {
-        for (int t = 0; t < nt; ++t) {
-            if (A.T.pair[t] < 0) continue;
-            const int src = (((t >> 6) * A.stride) << 6) + (t & 63);
-            A.stat[1] += A.q_adv[t]; ++A.stat[3];
-            if (!narrow_accepts(A.T.m[t], A.T.n[t], A.T.cutoff[t], A.main_cutoff[src], A.q_score[t])) { ++A.stat[0]; A.stat[2] += A.adv[src]; }
-            A.adv[src] += A.q_adv[t];
-        }
-    }
-}
-#endif
-
 // every group: the tallest band, the most rows and the most chunks of the list
 static BandLayout narrow_uniform(BandLayout lay) {
     int ns = 3, nr = 4, nch = 2;
@@ -464,10 +437,9 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
     HIP_CHECK(hipEventRecord(C.ev_fork, main_s)); HIP_CHECK(hipStreamWaitEvent(side, C.ev_fork, 0));
     BandedArgs a = score_args(B, S, reversed);
     a.lane_rel = sw(Sw::LaneRel);
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, main_s));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, main_s));
+    tl.end();
     C.stream = side;
     BandedArgs b = score_args(B, P, reversed);
     b.lane_rel = a.lane_rel;
@@ -489,14 +461,10 @@ static ScoreLaunch launch_banded_probe(quicked_batch& B, Context& C, const TaskL
 // workgroup's four slices are 72 KB: two workgroups still share a CU (launch_groups).  QE_SCORE_LDS = 0: never, 1: whatever
 // the list's size (by default a list of a group per SIMD, as the two passes themselves: smaller launches were not measured).
 static int score_lds_slots(const Context& C, const TaskList& L, int bound) {
-#ifndef QE_HAVE_K_BANDED_LDS
-    (void)C; (void)L; (void)bound;
-    return 0;                                        // a kernels header without the form (the host-only build's stand-ins)
-#else
+    if (!QE_K_BANDED_LDS) return 0;                  // the host-only build's kernels header declines the form
     const int mode = sw(Sw::ScoreLds);
     if (mode == 0 || (mode != 1 && (size_t)L.ngroups() < (size_t)chip(C.device).simds)) return 0;
     return score_lds_fits(bound) ? bound : 0;
-#endif
 }
 
 static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q, int qp, int slots1) {
@@ -519,8 +487,7 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     S2.T.v.pair = x.q_pair; S2.T.v.p0 = x.q_p0; S2.T.v.m = x.q_m; S2.T.v.t0 = x.q_t0; S2.T.v.n = x.q_n;
     S2.T.v.cutoff = x.q_cutoff; S2.T.v.tfin = x.q_tfin;
     const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     x.phase = 0;
     hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
     BandedArgs a = score_args(B, S, reversed);
@@ -530,11 +497,8 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     a.lds_slots = score_lds_slots(C, L, slots1);
     a.score_tall = (a.lds_slots && sw(Sw::ScoreTall) != 0) ? 1 : 0;      // tall passes: the LDS form only
     if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots), tall passes %s\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots, a.score_tall ? "on" : "off");
-#ifdef QE_HAVE_K_BANDED_LDS
     if (a.lds_slots) launch_groups(C, k_banded<false, true>, a, L.ngroups(), 8, (size_t)score_lds_bytes(a.lds_slots));
-    else
-#endif
-    launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
+    else launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
     x.phase = 1;
     hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
     BandedArgs b = score_args(B, S2, reversed);
@@ -543,7 +507,7 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     x.phase = 2;
     hipLaunchKernelGGL(k_narrow, grid, block, 0, C.stream, x);
     HIP_CHECK(hipGetLastError());
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     return S;
 }
 
@@ -626,8 +590,7 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
     a.o_score = S.O.score; a.o_first = S.O.first; a.o_last = S.O.last; a.o_posv = S.O.posv; a.o_adv = S.O.adv;
     a.o_maxrow = S.O.len; a.o_abort = S.O.hew;
     HIP_CHECK(hipMemsetAsync(S.O.hew, 0, S.nt * sizeof(int32_t), C.stream));
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     // band state on chip where a wave's tasks fit its share of the LDS (k_banded_coop_lds); QE_COOP_LDS = 0: never
     CoopLdsArgs x;
     memset(&x, 0, sizeof(x));
@@ -649,7 +612,7 @@ static ScoreLaunch launch_banded_coop(quicked_batch& B, Context& C, const TaskLi
     b.only_if = S.O.hew;
     b.lane_rel = sw(Sw::LaneRel);
     launch_groups(C, k_banded<false>, b, L.ngroups(), 8, 0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     return S;
 }
 
@@ -741,10 +704,9 @@ static ScoreLaunch launch_banded_wave(quicked_batch& B, Context& C, const TaskLi
     S.O = take_out(C, S.nt);
     BandedArgs a = score_args(B, S, reversed);       // no group workspace
     a.fill_multi = 0; a.lane_rel = 0;
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;       // timed = kind + 1 (Context::kernel_events)
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     launch_groups(C, k_banded_wave, a, S.nt, 4, 0);                     // one wave per task
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     return S;
 }
 
@@ -766,14 +728,13 @@ static ScoreLaunch launch_banded_sys(quicked_batch& B, Context& C, const TaskLis
     a.fill_geom = fill_geom ? 1 : 0;
     a.o_abort = S.O.hew;
     a.lane_rel = sw(Sw::LaneRel);
-    auto* ke = timed ? C.kernel_events(timed - 1) : nullptr;
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, timed - 1);       // timed = kind + 1, 0 = not timed
     if (lg == 4) launch_groups(C, k_banded_sys<4, false>, with_prio(a), S.nt / 4, 4, 0, false, (size_t)40 * 1024);
     else launch_groups(C, k_banded_sys<6, false>, with_prio(a), S.nt, 4, 0, false, (size_t)40 * 1024);
     a.only_if = S.O.hew;
     if (lg == 6 && max_nsl > 63) launch_groups(C, k_banded_sys2<false>, with_prio(a), S.nt, 4, 0, false, (size_t)40 * 1024);      // bands of 64 .. 127 slots
     launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     return S;
 }
 // whole-text passes on few tasks (QuickEd's stage-3 doubling rounds on the pairs a run left, a BandEd score-only call on one
@@ -929,20 +890,6 @@ static void run_fill_score(quicked_batch& B, Context& C, const TaskList& L, Stag
 // ---------------------------------------------------------------------------
 // Bounded runs (quicked_batch_run_bounded): per task "the distance if it is within the task's bound, else -1".
 // ---------------------------------------------------------------------------
-#ifndef QE_HAVE_K_BOUNDED_DIAG
-// a kernels header without the two (the host-only build's stand-ins): the same source on the host
-static void k_bounded_diag(BoundedArgs A) {
-    for (int t = 0; t < A.T.ntasks; ++t) {
-        const int pr = A.T.pair[t];
-        if (pr < 0) continue;
-        A.o_score[t] = bounded_diag_pair(A.P.pl_p + A.P.pl_p_off[pr], A.T.m[t], A.P.pl_t + A.P.pl_t_off[pr], A.T.n[t], A.T.cutoff[t]);
-        A.o_adv[t] = (u32)A.T.n[t];
-    }
-}
-static void k_bounded_threshold(int nt, const int32_t* score, const u32* adv, const int32_t* bound, int32_t* o_score, u32* o_adv) {
-    for (int t = 0; t < nt; ++t) { o_score[t] = bounded_answer(score[t], bound[t]); o_adv[t] = adv[t]; }
-}
-#endif
 
 // Which form takes a task.  QE_BOUNDED_DIAG = 1: the diagonal word (k_bounded_diag) wherever its precondition holds --
 // bounded_diag_takes: min(bound, max(m, n)) <= 63; 0: never.  Unset, the library's choice: the diagonal word for pairs of
@@ -980,10 +927,9 @@ static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList
         const DevTasks T = upload_tasks(Ld, C);
         BoundedArgs a{};
         a.P = pair_view(B, false); a.T = T.v; a.o_score = O.d_score; a.o_adv = O.d_adv;
-        auto* ke = C.kernel_events(3);
-        if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+        TimedLaunches tl(C, 3);
         launch_groups(C, k_bounded_diag, a, (size_t)Ld.ngroups(), 4, 0);
-        if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+        tl.end();
     }
     if (ng) {
         PendingFetch G;                                // where the pass leaves its scores and block-advance counts
@@ -1001,118 +947,6 @@ static BoundedOut run_bounded_score(quicked_batch& B, Context& C, const TaskList
 // ---------------------------------------------------------------------------
 // Search runs (quicked_batch_run_search): per task {d, text_start, text_end}, or {-1, -1, -1} = beyond.
 // ---------------------------------------------------------------------------
-#ifndef QE_HAVE_K_SEARCH
-// a kernels header without it (the host-only build's stand-ins): the same source on the host, task by task, in the
-// layout and with the arguments of the device form
-template <int NB, class Eq = SearchEq3>
-static void k_search(SearchArgs A) {
-    for (int t = 0; t < A.T.ntasks; ++t) {
-        const int pair = A.T.pair[t];
-        if (pair < 0) continue;
-        const int g = t >> 6, lane = t & 63, m = A.T.m[t];
-        int n = A.T.n[t], bound = A.T.cutoff[t], in_end = 0;
-        int64_t tbit = 0;
-        bool valid = true;
-        if (A.in_score) {
-            bound = A.in_score[t]; in_end = A.in_end[t];
-            valid = bound >= 0 && in_end >= 1 && in_end <= n;
-            tbit = n - in_end; n = in_end;
-        }
-        const int nbg = NB == 0 ? A.g_nb[g] : NB;
-        valid = valid && search_blocks(m) <= nbg;
-        SearchLane L;
-        search_lane_init(L, m, valid ? n : 0, A.mode, valid ? bound : 0, A.flags);
-        const u64* pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]);
-        const u64* tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]);
-        if (valid) {
-            if constexpr (NB > 0) {
-                SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
-                for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
-                R.load(pp, m);
-                search_run<NB>(R, L, tp, tbit);
-            } else {
-                u64* base = (u64*)(A.ws + A.g_ws_off[g]);
-                SearchWsStoreOf<Eq> W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
-                search_run<0>(W, L, tp, tbit);
-            }
-        }
-        int32_t score, end;
-        search_answer(L, score, end);
-        if (!valid) { score = -1; end = -1; }
-        if (A.in_score) {
-            if (valid) A.o_start[t] = (score == bound) ? in_end - end : -1;
-        } else {
-            A.o_score[t] = score; A.o_end[t] = end;
-            A.o_start[t] = (score >= 0 && A.mode == SEARCH_PREFIX) ? 0 : -1;
-        }
-        A.o_adv[t] += L.steps;
-    }
-}
-#endif
-
-#ifndef QE_HAVE_K_SEARCH_HITS
-// ... and of the all-occurrences kernels (SearchHitsArgs, HitExpandArgs)
-template <int NB, class Eq = SearchEq3>
-static void k_search_hits(SearchHitsArgs X) {
-    const SearchArgs& A = X.S;
-    for (int t = 0; t < A.T.ntasks; ++t) {
-        const int pair = A.T.pair[t];
-        if (pair < 0) continue;
-        const int g = t >> 6, lane = t & 63, m = A.T.m[t], n = A.T.n[t], bound = A.T.cutoff[t];
-        const int nbg = NB == 0 ? A.g_nb[g] : NB;
-        if (bound < 0 || search_blocks(m) > nbg) continue;
-        SearchLane L;
-        search_lane_init(L, m, n, A.mode, bound, 0);
-        SearchHitScan H;
-        H.init(L, reinterpret_cast<SearchHit*>(X.raw) + (int64_t)t * X.max_hits, 1, X.max_hits);
-        const u64* pp = A.P.pl_p + Eq::offset(A.P.pl_p_off[pair]);
-        const u64* tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]);
-        if constexpr (NB > 0) {
-            SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
-            for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
-            R.load(pp, m);
-            search_run_hits<NB>(R, L, H, tp, 0);
-        } else {
-            u64* base = (u64*)(A.ws + A.g_ws_off[g]);
-            SearchWsStoreOf<Eq> W{base + lane, base + (int64_t)nbg * 64 + lane, (int32_t*)(base + (int64_t)2 * nbg * 64) + lane, 64, pp, m};
-            search_run_hits<0>(W, L, H, tp, 0);
-        }
-        X.o_found[pair] = H.found; X.o_best[pair] = H.best; X.o_len[pair] = H.sink.count - 1;
-        A.o_adv[t] += L.steps;
-    }
-}
-static void k_hits_expand(HitExpandArgs A) {
-    for (int t = 0; t < A.T.ntasks; ++t) {
-        const int pair = A.T.pair[t];
-        if (pair < 0) continue;
-        const int stored = std::min(A.len[pair] + 1, A.max_hits), m = A.T.m[t], n = A.T.n[t];
-        const int32_t* raw = A.raw + 2 * (int64_t)t * A.max_hits;
-        for (int i = 0; i < stored; ++i) {
-            const int64_t j = A.off[pair] + i;
-            const int32_t end = raw[2 * i], score = raw[2 * i + 1];
-            int32_t task_n, in_end, base;
-            search_hit_task(m, n, end, score, task_n, in_end, base);
-            A.hits[3 * j] = A.infix ? base : 0; A.hits[3 * j + 1] = end; A.hits[3 * j + 2] = score;
-            if (A.infix) { A.o_pair[j] = pair; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = score; A.o_end[j] = in_end; }
-        }
-    }
-}
-static void k_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) {
-    for (int64_t j = 0; j < total; ++j) hits[3 * j] = o_start[j] < 0 ? -1 : hits[3 * j] + o_start[j];
-}
-#endif
-
-#ifndef QE_HAVE_K_SEARCH_IUPAC
-// ... and of the two producers of a flagged run's four planes: the scalar code of qe_iupac.h, so the host-only build of a
-// flagged run gives true answers (of an ASCII batch; a packed one derives them from the zeros k_unpack_wire's stand-in leaves)
-static void k_pack_iupac(IupacPackArgs A) {
-    for (int i = 0; i < A.nseq; ++i)
-        iupac_pack(A.asc + A.asc_off[i], A.len[i], A.reverse != 0, A.acgt_only != 0, A.planes + iupac_offset(A.pl_off[i]));
-}
-static void k_planes_iupac(IupacPlanesArgs A) {
-    for (int i = 0; i < A.nseq; ++i) iupac_from_planes3(A.src + A.pl_off[i], A.len[i], A.n_empty != 0, A.dst + iupac_offset(A.pl_off[i]));
-}
-#endif
 
 // Which form takes a pattern of nb blocks: the register form's instantiation (1, 2 or 4 blocks), or 0 = the workspace form.
 // QE_SEARCH_FORM = 0: the workspace form always; 1: the register form wherever it applies (up to QE_SEARCH_REG_BLOCKS
@@ -1199,29 +1033,33 @@ static size_t search_iupac_bytes(const quicked_batch& B, int eq, int mode) {    
     const size_t one = (iupac_offset((int64_t)B.pl_p_words) + iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64) + 512;
     return mode == SEARCH_INFIX ? 2 * one : one;
 }
-static PairView search_planes(quicked_batch& B, Context& C, int eq, bool reversed) {
-    if (!eq) return pair_view(B, reversed);
-    if (B.packed && reversed && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
-    PairView v = pair_view(B, reversed);
-    u64* pl_p = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_p_words) + 8);
-    u64* pl_t = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_t_words) + 8);
-    const int blocks = (int)((B.n + 3) / 4);
+// one side's four planes: the patterns' or the texts'.  QUICKED_SEARCH_IUPAC_PATTERN (eq 2) narrows the texts alone: ACGT only
+// (k_pack_iupac's acgt_only), N the empty set (k_planes_iupac's n_empty)
+static u64* iupac_side_planes(quicked_batch& B, Context& C, int eq, bool reversed, bool text) {
+    if (B.packed && reversed) ensure_reversed(B, C);
+    const PairView v = pair_view(B, reversed);
+    u64* pl = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)(text ? B.pl_t_words : B.pl_p_words)) + 8);
+    const int blocks = (int)((B.n + 3) / 4), narrow = (text && eq == 2) ? 1 : 0;
     if (B.packed) {
         IupacPlanesArgs a;
-        a.nseq = (int32_t)B.n;
-        a.src = v.pl_p; a.dst = pl_p; a.pl_off = B.d_plp_off; a.len = B.d_p_len; a.n_empty = 0;
-        hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
-        a.src = v.pl_t; a.dst = pl_t; a.pl_off = B.d_plt_off; a.len = B.d_t_len; a.n_empty = eq == 2 ? 1 : 0;
+        a.nseq = (int32_t)B.n; a.n_empty = narrow;
+        a.src = text ? v.pl_t : v.pl_p; a.dst = pl; a.pl_off = text ? B.d_plt_off : B.d_plp_off; a.len = text ? B.d_t_len : B.d_p_len;
         hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
     } else {
         IupacPackArgs a;
-        a.nseq = (int32_t)B.n; a.reverse = reversed ? 1 : 0;
-        a.asc = B.d_asc_p; a.asc_off = B.d_p_off; a.len = B.d_p_len; a.planes = pl_p; a.pl_off = B.d_plp_off; a.acgt_only = 0;
-        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
-        a.asc = B.d_asc_t; a.asc_off = B.d_t_off; a.len = B.d_t_len; a.planes = pl_t; a.pl_off = B.d_plt_off; a.acgt_only = eq == 2 ? 1 : 0;
+        a.nseq = (int32_t)B.n; a.reverse = reversed ? 1 : 0; a.acgt_only = narrow;
+        a.asc = text ? B.d_asc_t : B.d_asc_p; a.asc_off = text ? B.d_t_off : B.d_p_off; a.len = text ? B.d_t_len : B.d_p_len;
+        a.planes = pl; a.pl_off = text ? B.d_plt_off : B.d_plp_off;
         hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
     }
     HIP_CHECK(hipGetLastError());
+    return pl;
+}
+static PairView search_planes(quicked_batch& B, Context& C, int eq, bool reversed) {
+    if (!eq) return pair_view(B, reversed);
+    u64* const pl_p = iupac_side_planes(B, C, eq, reversed, false);
+    u64* const pl_t = iupac_side_planes(B, C, eq, reversed, true);
+    PairView v = pair_view(B, reversed);
     v.pl_p = pl_p; v.pl_t = pl_t;
     return v;
 }
@@ -1250,8 +1088,7 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
     for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
     auto pass = [&](bool start_pass) {
         const PairView PV = search_planes(B, C, eq, start_pass);
-        auto* ke = C.kernel_events(0);
-        if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+        TimedLaunches tl(C, 0);
         for (int f = 0; f < 4; ++f) {
             if (S.L[f].pair.empty()) continue;
             SearchArgs a{};
@@ -1263,11 +1100,11 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
             if (f == 0) { a.ws = ws; a.g_ws_off = d_ws_off; a.g_nb = d_nb; }
             launch_search(C, eq, f, a, ng);
         }
-        if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+        tl.end();
     };
     pass(false);
     if (mode == SEARCH_INFIX) {
-        if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+        if (!eq) ensure_reversed(B, C);
         pass(true);
     }
     return O;
@@ -1282,35 +1119,64 @@ static SearchOut run_search(quicked_batch& B, Context& C, const SearchLists& S, 
 // a launch over the whole list; a wave without a lane of the form leaves at once.  The workspace form's groups are all as
 // tall as the list's tallest pattern, and are run in slices that share one workspace of at most 256 MiB (QE_SEARCH_HITS_WS_KB).
 // Both passes are timed as kind 0; d_adv / d_adv2 hold their block steps per task / per occurrence.
-struct SearchHitsOut {
-    std::vector<int32_t> task_pair;
+struct HitsOut {                                   // of both all-occurrences runs, pairs and panel
+    std::vector<int32_t> task_pair;                // task (panel: slot) -> pair, -1 in the padding
     int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
     int64_t total = 0;
 };
-static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits, int eq = 0) {
-    SearchHitsOut O;
+// The per-pair arrays of an all-occurrences run -- found (0) | smallest score (-1) | stored - 1 (-1: the scan then counts 0) --,
+// the offsets and `nadv` step counters.  -> the stored counts, for the forward pass to fill
+static int32_t* hits_arrays(Context& C, HitsOut& O, size_t n, size_t nadv) {
+    int32_t* blk = C.scratch_p->take<int32_t>(3 * n);
+    O.d_found = blk; O.d_best = blk + n;
+    HIP_CHECK(hipMemsetAsync(O.d_found, 0, n * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(O.d_best, 0xFF, 2 * n * sizeof(int32_t), C.stream));
+    O.d_adv = C.scratch_p->take<u32>(nadv);
+    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nadv * sizeof(u32), C.stream));
+    O.d_off = C.scratch_p->take<int64_t>(n + 1);
+    return blk + 2 * n;
+}
+// ... and behind the forward pass the offsets in the order of the pairs (every pair counts: d_seq_len, lengths that are never
+// negative, stands in for the scan's list of tasks) with the total behind them -- the one thing the host reads in between
+static void hits_total(const quicked_batch& B, Context& C, HitsOut& O, const int32_t* d_len, const int32_t* d_seq_len) {
+    const size_t n = (size_t)B.n;
+    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, d_len, d_seq_len, O.d_off, O.d_off + n, (int)n);
+    HIP_CHECK(hipGetLastError());
+    std::vector<int64_t> tot;
+    FetchBatch fb(C);
+    fb.add(tot, (const int64_t*)(O.d_off + n), 1);
+    fb.sync();
+    O.total = tot[0];
+}
+// The start pass of the panel runs: k_search<4, Eq> in its start-pass form (PREFIX, the largest end, bound and window from the
+// forward pass's score / end on the device) over nt tasks laid out as arrays, one launch, timed as kind 0
+static void launch_start_pass(Context& C, int eq, const PairView& PV, size_t nt, const int32_t* pair, const int32_t* m, const int32_t* n,
+                              const int32_t* score, const int32_t* end, int32_t* o_start, u32* o_adv) {
+    SearchArgs s{};
+    s.P = PV;
+    s.T.ntasks = (int32_t)nt; s.T.pair = pair; s.T.m = m; s.T.n = n; s.T.cutoff = score;
+    s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
+    s.in_score = score; s.in_end = end; s.o_start = o_start; s.o_adv = o_adv;
+    TimedLaunches tl(C, 0);
+    launch_search(C, eq, 3, s, (nt + 63) / 64);
+    tl.end();
+}
+static HitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits, int eq = 0) {
+    HitsOut O;
     size_t off[5] = {0, 0, 0, 0, 0};
     for (int f = 0; f < 4; ++f) {
         O.task_pair.insert(O.task_pair.end(), S.L[f].pair.begin(), S.L[f].pair.end());
         off[f + 1] = O.task_pair.size();
     }
-    const size_t nt = O.task_pair.size(), n = (size_t)B.n;
+    const size_t nt = O.task_pair.size();
     if (nt == 0) return O;
-    int32_t* blk = C.scratch_p->take<int32_t>(3 * n);
-    O.d_found = blk; O.d_best = blk + n;
-    int32_t* d_len = blk + 2 * n;
-    HIP_CHECK(hipMemsetAsync(O.d_found, 0, n * sizeof(int32_t), C.stream));
-    HIP_CHECK(hipMemsetAsync(O.d_best, 0xFF, 2 * n * sizeof(int32_t), C.stream));
-    O.d_adv = C.scratch_p->take<u32>(nt);
-    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nt * sizeof(u32), C.stream));
+    int32_t* const d_len = hits_arrays(C, O, (size_t)B.n, nt);
     int32_t* raw = C.scratch_p->take<int32_t>(2 * nt * (size_t)max_hits);
-    O.d_off = C.scratch_p->take<int64_t>(n + 1);
     const SearchWs Wk = search_workspace(C, S.L[0]);
     DevTasks T[4];
     for (int f = 0; f < 4; ++f) if (!S.L[f].pair.empty()) T[f] = upload_tasks(S.L[f], C);
     const PairView PF = search_planes(B, C, eq, false);
-    auto* ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, 0);
     for (int f = 0; f < 4; ++f) {
         if (S.L[f].pair.empty()) continue;
         SearchHitsArgs x{};
@@ -1321,18 +1187,8 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
         if (f == 0) { x.S.ws = Wk.ws; x.S.g_ws_off = Wk.d_ws_off; x.S.g_nb = Wk.d_nb; }
         launch_search_hits(C, eq, f, x, ng);
     }
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
-    // offsets in the order of the pairs (a pair without a task has -1 + 1 = 0 stored; every pair counts: the lengths stand in
-    // for the scan's list of tasks), the total behind them
-    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, (const int32_t*)d_len, (const int32_t*)B.d_p_len, O.d_off, O.d_off + n, (int)n);
-    HIP_CHECK(hipGetLastError());
-    {
-        std::vector<int64_t> tot;
-        FetchBatch fb(C);
-        fb.add(tot, (const int64_t*)(O.d_off + n), 1);
-        fb.sync();
-        O.total = tot[0];
-    }
+    tl.end();
+    hits_total(B, C, O, d_len, B.d_p_len);                // (a pair without a task has 0 stored)
     if (O.total <= 0) return O;
     const size_t nh = (size_t)O.total;
     const bool infix = mode == SEARCH_INFIX;
@@ -1360,10 +1216,9 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
         HIP_CHECK(hipGetLastError());
     }
     if (!infix) return O;
-    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    if (!eq) ensure_reversed(B, C);
     const PairView PR = search_planes(B, C, eq, true);
-    ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl2(C, 0);
     const size_t ngh = (nh + 63) / 64;
     for (int f = 0; f < 4; ++f) {
         if (S.L[f].pair.empty()) continue;
@@ -1394,7 +1249,7 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
             launch_search(C, eq, f, a, ng);
         }
     }
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl2.end();
     hipLaunchKernelGGL(k_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
     HIP_CHECK(hipGetLastError());
     return O;
@@ -1403,56 +1258,6 @@ static SearchHitsOut run_search_hits(quicked_batch& B, Context& C, const SearchL
 // ---------------------------------------------------------------------------
 // Panel runs (quicked_batch_run_panel; qe_panel.h): every text of the batch against one shared set of patterns.
 // ---------------------------------------------------------------------------
-#ifndef QE_HAVE_K_SEARCH_PANEL
-// a kernels header without them (the host-only build's stand-ins): the per-slot functions of qe_panel.h that the device
-// kernels call, run slot by slot and slice by slice with the arguments of the device forms
-template <class Eq>
-static void k_search_panel(PanelArgs A) {
-    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
-    for (int slice = 0; slice < nslices; ++slice)
-        for (int slot = 0; slot < A.nslots; ++slot) {
-            const int pair = A.text[slot];
-            if (pair < 0) continue;
-            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
-            PanelKeeper keep;
-            keep.init();
-            u32 steps = 0;
-            panel_text<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, keep, steps,
-                           A.m_score ? A.m_score + (int64_t)pair * A.n_members : nullptr, A.m_score ? A.m_end + (int64_t)pair * A.n_members : nullptr);
-            panel_store_part(A, nslices, slice, slot, keep, steps);
-        }
-}
-static void k_panel_wire_codes(u64* planes, int64_t rows) { for (int64_t r = 0; r < rows; ++r) planes[3 * r] ^= planes[3 * r + 1]; }
-static void k_panel_reduce(PanelReduceArgs A) { for (int t = 0; t < A.nslots; ++t) panel_reduce_slot(A, t); }
-static void k_panel_finish(int nslots, const int32_t* text, const int32_t* o_pair, const int32_t* o_start, int32_t* hits) {
-    for (int t = 0; t < nslots; ++t) panel_finish_slot(t, text, o_pair, o_start, hits);
-}
-#endif
-#ifndef QE_HAVE_K_PANEL_HITS
-// ... and of the all-occurrences panel kernels (PanelHitsArgs, PanelHitsCountArgs, PanelHitsExpandArgs)
-template <class Eq>
-static void k_panel_hits(PanelHitsArgs A) {
-    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
-    for (int slice = 0; slice < nslices; ++slice)
-        for (int slot = 0; slot < A.nslots; ++slot) {
-            const int pair = A.text[slot];
-            if (pair < 0) continue;
-            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
-            PanelHitScan H;
-            panel_hit_scan_init(H, A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits, A.max_hits);
-            u32 steps = 0;
-            panel_text_hits<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, H, steps);
-            panel_hits_store_part(A, nslices, slice, slot, H, steps);
-        }
-}
-static void k_panel_hits_count(PanelHitsCountArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_count_slot(A, t); }
-static void k_panel_hits_expand(PanelHitsExpandArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_expand_slot(A, t); }
-static void k_panel_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) { for (int64_t j = 0; j < total; ++j) panel_hits_finish_one(j, o_start, hits); }
-#endif
 
 // Slices of the panel, chosen on the host: one while the text groups alone fill the chip (two waves on every SIMD); else enough
 // that groups x slices reach about twice the resident wave slots -- the last waves of a launch then have company --, never more
@@ -1469,44 +1274,34 @@ static size_t panel_plane_words(const PanelRun& pr) {
     for (int32_t p = 0; p < pr.n_patterns; ++p) w += 3 * ((size_t)(pr.len[p] + 63) / 64 + 2);
     return w;
 }
-// what a panel run takes from its pool (the planner's fixed needs): the panel's bytes, tables and planes (forward and, INFIX,
-// reversed), the slice partials at the most slices the host would choose, the start-pass arrays, the matrix, and a flagged
-// run's four-plane words of the texts
+// What the panel runs take from their pools alike (the planner's fixed needs): the panel's bytes, tables and planes (forward and,
+// INFIX, reversed), a flagged run's four-plane words of the texts, the takes' padding.  -> nslots: the non-empty texts in whole
+// waves, as panel_upload lays them out
+static size_t panel_shared_bytes(const quicked_batch& B, const SearchRun& sr, size_t& nslots) {
+    const PanelRun& pr = *sr.panel;
+    size_t texts = 0, pool = 0;
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
+    nslots = (texts + 63) / 64 * 64;
+    const size_t K = (size_t)pr.n_patterns, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
+    size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
+    if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
+    return b + 16 * 512;
+}
+// ... and a panel run besides: the slice partials at the most slices the host would choose, the start-pass arrays, the matrix
 static size_t panel_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
-    size_t texts = 0;                                             // the slots are the non-empty texts', as in run_search_panel
-    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
-    const size_t n = (size_t)B.n, K = (size_t)pr.n_patterns, nslots = (texts + 63) / 64 * 64, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
-    size_t pool = 0;
-    for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
-    size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
+    size_t nslots = 0, b = panel_shared_bytes(B, sr, nslots);
+    const size_t n = (size_t)B.n, K = (size_t)pr.n_patterns;
     b += 6 * (size_t)panel_slices(C, nslots / 64, pr.n_patterns) * nslots * sizeof(int32_t);
     b += nslots * 4 + n * 24 + nslots * 8 * 4 + n * 8;
     if (pr.matrix) b += 2 * n * K * sizeof(int32_t);
-    if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
-    return b + 16 * 512;
+    return b;
 }
 // The text planes a panel pass reads: the batch's own under the library's equality; a flagged run packs the four membership
 // planes of the TEXTS into its pool, as search_planes does for both sides -- the batch's patterns play no part
 static const u64* panel_text_planes(quicked_batch& B, Context& C, int eq, bool reversed) {
-    if (!eq) return pair_view(B, reversed).pl_t;
-    if (B.packed && reversed && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
-    const PairView v = pair_view(B, reversed);
-    u64* pl_t = C.scratch_p->take<u64>((size_t)iupac_offset((int64_t)B.pl_t_words) + 8);
-    const int blocks = (int)((B.n + 3) / 4);
-    if (B.packed) {
-        IupacPlanesArgs a;
-        a.nseq = (int32_t)B.n;
-        a.src = v.pl_t; a.dst = pl_t; a.pl_off = B.d_plt_off; a.len = B.d_t_len; a.n_empty = eq == 2 ? 1 : 0;
-        hipLaunchKernelGGL(k_planes_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
-    } else {
-        IupacPackArgs a;
-        a.nseq = (int32_t)B.n; a.reverse = reversed ? 1 : 0;
-        a.asc = B.d_asc_t; a.asc_off = B.d_t_off; a.len = B.d_t_len; a.planes = pl_t; a.pl_off = B.d_plt_off; a.acgt_only = eq == 2 ? 1 : 0;
-        hipLaunchKernelGGL(k_pack_iupac, dim3(blocks), dim3(256), 0, C.stream, a);
-    }
-    HIP_CHECK(hipGetLastError());
-    return pl_t;
+    return eq ? iupac_side_planes(B, C, eq, reversed, true) : pair_view(B, reversed).pl_t;
 }
 
 // The run: the panel's bytes and tables go up in one block and are packed on the device by the batch's own packers (k_pack
@@ -1621,8 +1416,7 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     HIP_CHECK(hipMemsetAsync(O.d_hits, 0xFF, 6 * n * sizeof(int32_t), C.stream));
     O.d_adv = C.scratch_p->take<u32>(nslots);
     HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nslots * sizeof(u32), C.stream));
-    auto* ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    TimedLaunches tl(C, 0);
     {
         // four text groups per workgroup, one per SIMD of its CU, and launch_groups' claim on the CU's LDS: at most two of
         // these workgroups share a CU, whichever slices they belong to
@@ -1631,7 +1425,7 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
         else hipLaunchKernelGGL(k_search_panel<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
     }
     HIP_CHECK(hipGetLastError());
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     // ---- the reduction, and the start pass's tasks
     PanelReduceArgs r{};
     r.nslots = (int32_t)nslots; r.nslices = nslices; r.infix = infix ? 1 : 0;
@@ -1651,19 +1445,11 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     HIP_CHECK(hipGetLastError());
     if (!infix) return O;
     // ---- the start pass: one lane per text over the window that ends at its best member's text_end, reversed
-    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    if (!eq) ensure_reversed(B, C);
     PairView PV = pair_view(B, true);
     PV.pl_p = panel_planes(true); PV.pl_p_off = r.o_plp_off;
     PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = B.d_plt_off;
-    SearchArgs s{};
-    s.P = PV;
-    s.T.ntasks = (int32_t)nslots; s.T.pair = r.o_pair; s.T.m = r.o_m; s.T.n = r.o_n; s.T.cutoff = r.o_score;
-    s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
-    s.in_score = r.o_score; s.in_end = r.o_end; s.o_start = o_start; s.o_adv = O.d_adv2;
-    ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
-    launch_search(C, eq, 3, s, ngroups);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    launch_start_pass(C, eq, PV, nslots, r.o_pair, r.o_m, r.o_n, r.o_score, r.o_end, o_start, O.d_adv2);
     hipLaunchKernelGGL(k_panel_finish, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, (int)nslots, (const int32_t*)d_text,
                        (const int32_t*)r.o_pair, (const int32_t*)o_start, O.d_hits);
     HIP_CHECK(hipGetLastError());
@@ -1686,38 +1472,26 @@ static int panel_hits_slices(const Context& C, size_t nslots, int K, int max_hit
     const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(1, per_slice_bytes));
     return (int)std::min<size_t>((size_t)panel_slices(C, nslots / 64, K), fit);
 }
-// what such a run takes from its pool before the total is known (the planner's fixed needs): the panel's bytes, tables and
-// planes, the slice partials and the raw buffer at the slices the host would choose, the per-pair arrays, and a flagged run's
-// four-plane words of the texts.  The arrays sized by the total (16 bytes per stored occurrence, 60 with the start pass) are
-// not known before the run and are not planned, as in an all-occurrences search run
+// what such a run takes from its pool before the total is known (the planner's fixed needs): panel_shared_bytes, the slice
+// partials and the raw buffer at the slices the host would choose, the per-pair arrays.  The arrays sized by the total (16
+// bytes per stored occurrence, 60 with the start pass) are not known before the run and are not planned, as in an
+// all-occurrences search run
 static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
-    const PanelRun& pr = *sr.panel;
-    size_t texts = 0;
-    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
-    const size_t n = (size_t)B.n, K = (size_t)pr.n_patterns, nslots = (texts + 63) / 64 * 64, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
-    size_t pool = 0;
-    for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
-    size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
-    const size_t nslices = (size_t)panel_hits_slices(C, nslots, pr.n_patterns, sr.max_hits);
+    size_t nslots = 0, b = panel_shared_bytes(B, sr, nslots);
+    const size_t n = (size_t)B.n, nslices = (size_t)panel_hits_slices(C, nslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
     b += nslots * 8 + n * 12 + (n + 1) * 8;
-    if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
-    return b + 16 * 512;
+    return b;
 }
-struct PanelHitsOut {
-    std::vector<int32_t> text;                     // slot -> pair, -1 in the padding
-    int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
-    int64_t total = 0;
-};
-static PanelHitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
+static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
     const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
     const bool infix = sr.mode == SEARCH_INFIX;
-    PanelHitsOut O;
+    HitsOut O;
     const PanelDev D = panel_upload(B, C, sr);
-    O.text = D.text;
-    if (O.text.empty()) return O;
-    const size_t n = (size_t)B.n, nslots = D.nslots, ngroups = D.ngroups;
+    O.task_pair = D.text;
+    if (O.task_pair.empty()) return O;
+    const size_t nslots = D.nslots, ngroups = D.ngroups;
     // ---- the forward pass
     const int want = panel_hits_slices(C, nslots, K, max_hits), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
     PanelHitsArgs a{};
@@ -1727,16 +1501,8 @@ static PanelHitsOut run_search_panel_hits(quicked_batch& B, Context& C, const Se
     a.nslots = (int32_t)nslots; a.text = D.d_text; a.mode = sr.mode; a.max_hits = max_hits;
     a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
     a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
-    int32_t* blk = C.scratch_p->take<int32_t>(3 * n);
-    O.d_found = blk; O.d_best = blk + n;
-    int32_t* d_plen = blk + 2 * n;
-    HIP_CHECK(hipMemsetAsync(O.d_found, 0, n * sizeof(int32_t), C.stream));
-    HIP_CHECK(hipMemsetAsync(O.d_best, 0xFF, 2 * n * sizeof(int32_t), C.stream));
-    O.d_adv = C.scratch_p->take<u32>(nslots);
-    HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nslots * sizeof(u32), C.stream));
-    O.d_off = C.scratch_p->take<int64_t>(n + 1);
-    auto* ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+    int32_t* const d_plen = hits_arrays(C, O, (size_t)B.n, nslots);
+    TimedLaunches tl(C, 0);
     {
         // k_search_panel's launch shape: four text groups per workgroup and launch_groups' claim on the CU's LDS
         const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
@@ -1744,21 +1510,13 @@ static PanelHitsOut run_search_panel_hits(quicked_batch& B, Context& C, const Se
         else hipLaunchKernelGGL(k_panel_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
     }
     HIP_CHECK(hipGetLastError());
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    tl.end();
     // ---- counts per pair, offsets in the order of the pairs (a pair without a slot has -1 + 1 = 0 stored), the total
     PanelHitsCountArgs c{};
     c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits; c.text = D.d_text; c.part = a.part;
     c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.o_adv = O.d_adv;
     hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
-    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, (const int32_t*)d_plen, (const int32_t*)B.d_t_len, O.d_off, O.d_off + n, (int)n);
-    HIP_CHECK(hipGetLastError());
-    {
-        std::vector<int64_t> tot;
-        FetchBatch fb(C);
-        fb.add(tot, (const int64_t*)(O.d_off + n), 1);
-        fb.sync();
-        O.total = tot[0];
-    }
+    hits_total(B, C, O, d_plen, B.d_t_len);
     if (O.total <= 0) return O;
     const size_t nh = (size_t)O.total;
     O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
@@ -1780,19 +1538,11 @@ static PanelHitsOut run_search_panel_hits(quicked_batch& B, Context& C, const Se
     HIP_CHECK(hipGetLastError());
     if (!infix) return O;
     // ---- the start pass: one lane per stored occurrence over its window, reversed
-    if (!eq && !B.have_rev[B.parity]) { launch_pack(B, C, true); B.have_rev[B.parity] = true; }
+    if (!eq) ensure_reversed(B, C);
     PairView PV = pair_view(B, true);
     PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
     PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
-    SearchArgs s{};
-    s.P = PV;
-    s.T.ntasks = (int32_t)nh; s.T.pair = e.o_pair; s.T.m = e.o_m; s.T.n = e.o_n; s.T.cutoff = e.o_score;
-    s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
-    s.in_score = e.o_score; s.in_end = e.o_end; s.o_start = o_start; s.o_adv = O.d_adv2;
-    ke = C.kernel_events(0);
-    if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
-    launch_search(C, eq, 3, s, (nh + 63) / 64);
-    if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+    launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
     hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
     HIP_CHECK(hipGetLastError());
     return O;
@@ -1811,38 +1561,6 @@ static bool wave_formatter_wanted(const quicked_batch& B, const SegList& SL, boo
     const int wave_env = sw(Sw::FormatWave);      // tests force either form
     return B.cigar_style != 2 && nr > 0 && (wave_env >= 0 ? wave_env != 0 : (nseg > 0 && pool_bytes / nr >= 512));
 }
-
-#ifndef QE_HAVE_K_TAGS
-// a kernels header without the tag kernels (the host-only build's stand-ins): the walker of qe_tags.h on the host, both forms
-struct HostTagRuns {
-    const SegFormatArgs& A; const u32* base = nullptr; int64_t stride = 1;
-    void open(int t) {
-        const int g = t >> 6, lane = t & 63;
-        if (A.runs_by_task) { base = A.runs + A.g_runs_off[g] + (int64_t)lane * A.g_runs_cap[g]; stride = 1; }
-        else { base = A.runs + A.g_runs_off[g] + lane; stride = 64; }
-    }
-    u32 at(int k) const { return base[(int64_t)k * stride]; }
-};
-template <bool WRITE> static void k_tags_segs(SegTagArgs T) {
-    const SegFormatArgs& A = T.F;
-    for (int i = 0; i < A.npairs; ++i) {
-        const int pair = T.root_pair[i];
-        const int m = T.P.p_len[pair];
-        TagWalker<WRITE> W;
-        W.want_md = T.want_md != 0;
-        if (WRITE) {
-            char* out = T.md_pool + T.md_off[i];
-            if (T.o_md_len[i] <= 0) { out[0] = '\0'; continue; }
-            W.sink = TagSink{out, T.o_md_len[i], T.P.asc_p + T.P.asc_p_off[pair], m};
-        }
-        HostTagRuns R{A};
-        const bool ok = tag_walk_segments(W, A.seg_off, A.seg_kind, A.seg_a, A.seg_b, A.nruns, i, R);
-        const int64_t md_len = W.finish();
-        if (!WRITE) tag_store_counts(T.want_stats ? T.o_stats + i : nullptr, T.want_md ? T.o_md_len + i : nullptr, T.o_md_bad, !ok, W.s, md_len, m);
-    }
-}
-template <bool WRITE> static void k_tags_segs_wave(SegTagArgs T) { k_tags_segs<WRITE>(T); }
-#endif
 
 // Which form of the tag kernels a stage takes: the wave form where the CIGAR formatter takes its wave form (runs laid out by
 // task: 256-byte rows), else the lane form; QE_TAGS_WAVE = 0 / 1 forces one (tests).  Both read either run layout.
@@ -2148,17 +1866,19 @@ static void reset_host_results(quicked_batch& B) {
     if (B.run_tags & QUICKED_TAG_STATS) B.wr->stats.assign((size_t)B.n, no_stats); else B.wr->stats.clear();
     if (B.run_tags & QUICKED_TAG_MD) B.wr->md_off.assign((size_t)B.n, -1); else B.wr->md_off.clear();
     B.wr->md_pool.size = 0;
-    if (B.search_run) { B.wr->text_start.assign((size_t)B.n, -1); B.wr->text_end.assign((size_t)B.n, -1); }
+    using Kind = quicked_batch::SearchKind;
+    if (B.search_kind == Kind::Best) { B.wr->text_start.assign((size_t)B.n, -1); B.wr->text_end.assign((size_t)B.n, -1); }
     else { B.wr->text_start.clear(); B.wr->text_end.clear(); }
-    if (B.hits_run) { B.wr->found.assign((size_t)B.n, 0); B.wr->hit_off.assign((size_t)B.n + 1, 0); }
+    if (B.search_kind == Kind::All) { B.wr->found.assign((size_t)B.n, 0); B.wr->hit_off.assign((size_t)B.n + 1, 0); }
     else { B.wr->found.clear(); B.wr->hit_off.clear(); }
     B.wr->hits.clear();
     static const quicked_panel_hit_t no_panel_hit = {-1, -1, -1, -1, -1, -1};
-    if (B.panel_run) B.wr->panel_hits.assign((size_t)B.n, no_panel_hit); else B.wr->panel_hits.clear();
-    B.wr->panel_members = B.panel_run;
-    if (B.panel_run && B.panel_matrix) { B.wr->panel_score.assign((size_t)B.n * (size_t)B.panel_run, -1); B.wr->panel_end.assign((size_t)B.n * (size_t)B.panel_run, -1); }
+    const bool panel = B.search_kind == Kind::Panel;
+    if (panel) B.wr->panel_hits.assign((size_t)B.n, no_panel_hit); else B.wr->panel_hits.clear();
+    B.wr->panel_members = panel ? B.panel_members : 0;
+    if (panel && B.panel_matrix) { B.wr->panel_score.assign((size_t)B.n * (size_t)B.panel_members, -1); B.wr->panel_end.assign((size_t)B.n * (size_t)B.panel_members, -1); }
     else { B.wr->panel_score.clear(); B.wr->panel_end.clear(); }
-    if (B.panel_all_run) { B.wr->panel_found.assign((size_t)B.n, 0); B.wr->panel_occ_off.assign((size_t)B.n + 1, 0); }
+    if (B.search_kind == Kind::PanelAll) { B.wr->panel_found.assign((size_t)B.n, 0); B.wr->panel_occ_off.assign((size_t)B.n + 1, 0); }
     else { B.wr->panel_found.clear(); B.wr->panel_occ_off.clear(); }
     B.wr->panel_occ.clear();
     B.wr->deferred_pairs = 0;
@@ -2419,8 +2139,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
         a.o_score = O.score + o; a.o_first = O.first + o; a.o_last = O.last + o; a.o_posv = O.posv + o; a.o_adv = O.adv + o;
         a.o_maxrow = O.len + o;
         a.only_if = nullptr;
-        auto* ke = C.kernel_events(1);
-        if (ke) HIP_CHECK(hipEventRecord(ke->first, C.stream));
+        TimedLaunches tl(C, 1);
         if (Gfill >= 2) {
             // few leaves: G lanes per leaf, band state on chip, the same checkpoints / carry words / band edges in the
             // traceback's layout (k_banded_coop_lds<true>); leaves it flags are refilled by the one-lane kernel
@@ -2463,7 +2182,7 @@ static void run_align(quicked_batch& B, Context& C, const TaskList& roots, bool 
         a.fill_multi = sw(Sw::FillMulti);
         a.lane_rel = sw(Sw::LaneRel);
         launch_groups(C, k_banded<true>, a, (size_t)(g1 - g0), 8, 0);     // everything, or what the cooperative fill flagged
-        if (ke) HIP_CHECK(hipEventRecord(ke->second, C.stream));
+        tl.end();
         TraceArgs tr;
         tr.P = a.P; tr.T = a.T;
         tr.ws = ws; tr.g_ws_off = a.g_ws_off; tr.g_nslots = a.g_nslots; tr.g_nrows = a.g_nrows; tr.g_nch = a.g_nch;

@@ -1,6 +1,6 @@
 // qe_tags.h -- per-pair alignment statistics and the SAM MD:Z string, as functions of an alignment's operation sequence
 // and the pattern's raw bytes.  Plain C++ with no HIP dependency (as qe_bounded.h): k_tags_segs (qe_kernels.hip) runs the
-// walker one lane per alignment, the host-only build runs it in place of the kernels (qe_stages.hip), and the CPU suite
+// walker one lane per alignment, the host-only build runs it in place of the kernels (tests/native/hip_stub/qe_kernels_stub.h), and the CPU suite
 // compiles the very same source with g++ (tests/native/tags_cpu.cpp) against a restatement in Python.
 //
 // The operation sequence is what the style-0 CIGAR expands to; I consumes text, D consumes pattern (AlignCheck,

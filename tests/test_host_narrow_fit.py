@@ -8,21 +8,12 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "quicked_amd", "csrc")
+from native_build import ASAN_UBSAN, build_host
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_fitted_first_pass_and_its_policy_under_address_and_ub_sanitizers(tmp_path):
-    exe = str(tmp_path / "narrow_fit_host")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unused-parameter",
-           "-Wno-class-memaccess", "-DQE_KERNELS_HEADER=\"qe_kernels_stub.h\"", "-I" + os.path.join(NATIVE, "hip_stub"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-x", "c++", os.path.join(CSRC, "qe_driver.hip"), os.path.join(CSRC, "qe_capi.cpp"), os.path.join(CSRC, "qe_hostpack.cpp"),
-           os.path.join(NATIVE, "narrow_fit_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert built.returncode == 0, built.stderr[-4000:]
+    exe = build_host("narrow_fit_host.cpp", tmp_path, ASAN_UBSAN)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", QE_STUB_HBM_BYTES=str(8 << 30))
     for name in ("QE_SCORE_NARROW", "QE_NARROW_FIT", "QE_STUB_BOUND"):
         env.pop(name, None)

@@ -10,20 +10,7 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "quicked_amd", "csrc")
-
-
-def build(tmp_path, tag, flags):
-    exe = str(tmp_path / f"host_scenarios_{tag}")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unused-parameter", "-Wno-class-memaccess",
-           "-DQE_KERNELS_HEADER=\"qe_kernels_stub.h\"", "-I" + os.path.join(NATIVE, "hip_stub"), "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + flags + \
-          ["-x", "c++", os.path.join(CSRC, "qe_driver.hip"), os.path.join(CSRC, "qe_capi.cpp"), os.path.join(CSRC, "qe_hostpack.cpp"),
-           os.path.join(NATIVE, "host_scenarios.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert built.returncode == 0, built.stderr[-4000:]
-    return exe
+from native_build import ASAN_UBSAN, build_host
 
 
 def run(exe, env_extra, timeout=600):
@@ -34,7 +21,7 @@ def run(exe, env_extra, timeout=600):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_host_layer_under_thread_sanitizer(tmp_path):
-    exe = build(tmp_path, "tsan", ["-fsanitize=thread"])
+    exe = build_host("host_scenarios.cpp", tmp_path, ["-fsanitize=thread"])
     env = {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1", "QE_STUB_HBM_BYTES": str(8 << 30)}
     r = run(exe, env)
     assert r.returncode == 0 and "host_scenarios ok" in r.stdout, (r.stdout + r.stderr)[-6000:]
@@ -60,7 +47,7 @@ def test_host_layer_under_thread_sanitizer(tmp_path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_host_layer_under_address_and_ub_sanitizers(tmp_path):
-    exe = build(tmp_path, "asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    exe = build_host("host_scenarios.cpp", tmp_path, ASAN_UBSAN)
     r = run(exe, {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1", "QE_STUB_HBM_BYTES": str(8 << 30)})
     assert r.returncode == 0 and "host_scenarios ok" in r.stdout, (r.stdout + r.stderr)[-6000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]

@@ -9,22 +9,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "quicked_amd", "csrc")
+from native_build import ASAN_UBSAN, build_host
 
 
 def test_tags_host_side_under_address_and_ub_sanitizers(tmp_path):
     if shutil.which("g++") is None:
         pytest.fail("g++ is needed to compile the host layer")
-    exe = str(tmp_path / "tags_host")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unused-parameter",
-           "-Wno-class-memaccess", "-DQE_KERNELS_HEADER=\"qe_kernels_stub.h\"", "-I" + os.path.join(NATIVE, "hip_stub"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-x", "c++", os.path.join(CSRC, "qe_driver.hip"), os.path.join(CSRC, "qe_capi.cpp"), os.path.join(CSRC, "qe_hostpack.cpp"),
-           os.path.join(NATIVE, "tags_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert built.returncode == 0, built.stderr[-4000:]
+    exe = build_host("tags_host.cpp", tmp_path, ASAN_UBSAN)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", QE_STUB_HBM_BYTES=str(8 << 30))
     for name in ("QE_TAGS_WAVE", "QE_FORMAT_WAVE", "QE_STUB_BOUND", "QE_STUB_SKIP_EVERY"):
         env.pop(name, None)
