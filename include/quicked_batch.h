@@ -291,6 +291,37 @@ quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode,
 quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored /* n each; either may be NULL */);
 int64_t          quicked_batch_panel_hit_total(quicked_batch_t* batch);   /* the sum of stored; -1 after any other run */
 quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_occ_t* hits, int64_t* hit_off /* n + 1 */);
+/* Windowed panel search: quicked_batch_run_panel_all for a few LONG texts -- contigs, a bacterial genome, 100 kb reads.  That
+ * run gives every text one lane; this one cuts every text into windows of `window` columns and gives every window a lane, so a
+ * 5 Mb text occupies the chip instead of one lane of one wave.
+ *
+ * The contract is one sentence: for every input it accepts it leaves exactly the results quicked_batch_run_panel_all leaves for
+ * the same batch, panel, mode, bounds and max_hits, whatever `window` is -- found, stored, every stored occurrence in (pattern,
+ * text_end) order and which ones the cap keeps; quicked_batch_scores, the statuses, empty texts; both IUPAC flags; ASCII and
+ * packed batches with the same reading of PLANES3's fifth symbol.  A lane owns the occurrences whose text_end lies in its window;
+ * it warms up over the 64 ceil((m + k) / 64) columns before the window (no occurrence of a member of m bases within its bound k
+ * is longer than m + k) and follows a plateau that is still pending at the window's end until it rises, falls or the text ends
+ * (DESIGN.md 4.14.2 has the argument).  The three getters above serve it: a scan run is a run of their kind; every other getter
+ * behaves as after quicked_batch_run_panel_all.  Counters [0] and kernel_times slot [0] count both passes; the block steps are
+ * the ones really walked, warm-up and run-out columns included.
+ *
+ * window: the text columns a lane owns.  0: the library's choice (a multiple of 64, at least 1024 and eight warm-ups, small
+ * enough that the windows and the panel's slices fill the chip about twice, widened until the rule below holds).  Otherwise a
+ * multiple of 64 that is at least 64.
+ *
+ * QUICKED_ERROR, nothing launched: everything quicked_batch_run_panel_all answers so (a NULL batch; a base mode that is not PREFIX
+ * or INFIX; unknown bits, QUICKED_PANEL_MATRIX; n_patterns out of range; an empty member; a negative bound; max_hits outside
+ * 1 .. 4096; (non-empty texts) x max_hits above 2^26); a window that is negative, not a multiple of 64 or above 2^31 - 64; with a
+ * forced window, (window slots of the batch = the sum of ceil(n / window) over the texts) x max_hits above 2^26.
+ * QUICKED_UNIMPLEMENTED, nothing queued: the base mode QUICKED_SEARCH_PREFIX (a PREFIX occurrence within the bound ends in the
+ * first m + k columns: quicked_batch_run_panel_all serves it); a member longer than QUICKED_PANEL_MAX_LEN bases; sync == 0; a
+ * batch configured with check != 0.
+ * Not built: a cap above 4096 per text, queued runs, members over 256 bases, alignments of occurrences, and windows for
+ * quicked_batch_run_panel / _run_search / _run_search_all. */
+quicked_status_t quicked_batch_run_panel_scan(quicked_batch_t* batch, int mode,
+                                              int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
+                                              const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all,
+                                              int32_t max_hits, int32_t window, int sync);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

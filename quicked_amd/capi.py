@@ -62,7 +62,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_run_bounded", "quicked_batch_run_search", "quicked_batch_locations",
            "quicked_batch_run_search_all", "quicked_batch_hit_counts", "quicked_batch_hit_total", "quicked_batch_hits",
            "quicked_batch_run_panel", "quicked_batch_panel_results", "quicked_batch_panel_matrix",
-           "quicked_batch_run_panel_all", "quicked_batch_panel_hit_counts", "quicked_batch_panel_hit_total", "quicked_batch_panel_hits",
+           "quicked_batch_run_panel_all", "quicked_batch_run_panel_scan", "quicked_batch_panel_hit_counts", "quicked_batch_panel_hit_total", "quicked_batch_panel_hits",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -135,6 +135,8 @@ def lib():
     L.quicked_batch_panel_matrix.restype = C.c_int
     L.quicked_batch_run_panel_all.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int]
     L.quicked_batch_run_panel_all.restype = C.c_int
+    L.quicked_batch_run_panel_scan.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int]
+    L.quicked_batch_run_panel_scan.restype = C.c_int
     L.quicked_batch_panel_hit_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_panel_hit_counts.restype = C.c_int
     L.quicked_batch_panel_hit_total.argtypes = [C.c_void_p]
@@ -521,6 +523,25 @@ class ResidentBatch:
             raise ValueError("max_dist: one bound per panel member")
         return self._lib.quicked_batch_run_panel_all(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, md.ctypes.data, 0,
                                                      int(max_hits), 1 if sync else 0)
+
+    def run_panel_scan(self, mode, panel, max_dist=None, max_hits=16, window=0, sync=True):
+        """quicked_batch_run_panel_scan: run_panel_all's results, exactly, with every text cut into windows of `window` columns
+        (0: the library's choice; else a multiple of 64) and a lane per window: for a few long texts.  INFIX only; mode's flags,
+        panel, max_dist and max_hits as in run_panel_all.  Read through panel_hit_counts() / panel_hits().  Sync runs only."""
+        panel = [bytes(p) for p in panel]
+        k = len(panel)
+        pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
+        plen = np.array([len(p) for p in panel], dtype=np.int32)
+        poff = np.zeros(max(k, 1), dtype=np.int64)
+        if k > 1:
+            poff[1:k] = np.cumsum(plen[:-1], dtype=np.int64)
+        md, md_all = None, 2**31 - 1 if max_dist is None else max_dist
+        if np.ndim(md_all) != 0:
+            md, md_all = np.ascontiguousarray(max_dist, dtype=np.int32), 0
+            if md.shape != (k,):
+                raise ValueError("max_dist: one bound per panel member")
+        return self._lib.quicked_batch_run_panel_scan(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data,
+                                                      None if md is None else md.ctypes.data, int(md_all), int(max_hits), int(window), 1 if sync else 0)
 
     def panel_hit_counts(self):
         """-> (found, stored) int32 arrays of the last all-occurrences panel run: found[i] occurrences of all members in text i

@@ -220,7 +220,15 @@ struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 // panel != nullptr: a panel run (quicked_batch_run_panel): the batch's texts against the panel's members; max_dist then has one
 // value per MEMBER; fetch only
 struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; const int32_t* len; bool matrix; };
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; };
+// ... and window >= 0: the same run with long texts split across lanes (quicked_batch_run_panel_scan): a lane owns `window` text
+// columns, 0 the library's choice (panel_scan_window); its results are an all-occurrences panel run's
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; };
+// the window slots of a batch at `window` columns per lane: every non-empty text in ceil(n / window) of them
+inline int64_t panel_scan_slots(const quicked_batch& B, int64_t window) {
+    int64_t slots = 0;
+    for (int64_t i = 0; i < B.n; ++i) slots += ((int64_t)B.t_len[(size_t)i] + window - 1) / window;
+    return slots;
+}
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd = nullptr, const SearchRun* sr = nullptr);
 // the results of the batch's last queued run to the host (quicked_batch_fetch)
 quicked_status_t fetch_results(quicked_batch& B);

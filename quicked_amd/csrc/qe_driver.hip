@@ -43,6 +43,12 @@
 #define QE_KERNELS_HEADER "qe_kernels.hip"
 #endif
 #include QE_KERNELS_HEADER
+// (the host-only build's stand-ins of kernels that are newer than its stub header, where the tree has them)
+#if !defined(__HIPCC__) && defined(__has_include)
+#if __has_include("qe_kernels_stub_scan.h")
+#include "qe_kernels_stub_scan.h"
+#endif
+#endif
 
 
 namespace qe {
@@ -728,7 +734,8 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     for (const auto& q : C.pool_a2) pools_held += q.cap;
     size_t need_mat = B.last_mat_bytes, need_fixed = B.last_fixed_bytes;
     int need_groups = B.last_groups;
-    if (sr && sr->panel && sr->max_hits > 0) need_fixed += panel_hits_fixed_bytes(B, C, *sr);      // ... every occurrence: its panel, partials, raw buffer, per-pair arrays
+    if (sr && sr->panel && sr->max_hits > 0 && sr->window >= 0) need_fixed += panel_scan_fixed_bytes(B, C, *sr);      // ... the same split across lanes: its slot table and rank bases besides
+    else if (sr && sr->panel && sr->max_hits > 0) need_fixed += panel_hits_fixed_bytes(B, C, *sr);      // ... every occurrence: its panel, partials, raw buffer, per-pair arrays
     else if (sr && sr->panel) need_fixed += panel_fixed_bytes(B, C, *sr);    // a panel run: its panel, partials, start-pass arrays, matrix, four-plane texts
     else if (sr) need_fixed += search_iupac_bytes(B, sr->eq, sr->mode);      // a flagged search run packs its four planes into its pool
     if (need_groups == 0 && !p.only_score && p.algo != WINDOWED) {
@@ -898,7 +905,8 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // All-occurrences panel run (sync only): found / smallest score / offsets per text and the stored occurrences, already in
         // the order of the texts and (pattern, text_end) within a text, in one read-back
         enter_a();
-        fetch_hits(B, C, run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
+        // (window >= 0: the same results from window slots, quicked_batch_run_panel_scan)
+        fetch_hits(B, C, sr->window >= 0 ? run_search_panel_scan(B, C, *sr) : run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
         ret = QUICKED_OK;
     } else if (sr && sr->panel) {
         // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every

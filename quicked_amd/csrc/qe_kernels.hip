@@ -1719,6 +1719,51 @@ __global__ __launch_bounds__(256) void k_panel_hits_finish(int64_t total, const 
     if (j < total) panel_hits_finish_one(j, o_start, hits);
 }
 
+// Every occurrence of every member, long texts split across lanes (qe_panel.h; quicked_batch_run_panel_scan; DESIGN.md
+// 4.14.2): k_panel_hits with a WINDOW SLOT {pair, c0, c1} per lane in the place of a text slot -- the grid is window groups x
+// panel slices, the launch shape k_panel_hits'.  The member index still comes from blockIdx.y and a loop counter only: length,
+// bound, block count, row bit, plane words and the warm-up's length stay wave-uniform, the dispatch on the block count a
+// uniform branch.  A lane walks its warm-up, its owned columns and -- only while a candidate is pending -- the run-out
+// (panel_member_window); the wave leaves a member when its last lane does.  Stores as k_panel_hits: one 12-byte record when
+// row m rises out of an owned valley, never past max_hits per (slice, slot).  No workspace, no task list.
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_scan(PanelScanArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.w_pair[slot];                           // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0, c0 = 0, c1 = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; c0 = A.w_c0[slot]; c1 = A.w_c1[slot]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelWindowScan H;
+    panel_window_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0, c0, c1);
+    u32 steps = 0;
+    panel_window_hits<Eq>(P, p0, p1, tp, n, c0, c1, H, steps);
+    if (pair >= 0) panel_scan_store_part(A, nslices, slice, slot, H, steps);
+}
+template __global__ void k_panel_scan<SearchEq3>(PanelScanArgs);
+template __global__ void k_panel_scan<SearchEqIupac>(PanelScanArgs);
+
+// one thread per (slice, text) over the text's window slots, then one thread per text over the slices: the counts merged and
+// every slice's rank base (PanelScanCountArgs); then -- behind k_scan_offsets -- one thread per lane (slice, window slot): its stored records ranked among the text's and put in
+// their places with their start-pass tasks (PanelScanExpandArgs).  k_panel_hits_finish serves the start pass as it is.
+__global__ __launch_bounds__(256) void k_panel_scan_sums(PanelScanCountArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.ntext) panel_scan_sums_slice(A, (int)blockIdx.y, t);
+}
+__global__ __launch_bounds__(256) void k_panel_scan_count(PanelScanCountArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.ntext) panel_scan_count_text(A, t);
+}
+__global__ __launch_bounds__(256) void k_panel_scan_expand(PanelScanExpandArgs A) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w < A.nslots) panel_scan_expand_lane(A, (int)blockIdx.y, w);
+}
+
 
 // ===========================================================================
 // BandEd score-only, cooperative form: G adjacent lanes share one alignment.

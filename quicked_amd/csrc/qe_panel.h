@@ -308,4 +308,194 @@ QE_S_HD void panel_hits_finish_one(int64_t j, const int32_t* o_start, int32_t* h
     hits[4 * j + 1] = o_start[j] < 0 ? -1 : hits[4 * j + 1] + o_start[j];
 }
 
+// ---- every occurrence of every member, long texts split across lanes (quicked_batch_run_panel_scan)
+// A lane is a WINDOW SLOT {pair, c0, c1}: it owns the occurrences of its text whose text_end lies in (c0, c1] (c0 a multiple
+// of 64, c1 = min(c0 + window, n)) and nothing else.  Per member of m bases and effective bound k it walks three stretches:
+//   warm-up   (ws, c0], ws = max(0, c0 - 64 ceil((m + k) / 64)): a fresh INFIX sweep from column ws.  An occurrence of score
+//             <= k that ends at e starts no earlier than e - (m + k), so the sweep's row m equals the text's wherever that is
+//             <= k from column c0 on, and is above k wherever that is: min(R', k + 1) = min(R, k + 1) for every e >= c0, which
+//             is all the scan reads (qe_search.h) -- c0 itself is the `prev` of the first owned column.  ws = 0 is the text's
+//             own column 0.  The scan runs but owns nothing.
+//   owned     (c0, c1]: a descent makes a candidate.
+//   run-out   columns after c1, chunk by chunk while the candidate is still pending: a rise or the text's end emits it, a
+//             descent cancels it (SearchOwnedColumns: that valley is the next window's).
+// Every occurrence is owned by the one window that holds its text_end, so the lanes of a text together emit the text's set
+// once.  The lane's stretch holds its slice's occurrences in (member, text_end) order, the first `cap` of them.
+typedef SearchHitScanOf<PanelHitSink, SearchOwnedColumns> PanelWindowScan;
+QE_S_HD void panel_window_scan_init(PanelWindowScan& H, PanelRawHit* out, int32_t cap, int32_t c0, int32_t c1) {
+    H.lo = c0; H.hi = c1;
+    H.prev = 0; H.pend_end = -1; H.pend_val = 0; H.found = 0; H.best = -1;
+    H.sink.out = out; H.sink.cap = cap; H.sink.count = 0; H.sink.member = -1;
+}
+// the warm-up of a member: whole chunks, so that chunk boundaries and ownership boundaries coincide
+QE_S_HD int panel_window_warmup(int m, int bound) { return 64 * ((m + search_effective(bound, m) + 63) / 64); }
+
+// one member of NB blocks at the most against the window (c0, c1] of one text of n columns: the register form
+template <int NB, class Eq>
+QE_S_HD void panel_member_window(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int c0, int c1, PanelWindowScan& H, uint32_t& steps) {
+    SearchLane L;
+    search_lane_init(L, m, n, SEARCH_INFIX, bound, 0);
+    SearchRegStore<NB, Eq> R;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.load(pp, m);
+    H.begin(L);
+    search_store_init<NB>(R, L);
+    const int warm = panel_window_warmup(m, bound);
+    int col0 = c0 > warm ? c0 - warm : 0;
+    // warm-up and owned columns, then the run-out while a candidate is pending (c1 is a chunk boundary or the text's end)
+    for (; col0 < c1 || (col0 < n && H.pend_end >= 0); col0 += 64) {
+        const int ncols = n - col0 < 64 ? n - col0 : 64;
+        uint64_t t[Eq::W];
+        Eq::text_chunk(tp, col0, ncols, t);
+        search_chunk<NB>(R, L, t, col0, ncols, H);
+    }
+    H.finish();                                 // still pending: the walk reached the end of the text, where a plateau counts
+    steps += L.steps;
+}
+
+// The window (c0, c1] of one text (planes tp, n columns; c1 <= c0: nothing) against the members [p0, p1): every occurrence
+// the window owns goes to H's sink, H.found / H.best run on over the members; steps: block steps, added to
+template <class Eq>
+QE_S_HD void panel_window_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int c0, int c1, PanelWindowScan& H, uint32_t& steps) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        H.sink.member = p;
+        if (nb <= 1) panel_member_window<1, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
+        else if (nb == 2) panel_member_window<2, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_window<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
+    }
+}
+
+// k_panel_scan<Eq>: k_panel_hits' shape with window slots for text slots.  Window slot w (nslots of them, a multiple of 64)
+// is {w_pair[w] (-1: an empty slot), w_c0[w], w_c1[w]}; a text's slots are contiguous and ascending by window.  Per (slice s,
+// slot w): field f of {found, stored, best, steps} at part[(f nslices + s) nslots + w] and the stored occurrences as PanelRawHit
+// number i at raw[(s nslots + w) max_hits + i].  A slot without a text writes nothing.
+struct PanelScanArgs {
+    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
+    int32_t n_members, per_slice;
+    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
+    int32_t nslots;  const int32_t* w_pair;  const int32_t* w_c0;  const int32_t* w_c1;
+    int32_t max_hits;
+    int32_t* part;
+    PanelRawHit* raw;
+};
+// The counts, in two steps so that a long text's slots are not one thread's work.  One thread per (slice s, text slot t)
+// (k_panel_scan_sums; text[t] the pair, -1: none) over the text's window slots [first_slot[pair], + nwin[pair]): field f of
+// {found, stored saturating at max_hits, best, steps} of that slice at sums[(f nslices + s) ntext + t].  Then one thread per
+// text slot t (k_panel_scan_count) over the slices: found[pair], best[pair], len[pair] = stored - 1 and o_adv[t] as
+// panel_hits_count_slot leaves them, and per slice the rank of its first record among the text's: base[s ntext + t] = the
+// stored counts of the slices before s, saturating at max_hits.
+struct PanelScanCountArgs {
+    int32_t ntext, nslots, nslices, max_hits;
+    const int32_t* text;  const int32_t* first_slot;  const int32_t* nwin;  const int32_t* part;
+    int32_t* sums;
+    int32_t* found;  int32_t* best;  int32_t* len;  int32_t* base;  uint32_t* o_adv;
+};
+// One thread per lane (slice s, window slot w) (k_panel_scan_expand).  The rank of the lane's record r = (p, e) among its
+// text's records in (pattern, text_end) order is base[s][text] + the number of records with a smaller key in the lanes
+// (w', s) of the text's windows: r's own index for w' = w; for w' < w every end is smaller than e, so the records with member
+// <= p; for w' > w every end is larger, so those with member < p -- one binary search per window, repeated only when the
+// member changes.  A record whose rank is below max_hits goes to hits[off[pair] + rank] with its start-pass task at the same
+// index (as panel_hits_expand_slot writes them); the others are dropped.
+// Ranks below max_hits are exact although a lane keeps only its first max_hits: every record before r in its own lane is
+// before it in the text, so rank-in-lane <= rank-in-text and the text's first max_hits are all stored; and a lane that lost
+// a record q < r holds max_hits stored records that are all < q < r, which puts r's computed rank at max_hits or above.
+struct PanelScanExpandArgs {
+    int32_t ntext, nslots, nslices, max_hits;
+    const int32_t* w_pair;  const int32_t* w_text;  const int32_t* first_slot;  const int32_t* nwin;
+    const int32_t* part;  const PanelRawHit* raw;  const int32_t* base;
+    const int64_t* off;
+    const int32_t* m_len;  const int64_t* m_off;  const int32_t* t_len;  const int64_t* t_off;
+    int32_t* hits;
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;  int64_t* o_plp_off;  int64_t* o_plt_off;
+};
+
+QE_S_HD void panel_scan_store_part(const PanelScanArgs& A, int nslices, int slice, int slot, const PanelWindowScan& H, uint32_t steps) {
+    const int64_t stride = (int64_t)nslices * A.nslots;
+    int32_t* q = A.part + (int64_t)slice * A.nslots + slot;
+    q[0] = H.found; q[stride] = H.sink.count; q[2 * stride] = H.best; q[3 * stride] = (int32_t)steps;
+}
+QE_S_HD void panel_scan_sums_slice(const PanelScanCountArgs& A, int s, int t) {
+    const int pair = A.text[t];
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots, tstride = (int64_t)A.nslices * A.ntext;
+    const int w0 = A.first_slot[pair], w1 = w0 + A.nwin[pair];
+    int32_t found = 0, stored = 0, best = -1;
+    uint32_t steps = 0;
+    for (int w = w0; w < w1; ++w) {
+        const int32_t* q = A.part + (int64_t)s * A.nslots + w;
+        const int32_t b = q[2 * stride];
+        found += q[0];
+        stored = stored + q[stride] < A.max_hits ? stored + q[stride] : A.max_hits;
+        best = (b >= 0 && (best < 0 || b < best)) ? b : best;
+        steps += (uint32_t)q[3 * stride];
+    }
+    int32_t* o = A.sums + (int64_t)s * A.ntext + t;
+    o[0] = found; o[tstride] = stored; o[2 * tstride] = best; o[3 * tstride] = (int32_t)steps;
+}
+QE_S_HD void panel_scan_count_text(const PanelScanCountArgs& A, int t) {
+    const int pair = A.text[t];
+    if (pair < 0) return;
+    const int64_t tstride = (int64_t)A.nslices * A.ntext;
+    int32_t found = 0, stored = 0, best = -1;
+    uint32_t steps = 0;
+    for (int s = 0; s < A.nslices; ++s) {
+        const int32_t* q = A.sums + (int64_t)s * A.ntext + t;
+        const int32_t b = q[2 * tstride];
+        A.base[(int64_t)s * A.ntext + t] = stored;
+        found += q[0];
+        stored = stored + q[tstride] < A.max_hits ? stored + q[tstride] : A.max_hits;
+        best = (b >= 0 && (best < 0 || b < best)) ? b : best;
+        steps += (uint32_t)q[3 * tstride];
+    }
+    A.found[pair] = found; A.best[pair] = best; A.len[pair] = stored - 1;
+    A.o_adv[t] = steps;
+}
+// the records of a lane's stretch (sorted by member, `have` of them) with member < p (or_equal: <= p)
+QE_S_HD int32_t panel_scan_members_below(const PanelRawHit* raw, int32_t have, int32_t p, bool or_equal) {
+    int32_t lo = 0, hi = have;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        const int32_t q = raw[mid].pattern;
+        if (q < p || (or_equal && q == p)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+QE_S_HD void panel_scan_expand_lane(const PanelScanExpandArgs& A, int s, int w) {
+    const int pair = A.w_pair[w];
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots;
+    const int32_t* stored = A.part + stride + (int64_t)s * A.nslots;              // [slot], of this slice
+    const int32_t have = stored[w], base = A.base[(int64_t)s * A.ntext + A.w_text[w]];
+    if (have <= 0 || base >= A.max_hits) return;
+    const int w0 = A.first_slot[pair], w1 = w0 + A.nwin[pair];
+    const PanelRawHit* raw = A.raw + ((int64_t)s * A.nslots + w) * A.max_hits;
+    const int n = A.t_len[pair];
+    const int64_t j0 = A.off[pair];
+    int32_t member = -1, others = 0;
+    for (int32_t i = 0; i < have; ++i) {
+        const PanelRawHit h = raw[i];
+        if (h.pattern != member) {
+            member = h.pattern; others = 0;
+            for (int v = w0; v < w1 && base + i + others < A.max_hits; ++v)
+                if (v != w && stored[v] > 0)
+                    others += panel_scan_members_below(A.raw + ((int64_t)s * A.nslots + v) * A.max_hits, stored[v], member, v < w);
+        }
+        const int32_t rank = base + i + others;
+        if (rank >= A.max_hits) break;          // (ranks ascend within a lane)
+        const int64_t j = j0 + rank;
+        const int m = A.m_len[h.pattern];
+        int32_t task_n, in_end, start;
+        search_hit_task(m, n, h.end, h.score, task_n, in_end, start);
+        A.o_pair[j] = (int32_t)j; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = h.score; A.o_end[j] = in_end;
+        A.o_plp_off[j] = A.m_off[h.pattern]; A.o_plt_off[j] = A.t_off[pair];
+        int32_t* o = A.hits + 4 * j;
+        o[0] = h.pattern; o[1] = start; o[2] = h.end; o[3] = h.score;
+    }
+}
+
 }  // namespace qe

@@ -285,8 +285,18 @@ struct SearchHitSink {
 // Sink: where an occurrence goes, put(end, score) -- the one thing a caller may vary; what an occurrence is is decided here
 // and nowhere else.  A scan may serve several patterns against one text in turn (a panel lane: qe_panel.h): begin() starts a
 // pattern -- column 0, no candidate --, found / best / the sink run on.
-template <class Sink = SearchHitSink>
-struct SearchHitScanOf {
+//
+// Range: which columns a descent may make a candidate in.  SearchAllColumns (the default: every column, no state) is the scan
+// of a lane that walks a whole text; SearchOwnedColumns is a lane that owns the columns (lo, hi] of a text other lanes walk
+// too (a window of quicked_batch_run_panel_scan): a descent outside the range clears the candidate -- the
+// valley it starts is another lane's --, everything else is the same walk.
+struct SearchAllColumns { QE_S_HD bool owns(int32_t) const { return true; } };
+struct SearchOwnedColumns {
+    int32_t lo, hi;
+    QE_S_HD bool owns(int32_t end) const { return end > lo && end <= hi; }
+};
+template <class Sink = SearchHitSink, class Range = SearchAllColumns>
+struct SearchHitScanOf : Range {
     int32_t prev, pend_end, pend_val, found, best;
     Sink sink;
     QE_S_HD void begin(const SearchLane& L) {
@@ -314,7 +324,7 @@ struct SearchHitScanOf {
         for (int c = 0; c < ncols; ++c) {
             v += (int32_t)((oP >> c) & 1) - (int32_t)((oM >> c) & 1);
             const int32_t w = v <= L.k ? v : L.k + 1;
-            if (w < prev) { pend_end = col0 + c + 1; pend_val = w; }      // a descent (w <= k: prev <= k + 1); an older candidate was no valley
+            if (w < prev) { pend_end = Range::owns(col0 + c + 1) ? col0 + c + 1 : -1; pend_val = w; }      // a descent (w <= k: prev <= k + 1); an older candidate was no valley
             else if (w > prev) emit();
             prev = w;
         }

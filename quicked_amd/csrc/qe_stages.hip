@@ -1548,6 +1548,146 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     return O;
 }
 
+// Every occurrence of every member, long texts split across lanes (quicked_batch_run_panel_scan): the run
+// above with a window slot {pair, c0, c1} per lane.  The slot table is built on the host -- the texts in the batch's length
+// order, a text's windows contiguous and ascending, padded to whole waves -- and goes up in one block with the per-pair
+// {first_slot, nwin}; k_panel_scan over window groups x slices leaves counts and raw records per (slice, slot);
+// k_panel_scan_sums (one thread per slice and text) and k_panel_scan_count (one per text) merge the counts and leave every
+// slice's rank base; k_scan_offsets and the total
+// as above; k_panel_scan_expand (one thread per lane) ranks the records among their text's and writes them and their
+// start-pass tasks; the start pass and k_panel_hits_finish are the run's above, unchanged.
+//
+// The library's window (window == 0).  A multiple of 64; enough window groups that groups x slices reach about twice the
+// resident wave slots with the panel cut as finely as it can be (slices cost no warm-up, windows do): groups = ceil(2 slots2
+// / K) rounded down to whole workgroups of four, window = the batch's text columns / (64 groups) rounded up; never below max(1024, 8 x the longest warm-up), so that a lane's
+// warm-up is at most an eighth of what it owns; then doubled until the window slots x max_hits fit 2^26 (one window per text
+// does, or the entry point has refused the run).  The 1024 and the eighth rest on the sweep in profiles/panel_scan.md as
+// far as it reaches; 2 slots2 is panel_slices' figure and was not swept again.
+static int32_t panel_scan_window(const quicked_batch& B, const Context& C, const SearchRun& sr) {
+    if (sr.window > 0) return sr.window;
+    const PanelRun& pr = *sr.panel;
+    int64_t columns = 0, longest = 0, warm = 64;
+    for (int64_t i = 0; i < B.n; ++i) { columns += B.t_len[(size_t)i]; longest = std::max<int64_t>(longest, B.t_len[(size_t)i]); }
+    for (int32_t p = 0; p < pr.n_patterns; ++p) warm = std::max<int64_t>(warm, panel_window_warmup(pr.len[p], sr.max_dist ? sr.max_dist[p] : sr.max_dist_all));
+    const int64_t whole = std::min<int64_t>(std::max<int64_t>(64, (longest + 63) / 64 * 64), 0x7FFFFFC0);      // one window per text
+    // (whole workgroups of four groups, rounded down, and the window rounded up: one group over two rounds of the chip is a third)
+    const int64_t groups = std::max<int64_t>(4, (2 * (int64_t)chip(C.device).slots2() + pr.n_patterns - 1) / pr.n_patterns / 4 * 4);
+    int64_t w = (columns + 64 * groups - 1) / (64 * groups);
+    w = (w + 63) / 64 * 64;
+    w = std::min(whole, std::max<int64_t>(w, std::max<int64_t>(1024, 8 * warm)));
+    while (w < whole && panel_scan_slots(B, w) * sr.max_hits > ((int64_t)1 << 26)) w = std::min(whole, 2 * w);
+    return (int32_t)w;
+}
+struct PanelScanTable {                            // window slot -> {pair (-1 in the padding), text slot, c0, c1}; pair -> {first_slot, nwin}
+    std::vector<int32_t> w_pair, w_text, w_c0, w_c1, first_slot, nwin;
+};
+static void panel_scan_table(const quicked_batch& B, const std::vector<int32_t>& text, int32_t window, PanelScanTable& T) {
+    T.first_slot.assign((size_t)B.n, 0); T.nwin.assign((size_t)B.n, 0);
+    for (size_t t = 0; t < text.size(); ++t) {
+        const int32_t pair = text[t];
+        if (pair < 0) continue;
+        const int64_t n = B.t_len[(size_t)pair];
+        T.first_slot[(size_t)pair] = (int32_t)T.w_pair.size();
+        for (int64_t c0 = 0; c0 < n; c0 += window) {
+            T.w_pair.push_back(pair); T.w_text.push_back((int32_t)t);
+            T.w_c0.push_back((int32_t)c0); T.w_c1.push_back((int32_t)std::min<int64_t>(n, c0 + window));
+            ++T.nwin[(size_t)pair];
+        }
+    }
+    while (T.w_pair.size() % 64) { T.w_pair.push_back(-1); T.w_text.push_back(-1); T.w_c0.push_back(0); T.w_c1.push_back(0); }
+}
+static int panel_scan_slices(const Context& C, size_t wslots, int K, int max_hits) { return panel_hits_slices(C, wslots, K, max_hits); }
+// the planner's fixed needs: panel_shared_bytes, the slot table, the partials, rank bases and the raw buffer at the slices the
+// host would choose, the per-pair arrays; what is sized by the total is not planned, as in run_search_panel_hits
+static size_t panel_scan_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
+    size_t ntext = 0, b = panel_shared_bytes(B, sr, ntext);
+    const size_t n = (size_t)B.n, wslots = ((size_t)panel_scan_slots(B, panel_scan_window(B, C, sr)) + 63) / 64 * 64;
+    const size_t nslices = (size_t)panel_scan_slices(C, wslots, sr.panel->n_patterns, sr.max_hits);
+    b += nslices * wslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit)) + 5 * nslices * ntext * sizeof(int32_t);
+    b += wslots * 16 + n * 8 + ntext * 8 + n * 12 + (n + 1) * 8 + 16 * 512;
+    return b;
+}
+static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchRun& sr) {
+    const PanelRun& pr = *sr.panel;
+    const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
+    HitsOut O;
+    const PanelDev D = panel_upload(B, C, sr);
+    O.task_pair = D.text;
+    if (O.task_pair.empty()) return O;
+    const size_t n = (size_t)B.n, ntext = D.nslots;
+    // ---- the window slots
+    PanelScanTable T;
+    panel_scan_table(B, D.text, panel_scan_window(B, C, sr), T);
+    const size_t nslots = T.w_pair.size(), ngroups = nslots / 64;
+    // one block, one copy: {w_pair | w_text | w_c0 | w_c1 | first_slot | nwin}, every array on a 16-byte boundary (the copy kernel
+    // moves whole uint4 and rounds a copy's end up)
+    const size_t n4 = (n + 3) & ~(size_t)3;
+    static thread_local std::vector<int32_t> tab;
+    tab.assign(4 * nslots + 2 * n4, 0);
+    const std::vector<int32_t>* src[6] = {&T.w_pair, &T.w_text, &T.w_c0, &T.w_c1, &T.first_slot, &T.nwin};
+    for (int q = 0; q < 6; ++q) memcpy(tab.data() + (q < 4 ? (size_t)q * nslots : 4 * nslots + (size_t)(q - 4) * n4), src[q]->data(), src[q]->size() * sizeof(int32_t));
+    int32_t* d_tab = C.scratch_p->take<int32_t>(tab.size());
+    h2d(d_tab, tab, C.stream);
+    int32_t *d_w_pair = d_tab, *d_w_text = d_tab + nslots, *d_w_c0 = d_tab + 2 * nslots, *d_w_c1 = d_tab + 3 * nslots;
+    int32_t *d_first = d_tab + 4 * nslots, *d_nwin = d_first + n4;
+    // ---- the forward pass
+    const int want = panel_scan_slices(C, nslots, K, max_hits), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    PanelScanArgs a{};
+    a.pl_m = panel_planes(B, C, D, K, eq, false); a.m_off = D.d_pl_off; a.m_len = D.d_len; a.m_bound = D.d_bound;
+    a.n_members = K; a.per_slice = per_slice;
+    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
+    a.nslots = (int32_t)nslots; a.w_pair = d_w_pair; a.w_c0 = d_w_c0; a.w_c1 = d_w_c1; a.max_hits = max_hits;
+    a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
+    a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
+    int32_t* const d_base = C.scratch_p->take<int32_t>((size_t)nslices * ntext);
+    int32_t* const d_plen = hits_arrays(C, O, n, ntext);
+    TimedLaunches tl(C, 0);
+    {
+        // k_panel_hits' launch shape: four window groups per workgroup and launch_groups' claim on the CU's LDS
+        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
+        if (eq) hipLaunchKernelGGL(k_panel_scan<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+        else hipLaunchKernelGGL(k_panel_scan<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    tl.end();
+    // ---- counts per pair and rank bases per (slice, text), offsets in the order of the pairs, the total
+    PanelScanCountArgs c{};
+    c.ntext = (int32_t)ntext; c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits;
+    c.text = D.d_text; c.first_slot = d_first; c.nwin = d_nwin; c.part = a.part;
+    c.sums = C.scratch_p->take<int32_t>(4 * (size_t)nslices * ntext);
+    c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.base = d_base; c.o_adv = O.d_adv;
+    hipLaunchKernelGGL(k_panel_scan_sums, dim3((unsigned)((ntext + 255) / 256), (unsigned)nslices), dim3(256), 0, C.stream, c);
+    hipLaunchKernelGGL(k_panel_scan_count, dim3((unsigned)((ntext + 255) / 256)), dim3(256), 0, C.stream, c);
+    hits_total(B, C, O, d_plen, B.d_t_len);
+    if (O.total <= 0) return O;
+    const size_t nh = (size_t)O.total;
+    O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
+    PanelScanExpandArgs e{};
+    e.ntext = (int32_t)ntext; e.nslots = (int32_t)nslots; e.nslices = nslices; e.max_hits = max_hits;
+    e.w_pair = d_w_pair; e.w_text = d_w_text; e.first_slot = d_first; e.nwin = d_nwin;
+    e.part = a.part; e.raw = a.raw; e.base = d_base; e.off = O.d_off;
+    e.m_len = D.d_len; e.m_off = D.d_pl_off; e.t_len = B.d_t_len; e.t_off = B.d_plt_off; e.hits = O.d_hits;
+    int32_t* const q = C.scratch_p->take<int32_t>(6 * nh);
+    e.o_pair = q; e.o_m = q + nh; e.o_n = q + 2 * nh; e.o_score = q + 3 * nh; e.o_end = q + 4 * nh;
+    int32_t* const o_start = q + 5 * nh;
+    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
+    e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
+    e.o_plt_off = e.o_plp_off + nh;
+    O.d_adv2 = C.scratch_p->take<u32>(nh);
+    HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
+    hipLaunchKernelGGL(k_panel_scan_expand, dim3((unsigned)((nslots + 255) / 256), (unsigned)nslices), dim3(256), 0, C.stream, e);
+    HIP_CHECK(hipGetLastError());
+    // ---- the start pass: one lane per stored occurrence over its window, reversed
+    if (!eq) ensure_reversed(B, C);
+    PairView PV = pair_view(B, true);
+    PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
+    PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
+    launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
+    hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
+    HIP_CHECK(hipGetLastError());
+    return O;
+}
+
 // One wave per alignment wherever the strings are more than a few runs long, else one lane per alignment.  Decided before the
 // traceback runs: the wave form wants every task's runs in a stretch of their own (TraceArgs::runs_by_task).  Round 5: the
 // wave form used to be kept for few alignments or very long reads; measured per read length and batch size
