@@ -273,8 +273,8 @@ quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* sco
  *     the other members is its {second_pattern, second_score};
  *  2. member p's smallest score, and the first end that has it, is the QUICKED_PANEL_MATRIX entry [i][p].
  *
- * QUICKED_ERROR, nothing launched: a NULL batch; a base mode that is not PREFIX or INFIX; both IUPAC flags or any other bit
- * (QUICKED_PANEL_MATRIX too: it has no meaning here); n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0;
+ * QUICKED_ERROR, nothing launched: a NULL batch; a base mode that is not PREFIX or INFIX; both IUPAC flags or any other bit but
+ * QUICKED_PANEL_CIGARS (QUICKED_PANEL_MATRIX too: it has no meaning here); n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0;
  * a negative bound; max_hits outside 1 .. 4096; (non-empty texts) x max_hits above 2^26.
  * QUICKED_UNIMPLEMENTED, nothing queued: a member longer than QUICKED_PANEL_MAX_LEN bases; sync == 0 (the host reads the total
  * between the passes); a batch configured with check != 0.
@@ -282,7 +282,8 @@ quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* sco
  * quicked_batch_panel_results, quicked_batch_panel_matrix, quicked_batch_hits, quicked_batch_hit_counts,
  * quicked_batch_locations and the CIGAR and tag getters return what they return after any run that produced none of their
  * data.  Tags are ignored.  Counters [0] and kernel_times slot [0] count both passes, as for the other search runs.  A reload
- * clears the results.  Not built: queued runs, members over 256 bases, alignments of occurrences. */
+ * clears the results.  Not built: queued runs, members over 256 bases, alignments for quicked_batch_run_panel and
+ * quicked_batch_run_search_all (this run has them: QUICKED_PANEL_CIGARS below), statistics and MD tags per occurrence. */
 typedef struct { int32_t pattern, text_start, text_end, score; } quicked_panel_occ_t;   /* 16 bytes */
 quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode,
                                              int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
@@ -316,12 +317,51 @@ quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_
  * QUICKED_UNIMPLEMENTED, nothing queued: the base mode QUICKED_SEARCH_PREFIX (a PREFIX occurrence within the bound ends in the
  * first m + k columns: quicked_batch_run_panel_all serves it); a member longer than QUICKED_PANEL_MAX_LEN bases; sync == 0; a
  * batch configured with check != 0.
- * Not built: a cap above 4096 per text, queued runs, members over 256 bases, alignments of occurrences, and windows for
- * quicked_batch_run_panel / _run_search / _run_search_all. */
+ * Not built: a cap above 4096 per text, queued runs, members over 256 bases, alignments of occurrences of
+ * quicked_batch_run_panel and _run_search_all (this run and quicked_batch_run_panel_all have them: QUICKED_PANEL_CIGARS below),
+ * statistics and MD tags per occurrence, and windows for quicked_batch_run_panel / _run_search / _run_search_all. */
 quicked_status_t quicked_batch_run_panel_scan(quicked_batch_t* batch, int mode,
                                               int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
                                               const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all,
                                               int32_t max_hits, int32_t window, int sync);
+/* The alignment of every stored occurrence.  QUICKED_PANEL_CIGARS is OR-ed into `mode` of quicked_batch_run_panel_all and
+ * quicked_batch_run_panel_scan, beside the two IUPAC flags.  Without the bit nothing about either run changes.  With it every
+ * result the unflagged run leaves is left unchanged -- found, stored, the records and their order, scores, statuses, counter
+ * [0], the refusals of the other getters; quicked_batch_cigars still returns -1 for every pair -- and every stored occurrence j
+ * (the index into quicked_batch_panel_hits' array) gets the CIGAR of the GLOBAL alignment of its member against
+ * text[text_start, text_end), in the cigar_style of quicked_batch_configure (0, 1, 2, style 2 with the "1X" of a leading mismatch
+ * as the pair runs print it).
+ *
+ * Which alignment.  D is the edit-distance matrix of the member (rows 1 .. m) against the stretch (columns 1 .. L) with
+ * D[0][j] = j and D[i][0] = i.  From (m, L), while i > 0 and j > 0: D[i][j] == D[i-1][j] + 1 emits D and decrements i; else
+ * D[i][j-1] == D[i-1][j-1] - 1 emits I and decrements j; else M where the two symbols are equal, X where not, and both are
+ * decremented.  The columns left are I, the rows left D; the string is that sequence reversed.  This is the traceback of the pair
+ * runs (the reference's) on the full matrix: on ACGT input the string is the one quicked_batch_run_bounded gives for (member,
+ * stretch) with bound = score.  It has exactly `score` edits, consumes m member symbols (M X D) and text_end - text_start text
+ * symbols (M X I), and never ends with I; an INFIX string never begins with I either (a PREFIX stretch starts at column 0
+ * wherever the occurrence does, so its string may).
+ * M means "equal under the run's equality": under the flags the sets intersect (R against A is M; a text N under
+ * QUICKED_SEARCH_IUPAC_PATTERN is X); unflagged, case is folded and any two bytes that are not A C G T are equal.  I consumes
+ * text, D consumes the member, as in every CIGAR of this library.
+ *
+ * quicked_batch_panel_hit_cigars copies the pool (quicked_batch_panel_hit_cigar_bytes bytes) and one offset per stored
+ * occurrence (quicked_batch_panel_hit_total of them); the string of occurrence j is NUL-terminated at pool + off[j].  off[j]
+ * is never -1 for a stored occurrence of a run that returned QUICKED_OK.  The pool is padded between the strings (with unspecified bytes): only off and
+ * the strings are the contract.  Both getters return QUICKED_ERROR / -1 after any run without the bit and after a reload.
+ * A run returns QUICKED_ERROR with off[j] = -1 where the aligner did not reach (0, 0) with the occurrence's score: the sweeps
+ * and the aligner disagree, which is a defect of the library and is not hidden.
+ *
+ * QUICKED_ERROR, nothing launched: the bit on quicked_batch_run_panel (any unknown bit there: the best member's alignment is the
+ * first record with the smallest key of quicked_batch_run_panel_all); the bit together with QUICKED_PANEL_MATRIX.  Every other
+ * refusal of the two runs stands.  The tags of quicked_batch_configure_tags stay ignored.
+ * Counters: [0] and kernel_times slot [0] are the unflagged run's; counter [1] is the block steps of the alignment sweep,
+ * counter [3] the operations emitted, kernel_times slot [1] the alignment launches (QE_PANEL_ALIGN_WS_KB bounds the pass's
+ * workspace; more occurrences than fit are aligned in several launches).
+ * Not built: alignments for quicked_batch_run_panel and quicked_batch_run_search_all (whose patterns may exceed 256 bases),
+ * statistics and MD tags per occurrence, queued runs. */
+enum { QUICKED_PANEL_CIGARS = 512 };           /* OR-ed into mode of quicked_batch_run_panel_all / _scan, beside the two IUPAC flags (128 and 256 stay unknown bits) */
+int64_t          quicked_batch_panel_hit_cigar_bytes(quicked_batch_t* batch);   /* -1 unless the last run was a flagged run */
+quicked_status_t quicked_batch_panel_hit_cigars(quicked_batch_t* batch, char* pool, int64_t* off /* hit_total entries */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -63,6 +63,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_run_search_all", "quicked_batch_hit_counts", "quicked_batch_hit_total", "quicked_batch_hits",
            "quicked_batch_run_panel", "quicked_batch_panel_results", "quicked_batch_panel_matrix",
            "quicked_batch_run_panel_all", "quicked_batch_run_panel_scan", "quicked_batch_panel_hit_counts", "quicked_batch_panel_hit_total", "quicked_batch_panel_hits",
+           "quicked_batch_panel_hit_cigar_bytes", "quicked_batch_panel_hit_cigars",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -70,6 +71,7 @@ HIT_DTYPE = np.dtype([("text_start", np.int32), ("text_end", np.int32), ("score"
 SEARCH_PREFIX, SEARCH_INFIX = 1, 2
 SEARCH_IUPAC, SEARCH_IUPAC_PATTERN = 16, 32      # OR-ed into a search mode: IUPAC base sets on both sides / on the pattern only
 PANEL_MATRIX = 64                                # OR-ed into a panel run's mode: keep every {score, text_end}
+PANEL_CIGARS = 512                               # OR-ed into run_panel_all's / run_panel_scan's mode: every stored occurrence's alignment
 PANEL_MAX_PATTERNS, PANEL_MAX_LEN = 4096, 256
 PANEL_HIT_DTYPE = np.dtype([("pattern", np.int32), ("score", np.int32), ("text_start", np.int32), ("text_end", np.int32),
                             ("second_pattern", np.int32), ("second_score", np.int32)])      # quicked_panel_hit_t
@@ -143,6 +145,11 @@ def lib():
     L.quicked_batch_panel_hit_total.restype = C.c_int64
     L.quicked_batch_panel_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_panel_hits.restype = C.c_int
+    if hasattr(L, "quicked_batch_panel_hit_cigars"):      # (an older build loaded for an A/B run lacks the newer symbols)
+        L.quicked_batch_panel_hit_cigar_bytes.argtypes = [C.c_void_p]
+        L.quicked_batch_panel_hit_cigar_bytes.restype = C.c_int64
+        L.quicked_batch_panel_hit_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.quicked_batch_panel_hit_cigars.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -505,7 +512,8 @@ class ResidentBatch:
 
     def run_panel_all(self, mode, panel, max_dist=None, max_hits=16, sync=True):
         """quicked_batch_run_panel_all: every occurrence of every panel member in every text, at most max_hits (1 .. 4096) stored
-        per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag).  Sync runs only."""
+        per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag); PANEL_CIGARS OR-ed into
+        mode aligns every stored occurrence besides (panel_hit_cigars()).  Sync runs only."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -527,7 +535,8 @@ class ResidentBatch:
     def run_panel_scan(self, mode, panel, max_dist=None, max_hits=16, window=0, sync=True):
         """quicked_batch_run_panel_scan: run_panel_all's results, exactly, with every text cut into windows of `window` columns
         (0: the library's choice; else a multiple of 64) and a lane per window: for a few long texts.  INFIX only; mode's flags,
-        panel, max_dist and max_hits as in run_panel_all.  Read through panel_hit_counts() / panel_hits().  Sync runs only."""
+        panel, max_dist and max_hits as in run_panel_all (PANEL_CIGARS included).  Read through panel_hit_counts() / panel_hits() /
+        panel_hit_cigars().  Sync runs only."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -566,6 +575,22 @@ class ResidentBatch:
         if st < 0:
             raise QuickedException(st)
         return off, hits
+
+    def panel_hit_cigars(self):
+        """-> [str], one per stored occurrence in panel_hits() order, of the last run_panel_all / run_panel_scan whose mode had
+        PANEL_CIGARS: the global alignment of the occurrence's member against text[text_start:text_end] in the batch's
+        cigar_style (None where the run reported a disagreement).  QuickedException after any other run"""
+        nbytes = self._lib.quicked_batch_panel_hit_cigar_bytes(self._h)
+        total = self._lib.quicked_batch_panel_hit_total(self._h)
+        if nbytes < 0 or total < 0:
+            raise QuickedException(QUICKED_ERROR)
+        pool = np.zeros(max(int(nbytes), 1), dtype=np.uint8)
+        off = np.zeros(max(int(total), 1), dtype=np.int64)
+        st = self._lib.quicked_batch_panel_hit_cigars(self._h, pool.ctypes.data, off.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        raw = pool.tobytes()
+        return [None if o < 0 else raw[o:raw.index(b"\0", o)].decode() for o in off[:total].tolist()]
 
     def locations(self):
         """-> (text_start, text_end) int32 arrays of the last search run: the located stretch is text[start:end]; -1 / -1 for a

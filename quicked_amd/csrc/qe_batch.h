@@ -115,9 +115,14 @@ struct quicked_batch {
         std::vector<int32_t> panel_found;
         std::vector<int64_t> panel_occ_off;
         std::vector<quicked_panel_occ_t> panel_occ;
+        // ... run with QUICKED_PANEL_CIGARS: panel_cigars, and the string of stored occurrence j NUL-terminated at panel_cig_pool +
+        // panel_cig_off[j] (quicked_batch_panel_hit_cigars); else false and empty
+        bool panel_cigars = false;
+        std::vector<int64_t> panel_cig_off;
+        std::vector<char> panel_cig_pool;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; panel_found.clear(); panel_occ_off.clear(); panel_occ.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; panel_found.clear(); panel_occ_off.clear(); panel_occ.clear(); panel_cigars = false; panel_cig_off.clear(); panel_cig_pool.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -222,7 +227,8 @@ struct BoundedRun { const int32_t* max_dist; int32_t max_dist_all; };
 struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; const int32_t* len; bool matrix; };
 // ... and window >= 0: the same run with long texts split across lanes (quicked_batch_run_panel_scan): a lane owns `window` text
 // columns, 0 the library's choice (panel_scan_window); its results are an all-occurrences panel run's
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; };
+// ... and cigars: QUICKED_PANEL_CIGARS, every stored occurrence's alignment besides (run_panel_align)
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; bool cigars = false; };
 // the window slots of a batch at `window` columns per lane: every non-empty text in ceil(n / window) of them
 inline int64_t panel_scan_slots(const quicked_batch& B, int64_t window) {
     int64_t slots = 0;

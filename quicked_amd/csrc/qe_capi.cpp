@@ -364,12 +364,13 @@ static_assert(sizeof(quicked_panel_occ_t) == 16, "quicked_panel_occ_t is four in
 QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
                                                     const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
                                                     int32_t max_dist_all, int32_t max_hits, int sync) {
-    const int eq = search_mode_eq(mode);                                            // (QUICKED_PANEL_MATRIX is "any other bit" here)
+    const bool cigars = (mode & QUICKED_PANEL_CIGARS) != 0;                         // every stored occurrence's alignment besides
+    const int eq = search_mode_eq(mode & ~QUICKED_PANEL_CIGARS);                    // (QUICKED_PANEL_MATRIX is "any other bit" here)
     bool too_long = false;
     if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
-    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr}, too_long, sync};
+    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, -1, cigars}, too_long, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         int64_t texts = 0;
@@ -386,13 +387,14 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
 QE_API quicked_status_t quicked_batch_run_panel_scan(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
                                                      const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
                                                      int32_t max_dist_all, int32_t max_hits, int32_t window, int sync) {
-    const int eq = search_mode_eq(mode);
+    const bool cigars = (mode & QUICKED_PANEL_CIGARS) != 0;
+    const int eq = search_mode_eq(mode & ~QUICKED_PANEL_CIGARS);
     bool too_long = false;
     if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     if (window < 0 || window % 64 != 0 || window > 0x7FFFFFC0) return QUICKED_ERROR;
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
-    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, window}, too_long, sync};
+    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, window, cigars}, too_long, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         int64_t texts = 0;
@@ -414,6 +416,19 @@ QE_API quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, i
 QE_API int64_t quicked_batch_panel_hit_total(quicked_batch_t* batch) { return hit_total(batch, &HostResults::panel_found, &HostResults::panel_occ_off); }
 QE_API quicked_status_t quicked_batch_panel_hits(quicked_batch_t* batch, quicked_panel_occ_t* hits, int64_t* hit_off) {
     return hit_lists(batch, &HostResults::panel_found, &HostResults::panel_occ_off, &HostResults::panel_occ, hits, hit_off);
+}
+
+// The strings of a run with QUICKED_PANEL_CIGARS, laid out like the CIGAR getters' pool and offsets
+QE_API int64_t quicked_batch_panel_hit_cigar_bytes(quicked_batch_t* batch) {
+    const HostResults* R = hit_results(batch, &HostResults::panel_found);
+    return (R && R->panel_cigars) ? (int64_t)R->panel_cig_pool.size() : -1;
+}
+QE_API quicked_status_t quicked_batch_panel_hit_cigars(quicked_batch_t* batch, char* pool, int64_t* off) {
+    const HostResults* R = hit_results(batch, &HostResults::panel_found);
+    if (!R || !R->panel_cigars) return QUICKED_ERROR;
+    if (pool && !R->panel_cig_pool.empty()) memcpy(pool, R->panel_cig_pool.data(), R->panel_cig_pool.size());
+    if (off && !R->panel_cig_off.empty()) memcpy(off, R->panel_cig_off.data(), R->panel_cig_off.size() * sizeof(int64_t));
+    return QUICKED_OK;
 }
 
 QE_API quicked_status_t quicked_batch_sync(quicked_batch_t* batch) {

@@ -35,6 +35,7 @@
 #include "qe_bounded.h"
 #include "qe_search.h"
 #include "qe_panel.h"
+#include "qe_panel_align.h"
 #include "qe_tags.h"
 // the kernels: this translation unit's device half.  (QE_KERNELS_HEADER: the sanitizer build of the host half on a machine
 // without a GPU names tests/native/hip_stub/qe_kernels_stub.h here, which holds every host stand-in of a kernel -- none lives
@@ -47,6 +48,9 @@
 #if !defined(__HIPCC__) && defined(__has_include)
 #if __has_include("qe_kernels_stub_scan.h")
 #include "qe_kernels_stub_scan.h"
+#endif
+#if __has_include("qe_kernels_stub_align.h")
+#include "qe_kernels_stub_align.h"
 #endif
 #endif
 
@@ -678,13 +682,21 @@ static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 
 // The one read-back of an all-occurrences run, pairs or panel: found / offsets / the stored occurrences into the result vectors
 // named, the smallest score as every searched pair's score, the block steps of both passes into counter 0
+// A run with QUICKED_PANEL_CIGARS brings the strings' offsets and pool and the alignment pass's counts in the same read-back:
+// block steps into counter 1, operations into counter 3.  -> false: a lane's alignment did not end at (0, 0) with its score
 template <class Occ>
-static void fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
+static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
     const size_t n = (size_t)B.n, nh = (size_t)HO.total;
-    std::vector<int32_t> best; std::vector<u32> adv, adv2;
+    std::vector<int32_t> best; std::vector<u32> adv, adv2, al;
     occ.resize(nh);
     {
         FetchBatch fb(C);
+        if (HO.cigars) {
+            B.wr->panel_cig_pool.resize((size_t)HO.cig_bytes);
+            fb.add(B.wr->panel_cig_off, (const int64_t*)HO.d_cig_off, nh);
+            fb.add_bytes(B.wr->panel_cig_pool.data(), HO.d_cig_pool, (size_t)HO.cig_bytes);
+            fb.add(al, (const u32*)HO.d_al_steps, 2 * nh);
+        }
         fb.add(found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
         fb.add(off, (const int64_t*)HO.d_off, n + 1);
         fb.add(adv, (const u32*)HO.d_adv, HO.task_pair.size());
@@ -694,6 +706,10 @@ static void fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
     }
     B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
     for (const int32_t pr : HO.task_pair) if (pr >= 0) { B.wr->score[pr] = best[(size_t)pr]; B.wr->status[pr] = QUICKED_OK; }
+    bool ok = true;
+    for (size_t j = 0; j < al.size(); ++j) B.counters[j < nh ? 1 : 3] += (int64_t)al[j];
+    for (const int64_t o : B.wr->panel_cig_off) ok = ok && o >= 0;
+    return ok;
 }
 
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd, const SearchRun* sr) {
@@ -906,8 +922,10 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         // the order of the texts and (pattern, text_end) within a text, in one read-back
         enter_a();
         // (window >= 0: the same results from window slots, quicked_batch_run_panel_scan)
-        fetch_hits(B, C, sr->window >= 0 ? run_search_panel_scan(B, C, *sr) : run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
-        ret = QUICKED_OK;
+        // (with QUICKED_PANEL_CIGARS: the getters of the strings answer after this run, whether or not it stored an occurrence)
+        B.wr->panel_cigars = sr->cigars;
+        const bool aligned = fetch_hits(B, C, sr->window >= 0 ? run_search_panel_scan(B, C, *sr) : run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
+        ret = aligned ? QUICKED_OK : QUICKED_ERROR;
     } else if (sr && sr->panel) {
         // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every
         // {d, text_end}, in one read-back

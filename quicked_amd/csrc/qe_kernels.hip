@@ -32,6 +32,7 @@
 #include "qe_bounded.h"
 #include "qe_search.h"
 #include "qe_panel.h"
+#include "qe_panel_align.h"
 #include "qe_pack.h"
 #include "qe_tags.h"
 #include "qe_check.h"
@@ -1762,6 +1763,23 @@ __global__ __launch_bounds__(256) void k_panel_scan_count(PanelScanCountArgs A) 
 __global__ __launch_bounds__(256) void k_panel_scan_expand(PanelScanExpandArgs A) {
     const int w = blockIdx.x * 256 + threadIdx.x;
     if (w < A.nslots) panel_scan_expand_lane(A, (int)blockIdx.y, w);
+}
+
+// The alignment of every stored occurrence (qe_panel_align.h; QUICKED_PANEL_CIGARS): one lane per occurrence
+// of the launch, a thin shell around panel_align_occ.  Nothing about a lane is wave-uniform -- a wave holds occurrences of
+// several members and texts, as the start pass's does: the plane words, {Pv, Mv} of up to four blocks and the writer are per
+// lane.  The wave's history is its own stretch of A.hist, [column][block][lane]: a store of one column and block is 64
+// consecutive 16-byte cells.  The string goes backwards into the lane's slot of the pool, byte by byte.
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_occ_align(PanelAlignArgs A) {
+    panel_align_occ<Eq>(A, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+template __global__ void k_panel_occ_align<SearchEq3>(PanelAlignArgs);
+template __global__ void k_panel_occ_align<SearchEqIupac>(PanelAlignArgs);
+// the slots' sizes, for k_scan_offsets
+__global__ __launch_bounds__(256) void k_panel_align_sizes(int64_t total, const int32_t* __restrict__ hits, int32_t* __restrict__ len) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < total) panel_align_size_one(j, hits, len);
 }
 
 

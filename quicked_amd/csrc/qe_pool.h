@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, ScoreLds, ScoreTall, TagsWave, SearchForm, SearchHitsWsKb, PanelSlices, PanelHitsRawKb, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, ScoreLds, ScoreTall, TagsWave, SearchForm, SearchHitsWsKb, PanelSlices, PanelHitsRawKb, PanelAlignWsKb, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -118,6 +118,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::SearchHitsWsKb, "QE_SEARCH_HITS_WS_KB", 262144},      // all-occurrences runs (quicked_batch_run_search_all): KiB of workspace the start pass's workspace-form launches share; more groups than fit run in slices (tests force slices with a small value)
     {Sw::PanelSlices, "QE_PANEL_SLICES", -1},          // panel runs (quicked_batch_run_panel): unset, the host's choice of panel slices (panel_slices: one while the text groups fill the chip, else enough for about twice the resident wave slots); set, that many, clamped to 1 .. the panel's size (tests, tools/search_panel_bench.py)
     {Sw::PanelHitsRawKb, "QE_PANEL_HITS_RAW_KB", 1048576},     // all-occurrences panel runs (quicked_batch_run_panel_all): KiB the raw occurrence buffer (slices x slots x max_hits records of 12 bytes) may take; the slice count -- the host's or QE_PANEL_SLICES' -- is lowered until it fits, never below one (tests force that with a small value)
+    {Sw::PanelAlignWsKb, "QE_PANEL_ALIGN_WS_KB", 1048576},     // ... with QUICKED_PANEL_CIGARS: KiB the alignment pass's history (columns x blocks x 64 cells of 16 bytes per wave of occurrences) may take; more waves than fit run in sub-batches that share it, never fewer than one wave at a time (tests force that with a small value)
 };
 inline constexpr int switch_count = (int)Sw::Count;
 constexpr bool switch_rows_in_order() {

@@ -1123,6 +1123,10 @@ struct HitsOut {                                   // of both all-occurrences ru
     std::vector<int32_t> task_pair;                // task (panel: slot) -> pair, -1 in the padding
     int32_t *d_found = nullptr, *d_best = nullptr, *d_hits = nullptr; int64_t* d_off = nullptr; u32 *d_adv = nullptr, *d_adv2 = nullptr;
     int64_t total = 0;
+    // QUICKED_PANEL_CIGARS (run_panel_align): per stored occurrence where its string starts in the pool (-1: the aligner and the
+    // sweeps disagree) and its block steps | operations; the pool's bytes
+    bool cigars = false;
+    int64_t* d_cig_off = nullptr; char* d_cig_pool = nullptr; int64_t cig_bytes = 0; u32* d_al_steps = nullptr;
 };
 // The per-pair arrays of an all-occurrences run -- found (0) | smallest score (-1) | stored - 1 (-1: the scan then counts 0) --,
 // the offsets and `nadv` step counters.  -> the stored counts, for the forward pass to fill
@@ -1456,6 +1460,79 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     return O;
 }
 
+// The alignment pass of the all-occurrences panel runs (QUICKED_PANEL_CIGARS; qe_panel_align.h), behind
+// k_panel_hits_finish: k_panel_align_sizes and k_scan_offsets lay the strings' slots out from the scores (4 (2 score + 1) + 1
+// bytes hold any string with `score` edits), the host reads their total, and k_panel_occ_align<Eq> runs one lane per stored
+// occurrence over the run's forward planes.  A wave's history is cols x blocks x 64 cells of 16 bytes -- cols the longest
+// stretch a member can have (m + its effective bound), blocks the panel's tallest member --, and the launch is cut into
+// sub-batches of as many waves as QE_PANEL_ALIGN_WS_KB holds (unset: 1 GiB; never fewer than one), which reuse one history in
+// stream order.  Every launch is timed as kind 1.
+static void panel_align_geometry(const SearchRun& sr, int& cols, int& blocks) {
+    const PanelRun& pr = *sr.panel;
+    cols = 1; blocks = 1;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) {
+        const int m = pr.len[p];
+        cols = std::max(cols, m + search_effective(sr.max_dist ? sr.max_dist[p] : sr.max_dist_all, m));
+        blocks = std::max(blocks, search_blocks(m));
+    }
+}
+static size_t panel_align_wave_bytes(const SearchRun& sr) {
+    int cols, blocks;
+    panel_align_geometry(sr, cols, blocks);
+    return (size_t)cols * (size_t)blocks * 64 * sizeof(AlignCell);
+}
+static size_t panel_align_waves(const SearchRun& sr, size_t waves) {
+    const size_t budget = (size_t)std::max<long long>(1, sw_ll(Sw::PanelAlignWsKb)) << 10;
+    return std::max<size_t>(1, std::min(waves, budget / panel_align_wave_bytes(sr)));
+}
+// what is fixed of it before the total is known: the history at the most occurrences the run can store
+static size_t panel_align_fixed_bytes(const quicked_batch& B, const SearchRun& sr) {
+    if (!sr.cigars) return 0;
+    size_t texts = 0;
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    return panel_align_waves(sr, (texts * (size_t)sr.max_hits + 63) / 64) * panel_align_wave_bytes(sr) + 1024;
+}
+static void run_panel_align(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const u64* pl_m, const u64* pl_t, HitsOut& O) {
+    const size_t nh = (size_t)O.total;
+    O.cigars = true;
+    int32_t* d_len = C.scratch_p->take<int32_t>(nh);
+    int64_t* d_str_off = C.scratch_p->take<int64_t>(nh + 1);
+    hipLaunchKernelGGL(k_panel_align_sizes, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)O.d_hits, d_len);
+    hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, (const int32_t*)d_len, (const int32_t*)d_len, d_str_off, d_str_off + nh, (int)nh);
+    HIP_CHECK(hipGetLastError());
+    {
+        std::vector<int64_t> tot;
+        FetchBatch fb(C);
+        fb.add(tot, (const int64_t*)(d_str_off + nh), 1);
+        fb.sync();
+        O.cig_bytes = tot[0];
+    }
+    O.d_cig_pool = C.scratch_p->take<char>(((size_t)O.cig_bytes + 127) & ~(size_t)63);
+    O.d_cig_off = C.scratch_p->take<int64_t>(nh);
+    O.d_al_steps = C.scratch_p->take<u32>(2 * nh);
+    int cols, blocks;
+    panel_align_geometry(sr, cols, blocks);
+    const size_t waves = (nh + 63) / 64, per = panel_align_waves(sr, waves), wave_cells = (size_t)cols * (size_t)blocks * 64;
+    PanelAlignArgs a{};
+    a.pl_m = pl_m; a.m_off = D.d_pl_off; a.m_len = D.d_len; a.n_members = sr.panel->n_patterns;
+    a.pl_t = pl_t; a.t_off = B.d_plt_off; a.t_len = B.d_t_len;
+    a.occ_off = O.d_off; a.npairs = (int32_t)B.n;
+    a.hits = O.d_hits; a.total = (int64_t)nh;
+    a.hist = C.scratch_p->take<AlignCell>(per * wave_cells); a.hist_cols = cols; a.hist_blocks = blocks;
+    a.style = B.cigar_style;
+    a.str_off = d_str_off; a.pool = O.d_cig_pool;
+    a.o_off = O.d_cig_off; a.o_steps = O.d_al_steps; a.o_ops = O.d_al_steps + nh;
+    for (size_t w0 = 0; w0 < waves; w0 += per) {
+        a.first = (int64_t)(64 * w0); a.count = (int64_t)std::min(nh - 64 * w0, 64 * per);
+        TimedLaunches tl(C, 1);
+        const dim3 grid((unsigned)((a.count + 255) / 256));
+        if (sr.eq) hipLaunchKernelGGL(k_panel_occ_align<SearchEqIupac>, grid, dim3(256), 0, C.stream, a);
+        else hipLaunchKernelGGL(k_panel_occ_align<SearchEq3>, grid, dim3(256), 0, C.stream, a);
+        HIP_CHECK(hipGetLastError());
+        tl.end();
+    }
+}
+
 // Every occurrence of every member (quicked_batch_run_panel_all): the panel upload and pack of a panel run,
 // k_panel_hits over text groups x slices -- per (slice, slot) its counts and up to max_hits raw records --, k_panel_hits_count
 // (found / smallest score / stored per pair), the offset scan over the stored counts in the order of the pairs and -- the one
@@ -1481,7 +1558,7 @@ static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, c
     const size_t n = (size_t)B.n, nslices = (size_t)panel_hits_slices(C, nslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
     b += nslots * 8 + n * 12 + (n + 1) * 8;
-    return b;
+    return b + panel_align_fixed_bytes(B, sr);
 }
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
@@ -1536,15 +1613,17 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     }
     hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
     HIP_CHECK(hipGetLastError());
-    if (!infix) return O;
-    // ---- the start pass: one lane per stored occurrence over its window, reversed
-    if (!eq) ensure_reversed(B, C);
-    PairView PV = pair_view(B, true);
-    PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
-    PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
-    launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
-    hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
-    HIP_CHECK(hipGetLastError());
+    if (infix) {
+        // ---- the start pass: one lane per stored occurrence over its window, reversed
+        if (!eq) ensure_reversed(B, C);
+        PairView PV = pair_view(B, true);
+        PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
+        PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
+        launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
+        hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
     return O;
 }
 
@@ -1605,7 +1684,7 @@ static size_t panel_scan_fixed_bytes(const quicked_batch& B, const Context& C, c
     const size_t nslices = (size_t)panel_scan_slices(C, wslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * wslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit)) + 5 * nslices * ntext * sizeof(int32_t);
     b += wslots * 16 + n * 8 + ntext * 8 + n * 12 + (n + 1) * 8 + 16 * 512;
-    return b;
+    return b + panel_align_fixed_bytes(B, sr);
 }
 static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
@@ -1685,6 +1764,7 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
     hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
     HIP_CHECK(hipGetLastError());
+    if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
     return O;
 }
 
@@ -2021,6 +2101,7 @@ static void reset_host_results(quicked_batch& B) {
     if (B.search_kind == Kind::PanelAll) { B.wr->panel_found.assign((size_t)B.n, 0); B.wr->panel_occ_off.assign((size_t)B.n + 1, 0); }
     else { B.wr->panel_found.clear(); B.wr->panel_occ_off.clear(); }
     B.wr->panel_occ.clear();
+    B.wr->panel_cigars = false; B.wr->panel_cig_off.clear(); B.wr->panel_cig_pool.clear();
     B.wr->deferred_pairs = 0;
 }
 
