@@ -362,6 +362,39 @@ quicked_status_t quicked_batch_run_panel_scan(quicked_batch_t* batch, int mode,
 enum { QUICKED_PANEL_CIGARS = 512 };           /* OR-ed into mode of quicked_batch_run_panel_all / _scan, beside the two IUPAC flags (128 and 256 stay unknown bits) */
 int64_t          quicked_batch_panel_hit_cigar_bytes(quicked_batch_t* batch);   /* -1 unless the last run was a flagged run */
 quicked_status_t quicked_batch_panel_hit_cigars(quicked_batch_t* batch, char* pool, int64_t* off /* hit_total entries */);
+/* A member cut off by the text's end (3' tails).  QUICKED_PANEL_TAILS is OR-ed into `mode` of quicked_batch_run_panel_all,
+ * beside the two IUPAC flags and QUICKED_PANEL_CIGARS.  Without the bit nothing about the run changes.  With it every result the
+ * unflagged run leaves is left unchanged -- found, stored, the records and their order, quicked_batch_scores, the statuses,
+ * counter [0], the strings of a QUICKED_PANEL_CIGARS run, the refusals of the other getters -- and every text gets one record
+ * besides: the panel member whose beginning the text ends in.  A read that runs into its 3' adapter ends with the adapter's
+ * first r < m bases; row m of the matrix never comes within the bound there, so the occurrences above do not see it.
+ *
+ * The definition.  Text i has n >= 1 bases, member p has m bases and the effective bound k = min(bound, m); D is the INFIX
+ * matrix (D[0][j] = 0) under the run's equality, IUPAC flags included.  Row r is a tail of p in i when
+ *     min_overlap <= r <= m - 1   and   D[r][n] <= floor(r * k / m):
+ * the member's first r bases fit a stretch that ends at the text's end, at the member's own error rate.  The member's tail is
+ * the tail row with the largest matched length r - D[r][n]; on a tie the smaller D[r][n] (r is then determined).  The text's
+ * tail is the best member's by the same two keys, then the smaller member index.  The record is {pattern, overlap = r,
+ * text_start, score = D[r][n]}: text_start is the smallest s with ed(member[0:r], text[s:n]) == score -- the longest stretch, the
+ * best search's rule --, the stretch's end is always n.  Every field is -1 where no member has a tail; an empty text has none.
+ * Tails say nothing about full occurrences and full occurrences nothing about tails: a text may have both, and the caller
+ * decides.  Row m is not a tail; it is the occurrence scan's.
+ *
+ * quicked_batch_configure_panel_tails sets min_overlap for the runs to come (default 3); QUICKED_ERROR outside
+ * 1 .. QUICKED_PANEL_MAX_LEN.  quicked_batch_panel_tails copies the n records; QUICKED_ERROR after any run without the bit and
+ * after a reload.  A run returns QUICKED_ERROR with text_start = -1 where the start pass did not find the tail's score: the
+ * two passes disagree, which is a defect of the library and is not hidden.
+ *
+ * QUICKED_ERROR, nothing launched: the bit with the base mode QUICKED_SEARCH_PREFIX (D[0][n] = n there: a tail means nothing);
+ * the bit on quicked_batch_run_panel, _run_panel_scan, _run_search and _run_search_all (an unknown bit there).  Every other
+ * refusal of quicked_batch_run_panel_all stands (sync == 0, members over 256 bases, check != 0).
+ * Counters: [2] is the row steps of the walk down the last column; [0], [1] and [3] keep their meaning.
+ * Not built: tails on quicked_batch_run_panel_scan; 5' tails (a member's suffix at the text's start); one tail per member
+ * instead of one per text; tail CIGARs. */
+enum { QUICKED_PANEL_TAILS = 2048 };           /* OR-ed into mode of quicked_batch_run_panel_all (1024 stays an unknown bit) */
+typedef struct { int32_t pattern, overlap, text_start, score; } quicked_panel_tail_t;   /* 16 bytes */
+quicked_status_t quicked_batch_configure_panel_tails(quicked_batch_t* batch, int32_t min_overlap);
+quicked_status_t quicked_batch_panel_tails(quicked_batch_t* batch, quicked_panel_tail_t* out /* n */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

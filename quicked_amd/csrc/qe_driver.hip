@@ -52,6 +52,9 @@
 #if __has_include("qe_kernels_stub_align.h")
 #include "qe_kernels_stub_align.h"
 #endif
+#if __has_include("qe_kernels_stub_tails.h")
+#include "qe_kernels_stub_tails.h"
+#endif
 #endif
 
 
@@ -684,10 +687,12 @@ static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 // named, the smallest score as every searched pair's score, the block steps of both passes into counter 0
 // A run with QUICKED_PANEL_CIGARS brings the strings' offsets and pool and the alignment pass's counts in the same read-back:
 // block steps into counter 1, operations into counter 3.  -> false: a lane's alignment did not end at (0, 0) with its score
+// A run with QUICKED_PANEL_TAILS brings every text's tail and the walk's row steps (counter 2) too.  -> false as well where a
+// tail's start pass did not find its score
 template <class Occ>
 static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
     const size_t n = (size_t)B.n, nh = (size_t)HO.total;
-    std::vector<int32_t> best; std::vector<u32> adv, adv2, al;
+    std::vector<int32_t> best; std::vector<u32> adv, adv2, al, rows;
     occ.resize(nh);
     {
         FetchBatch fb(C);
@@ -696,6 +701,11 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
             fb.add(B.wr->panel_cig_off, (const int64_t*)HO.d_cig_off, nh);
             fb.add_bytes(B.wr->panel_cig_pool.data(), HO.d_cig_pool, (size_t)HO.cig_bytes);
             fb.add(al, (const u32*)HO.d_al_steps, 2 * nh);
+        }
+        if (HO.d_tails) {
+            B.wr->panel_tails.resize(n);
+            fb.add_bytes(B.wr->panel_tails.data(), HO.d_tails, n * sizeof(quicked_panel_tail_t));
+            fb.add(rows, (const u32*)HO.d_tail_rows, HO.task_pair.size());
         }
         fb.add(found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
         fb.add(off, (const int64_t*)HO.d_off, n + 1);
@@ -709,6 +719,8 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
     bool ok = true;
     for (size_t j = 0; j < al.size(); ++j) B.counters[j < nh ? 1 : 3] += (int64_t)al[j];
     for (const int64_t o : B.wr->panel_cig_off) ok = ok && o >= 0;
+    if (HO.d_tails) B.counters[2] = (int64_t)sum_u32(rows);
+    for (const quicked_panel_tail_t& t : B.wr->panel_tails) ok = ok && (t.pattern < 0 || t.text_start >= 0);
     return ok;
 }
 

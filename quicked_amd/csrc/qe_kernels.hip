@@ -1720,6 +1720,56 @@ __global__ __launch_bounds__(256) void k_panel_hits_finish(int64_t total, const 
     if (j < total) panel_hits_finish_one(j, o_start, hits);
 }
 
+// A member cut off by the text's end (qe_panel.h; QUICKED_PANEL_TAILS): k_panel_hits -- its grid, slots,
+// slices, scan and stores, through the argument block it takes -- and, after every member's walk of the text, the walk down
+// the column the lane's registers end in (panel_tail_walk).  The member index still comes from blockIdx.y and a loop counter
+// only, so the member's length, bound, allowance and the walk's loop bounds are wave-uniform; the live-block count and the
+// words are the lane's.  Besides k_panel_hits' stores one tail keeper per (slice, slot).  A kernel of its own: a run without
+// the bit launches k_panel_hits as it is.
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_tails(PanelTailsArgs T) {
+    const PanelHitsArgs& A = T.H;
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelHitScan H;
+    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    PanelTailKeeper keep;
+    keep.init();
+    u32 steps = 0, rows = 0;
+    panel_text_tails<Eq>(P, p0, p1, tp, n, A.mode, T.min_overlap, H, keep, steps, rows);      // (a lane without a text has n = 0: no tail)
+    if (pair >= 0) { panel_hits_store_part(A, nslices, slice, slot, H, steps); panel_tails_store_part(T, nslices, slice, slot, keep, rows); }
+}
+template __global__ void k_panel_tails<SearchEq3>(PanelTailsArgs);
+template __global__ void k_panel_tails<SearchEqIupac>(PanelTailsArgs);
+
+// one thread per text slot: the slices' tail keepers merged by the key and the slot's task of the start pass
+// (PanelTailsMergeArgs); the task's pattern, the reversed prefix, laid out word-aligned (PanelTailPlanesArgs); and, behind the
+// start pass, the window's base added
+__global__ __launch_bounds__(256) void k_panel_tails_merge(PanelTailsMergeArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_tails_merge_slot(A, t);
+}
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_tail_planes(PanelTailPlanesArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_tail_planes_slot<Eq>(A, t);
+}
+template __global__ void k_panel_tail_planes<SearchEq3>(PanelTailPlanesArgs);
+template __global__ void k_panel_tail_planes<SearchEqIupac>(PanelTailPlanesArgs);
+__global__ __launch_bounds__(256) void k_panel_tails_finish(int nslots, const int32_t* __restrict__ o_pair, const int32_t* __restrict__ o_start, int32_t* __restrict__ tails) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < nslots) panel_tails_finish_slot(t, o_pair, o_start, tails);
+}
+
 // Every occurrence of every member, long texts split across lanes (qe_panel.h; quicked_batch_run_panel_scan; DESIGN.md
 // 4.14.2): k_panel_hits with a WINDOW SLOT {pair, c0, c1} per lane in the place of a text slot -- the grid is window groups x
 // panel slices, the launch shape k_panel_hits'.  The member index still comes from blockIdx.y and a loop counter only: length,

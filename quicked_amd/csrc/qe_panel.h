@@ -18,7 +18,8 @@
 // the SearchLane and the keeper.
 //
 // The second half of the file is the all-occurrences run (quicked_batch_run_panel_all): the same lanes and
-// slices with qe_search.h's valley scan in the keeper's place.
+// slices with qe_search.h's valley scan in the keeper's place; behind it the 3' tails (QUICKED_PANEL_TAILS):
+// the walk down the column that run ends in; and the windowed run (quicked_batch_run_panel_scan).
 #pragma once
 #include <stdint.h>
 
@@ -306,6 +307,190 @@ QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) {
 // k_panel_hits_finish's occurrence j: the start pass's o_start is relative to the occurrence's window
 QE_S_HD void panel_hits_finish_one(int64_t j, const int32_t* o_start, int32_t* hits) {
     hits[4 * j + 1] = o_start[j] < 0 ? -1 : hits[4 * j + 1] + o_start[j];
+}
+
+// ---- a member cut off by the text's end: 3' tails (QUICKED_PANEL_TAILS on quicked_batch_run_panel_all)
+// The definition.  D is the INFIX matrix of member p (m bases, effective bound k = min(bound, m)) against the text (n >= 1
+// columns).  Row r is a tail of p when min_overlap <= r <= m - 1 and D[r][n] <= floor(r k / m): the member's first r bases end
+// where the text ends, at the member's own error rate.  The key of a tail is (matched length r - D[r][n] descending, D[r][n]
+// ascending, member index ascending); within one member the first two fix r.  A text's tail is the smallest key over its members.
+//
+// Where D[.][n] comes from.  After search_run_hits the lane's store holds column n: Pv / Mv of block b are the vertical deltas
+// of rows 64 b + 1 .. 64 b + 64 and S(b - 1) is the value of row 64 b (row 0: 0), so a running sum down the live blocks gives
+// D[i][n].  Every allowance is at most k, the live-block rule keeps every cell <= k exact and every other cell above k, and a
+// block that is not live holds no cell <= k (qe_search.h, "Why that loses no answer"): the walk over the live blocks decides
+// every row as the full matrix does.  What a tail is is decided here and nowhere else.
+struct PanelTailKeeper {
+    int32_t p, r, d;         // the smallest key: member p, overlap r, score d; p < 0: none
+    QE_S_HD void init() { p = -1; r = -1; d = -1; }
+    static QE_S_HD bool before(int32_t ra, int32_t da, int32_t pa, int32_t rb, int32_t db, int32_t pb) {
+        const int32_t ma = ra - da, mb = rb - db;
+        return ma > mb || (ma == mb && (da < db || (da == db && pa < pb)));
+    }
+    // row rr of member pp is a tail at distance dd (pp < 0: nothing); selects, as PanelKeeper::take
+    QE_S_HD void take(int32_t pp, int32_t rr, int32_t dd) {
+        const bool t = pp >= 0 && (p < 0 || before(rr, dd, pp, r, d, p));
+        p = t ? pp : p; r = t ? rr : r; d = t ? dd : d;
+    }
+    QE_S_HD void merge(const PanelTailKeeper& o) { take(o.p, o.r, o.d); }
+};
+
+// The walk: column n of the lane's store after the member's search_run_hits.  m, k, min_overlap and every loop bound are the
+// member's (wave-uniform on the device); L.live and the words are the lane's.  The allowance floor(i k / m) runs along with
+// the row: k <= m, so it rises by at most one per row.  rows: the row steps, added to
+template <int NB, class Store>
+QE_S_HD void panel_tail_walk(Store& st, const SearchLane& L, int min_overlap, int32_t p, PanelTailKeeper& keep, uint32_t& rows) {
+    if (L.n < 1) return;                                      // an empty text has no tail
+    const int m = L.m, k = search_effective(L.k, m);          // (an all-occurrences lane keeps its bound: L.k is the member's)
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) {
+        const int left = m - 1 - 64 * b, nrows = left < 64 ? left : 64;      // rows 64 b + 1 .. m - 1 of this block
+        if (nrows <= 0 || b >= L.live) continue;
+        int32_t allow = b ? (64 * b * k) / m : 0, acc = b ? (64 * b * k) % m : 0;
+        int32_t v = b ? st.S(b - 1) : 0;
+        const uint64_t P = st.P(b), M = st.M(b);
+        for (int r = 0; r < nrows; ++r) {
+            v += (int32_t)((P >> r) & 1) - (int32_t)((M >> r) & 1);
+            acc += k;
+            if (acc >= m) { acc -= m; ++allow; }
+            const int i = 64 * b + r + 1;
+            keep.take((i >= min_overlap && v <= allow) ? p : -1, i, v);
+        }
+        rows += (uint32_t)nrows;
+    }
+}
+
+// one member of NB blocks at the most against one text: panel_member_hits, and the walk over the column it ends in
+template <int NB, class Eq>
+QE_S_HD void panel_member_tails(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int mode, int min_overlap, int32_t p,
+                                PanelHitScan& H, PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
+    SearchLane L;
+    search_lane_init(L, m, n, mode, bound, 0);
+    SearchRegStore<NB, Eq> R;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.load(pp, m);
+    H.begin(L);
+    search_run_hits<NB>(R, L, H, tp, 0);
+    steps += L.steps;
+    panel_tail_walk<NB>(R, L, min_overlap, p, keep, rows);
+}
+// One text against the members [p0, p1): panel_text_hits, with the text's best tail among them in `keep`
+template <class Eq>
+QE_S_HD void panel_text_tails(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, int min_overlap,
+                              PanelHitScan& H, PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        H.sink.member = p;
+        if (nb <= 1) panel_member_tails<1, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
+        else if (nb == 2) panel_member_tails<2, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_tails<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
+    }
+}
+
+// k_panel_tails<Eq>: k_panel_hits with the walk.  H is k_panel_hits' argument block and everything it names is written as that
+// kernel writes it; besides, per (slice s, slot t), field f of {pattern, overlap, score, row steps} of the slice's best tail at
+// tpart[(f nslices + s) nslots + t].
+struct PanelTailsArgs {
+    PanelHitsArgs H;
+    int32_t min_overlap;
+    int32_t* tpart;
+};
+// One thread per text slot (k_panel_tails_merge): the slices' keepers merged by the key into tails[pair] =
+// quicked_panel_tail_t as {pattern, overlap, text_start, score} (tails: -1 everywhere before) and o_rows[t] = the slot's row
+// steps.  text_start: the base of the start pass's window, and the slot's task of that pass -- search_hit_task for the
+// overlap's rows ending at column n -- goes to o_pair / o_m / o_n / o_score / o_end [t] (o_pair -1: no tail); the task's pattern
+// is the reversed prefix, which k_panel_tail_planes lays out at three-plane word t plane_stride of a scratch pool
+// (o_plp_off[pair]).  k_panel_tails_finish then adds the pass's o_start (or leaves -1).
+struct PanelTailsMergeArgs {
+    int32_t nslots, nslices;
+    const int32_t* text;  const int32_t* tpart;  const int32_t* t_len;
+    int64_t plane_stride;
+    int32_t* tails;  uint32_t* o_rows;
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;  int64_t* o_plp_off;
+};
+// One thread per text slot (k_panel_tail_planes<Eq>): the first `overlap` bases of the tail's member, reversed, from the
+// member's forward planes (Eq::W words per row, at Eq::offset(m_off[pattern]) of pl_m) to Eq::offset(o_plp_off[pair]) of pool,
+// two rows of zeros behind
+struct PanelTailPlanesArgs {
+    int32_t nslots;
+    const int32_t* o_pair;  const int32_t* tails;
+    const uint64_t* pl_m;  const int64_t* m_off;  const int64_t* o_plp_off;
+    uint64_t* pool;
+};
+
+QE_S_HD void panel_tails_store_part(const PanelTailsArgs& A, int nslices, int slice, int slot, const PanelTailKeeper& keep, uint32_t rows) {
+    const int64_t stride = (int64_t)nslices * A.H.nslots;
+    int32_t* q = A.tpart + (int64_t)slice * A.H.nslots + slot;
+    q[0] = keep.p; q[stride] = keep.r; q[2 * stride] = keep.d; q[3 * stride] = (int32_t)rows;
+}
+QE_S_HD void panel_tails_merge_slot(const PanelTailsMergeArgs& A, int t) {
+    const int pair = A.text[t];
+    A.o_pair[t] = -1;
+    if (pair < 0) return;
+    const int64_t stride = (int64_t)A.nslices * A.nslots;
+    PanelTailKeeper keep;
+    keep.init();
+    uint32_t rows = 0;
+    for (int s = 0; s < A.nslices; ++s) {
+        const int32_t* q = A.tpart + (int64_t)s * A.nslots + t;
+        PanelTailKeeper o;
+        o.p = q[0]; o.r = q[stride]; o.d = q[2 * stride];
+        keep.merge(o);
+        rows += (uint32_t)q[3 * stride];
+    }
+    A.o_rows[t] = rows;
+    if (keep.p < 0) return;
+    const int n = A.t_len[pair];
+    int32_t task_n, in_end, base;
+    search_hit_task(keep.r, n, n, keep.d, task_n, in_end, base);
+    A.o_pair[t] = pair; A.o_m[t] = keep.r; A.o_n[t] = task_n; A.o_score[t] = keep.d; A.o_end[t] = in_end;
+    A.o_plp_off[pair] = (int64_t)t * A.plane_stride;
+    int32_t* o = A.tails + 4 * (int64_t)pair;
+    o[0] = keep.p; o[1] = keep.r; o[2] = base; o[3] = keep.d;
+}
+QE_S_HD uint64_t panel_reverse_bits(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __brevll(x);
+#else
+    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
+    return __builtin_bswap64(x);
+#endif
+}
+// the reversed prefix of `len` bases: reversed positions [64 row, 64 row + 64) are the forward positions e - 1 down to e - 64,
+// e = len - 64 row (k_reverse_planes' formula, for any plane count); rows past the prefix are zeros
+template <class Eq>
+QE_S_HD void panel_tail_planes_slot(const PanelTailPlanesArgs& A, int t) {
+    const int pair = A.o_pair[t];
+    if (pair < 0) return;
+    const int len = A.tails[4 * (int64_t)pair + 1], nw = (len + 63) >> 6;
+    const uint64_t* src = A.pl_m + Eq::offset(A.m_off[A.tails[4 * (int64_t)pair]]);
+    uint64_t* dst = A.pool + Eq::offset(A.o_plp_off[pair]);
+    for (int row = 0; row < nw + 2; ++row) {
+        uint64_t x[Eq::W];
+        for (int k = 0; k < Eq::W; ++k) x[k] = 0;
+        if (row < nw) {
+            const int s = len - 64 * row - 64;
+            if (s >= 0) search_text_words<Eq::W>(src, s, 64, x);
+            else for (int k = 0; k < Eq::W; ++k) x[k] = src[k] << (-s);
+            for (int k = 0; k < Eq::W; ++k) x[k] = panel_reverse_bits(x[k]);
+        }
+        for (int k = 0; k < Eq::W; ++k) dst[Eq::W * (int64_t)row + k] = x[k];
+    }
+}
+// k_panel_tails_finish's slot t: the start pass's o_start is relative to the tail's window
+QE_S_HD void panel_tails_finish_slot(int t, const int32_t* o_pair, const int32_t* o_start, int32_t* tails) {
+    const int pair = o_pair[t];
+    if (pair < 0) return;
+    int32_t* o = tails + 4 * (int64_t)pair;
+    o[2] = o_start[t] < 0 ? -1 : o[2] + o_start[t];
 }
 
 // ---- every occurrence of every member, long texts split across lanes (quicked_batch_run_panel_scan)

@@ -1127,6 +1127,9 @@ struct HitsOut {                                   // of both all-occurrences ru
     // sweeps disagree) and its block steps | operations; the pool's bytes
     bool cigars = false;
     int64_t* d_cig_off = nullptr; char* d_cig_pool = nullptr; int64_t cig_bytes = 0; u32* d_al_steps = nullptr;
+    // QUICKED_PANEL_TAILS (run_panel_tails): every pair's quicked_panel_tail_t (-1 in every field: none) and the row steps of
+    // the walk per slot (task_pair.size() of them)
+    int32_t* d_tails = nullptr; u32* d_tail_rows = nullptr;
 };
 // The per-pair arrays of an all-occurrences run -- found (0) | smallest score (-1) | stored - 1 (-1: the scan then counts 0) --,
 // the offsets and `nadv` step counters.  -> the stored counts, for the forward pass to fill
@@ -1533,6 +1536,60 @@ static void run_panel_align(quicked_batch& B, Context& C, const SearchRun& sr, c
     }
 }
 
+// The tails of an all-occurrences panel run (QUICKED_PANEL_TAILS; qe_panel.h), behind k_panel_tails, which
+// left one keeper per (slice, slot): k_panel_tails_merge merges them per text and writes the start-pass task of every text that
+// has a tail; k_panel_tail_planes<Eq> lays the task's pattern -- the member's first `overlap` bases, reversed -- out in a
+// scratch pool of one stretch per slot (the panel's tallest member and two rows of zeros); the start pass is the unchanged
+// k_search<4, Eq> in its start-pass form over those planes and the texts' reversed planes, one lane per slot, timed as kind 0;
+// k_panel_tails_finish adds its o_start.  Nothing here waits for the host or depends on the occurrences' total: a batch
+// without a single full occurrence gets its tails all the same.  The pass's block steps are not the unflagged run's and stay
+// out of counter 0.
+static int panel_tallest_rows(const PanelRun& pr) {
+    int nb = 1;
+    for (int32_t p = 0; p < pr.n_patterns; ++p) nb = std::max(nb, search_blocks(pr.len[p]));
+    return nb + 2;
+}
+static size_t panel_tails_fixed_bytes(const quicked_batch& B, const SearchRun& sr, size_t nslots, size_t nslices) {
+    if (!sr.tails) return 0;
+    const size_t n = (size_t)B.n, plane_words = (size_t)iupac_offset(3 * (int64_t)panel_tallest_rows(*sr.panel)) * nslots + 8;
+    return 4 * nslices * nslots * sizeof(int32_t) + 4 * n * sizeof(int32_t) + 8 * nslots * sizeof(int32_t) + n * sizeof(int64_t) + plane_words * sizeof(u64) + 8 * 512;
+}
+static void run_panel_tails(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const PanelTailsArgs& ta, int nslices, const u64* pl_t_rev, HitsOut& O) {
+    const size_t n = (size_t)B.n, nslots = D.nslots;
+    const int eq = sr.eq;
+    O.d_tails = C.scratch_p->take<int32_t>(4 * n);
+    HIP_CHECK(hipMemsetAsync(O.d_tails, 0xFF, 4 * n * sizeof(int32_t), C.stream));
+    O.d_tail_rows = C.scratch_p->take<u32>(nslots);
+    HIP_CHECK(hipMemsetAsync(O.d_tail_rows, 0, nslots * sizeof(u32), C.stream));
+    PanelTailsMergeArgs g{};
+    g.nslots = (int32_t)nslots; g.nslices = nslices; g.text = D.d_text; g.tpart = ta.tpart; g.t_len = B.d_t_len;
+    g.plane_stride = 3 * (int64_t)panel_tallest_rows(*sr.panel);
+    g.tails = O.d_tails; g.o_rows = O.d_tail_rows;
+    int32_t* q = C.scratch_p->take<int32_t>(7 * nslots);
+    g.o_pair = q; g.o_m = q + nslots; g.o_n = q + 2 * nslots; g.o_score = q + 3 * nslots; g.o_end = q + 4 * nslots;
+    int32_t* o_start = q + 5 * nslots;
+    u32* o_adv = (u32*)(q + 6 * nslots);
+    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(o_adv, 0, nslots * sizeof(u32), C.stream));
+    g.o_plp_off = C.scratch_p->take<int64_t>(n);
+    HIP_CHECK(hipMemsetAsync(g.o_plp_off, 0, n * sizeof(int64_t), C.stream));
+    const dim3 grid((unsigned)((nslots + 255) / 256));
+    hipLaunchKernelGGL(k_panel_tails_merge, grid, dim3(256), 0, C.stream, g);
+    PanelTailPlanesArgs w{};
+    w.nslots = (int32_t)nslots; w.o_pair = g.o_pair; w.tails = O.d_tails;
+    w.pl_m = ta.H.pl_m; w.m_off = D.d_pl_off; w.o_plp_off = g.o_plp_off;
+    w.pool = C.scratch_p->take<u64>((size_t)(eq ? iupac_offset(g.plane_stride) : g.plane_stride) * nslots + 8);
+    if (eq) hipLaunchKernelGGL(k_panel_tail_planes<SearchEqIupac>, grid, dim3(256), 0, C.stream, w);
+    else hipLaunchKernelGGL(k_panel_tail_planes<SearchEq3>, grid, dim3(256), 0, C.stream, w);
+    HIP_CHECK(hipGetLastError());
+    PairView PV = pair_view(B, true);
+    PV.pl_p = w.pool; PV.pl_p_off = g.o_plp_off;
+    PV.pl_t = pl_t_rev; PV.pl_t_off = B.d_plt_off;
+    launch_start_pass(C, eq, PV, nslots, g.o_pair, g.o_m, g.o_n, g.o_score, g.o_end, o_start, o_adv);
+    hipLaunchKernelGGL(k_panel_tails_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)g.o_pair, (const int32_t*)o_start, O.d_tails);
+    HIP_CHECK(hipGetLastError());
+}
+
 // Every occurrence of every member (quicked_batch_run_panel_all): the panel upload and pack of a panel run,
 // k_panel_hits over text groups x slices -- per (slice, slot) its counts and up to max_hits raw records --, k_panel_hits_count
 // (found / smallest score / stored per pair), the offset scan over the stored counts in the order of the pairs and -- the one
@@ -1558,7 +1615,7 @@ static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, c
     const size_t n = (size_t)B.n, nslices = (size_t)panel_hits_slices(C, nslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
     b += nslots * 8 + n * 12 + (n + 1) * 8;
-    return b + panel_align_fixed_bytes(B, sr);
+    return b + panel_align_fixed_bytes(B, sr) + panel_tails_fixed_bytes(B, sr, nslots, nslices);
 }
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
@@ -1579,20 +1636,33 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
     a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
     int32_t* const d_plen = hits_arrays(C, O, (size_t)B.n, nslots);
+    // (QUICKED_PANEL_TAILS: k_panel_tails is k_panel_hits with the walk down the last column, and one keeper per (slice, slot) more)
+    PanelTailsArgs ta{};
+    if (sr.tails) { ta.H = a; ta.min_overlap = B.tail_min_overlap; ta.tpart = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots); }
     TimedLaunches tl(C, 0);
     {
         // k_search_panel's launch shape: four text groups per workgroup and launch_groups' claim on the CU's LDS
         const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
-        if (eq) hipLaunchKernelGGL(k_panel_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+        if (sr.tails) {
+            if (eq) hipLaunchKernelGGL(k_panel_tails<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, ta);
+            else hipLaunchKernelGGL(k_panel_tails<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, ta);
+        } else if (eq) hipLaunchKernelGGL(k_panel_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
         else hipLaunchKernelGGL(k_panel_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
     }
     HIP_CHECK(hipGetLastError());
     tl.end();
+    // the texts' reversed planes, packed once for the start passes that want them
+    const u64* pl_t_rev = nullptr;
+    auto text_planes_reversed = [&]() {
+        if (!pl_t_rev) { if (!eq) ensure_reversed(B, C); pl_t_rev = panel_text_planes(B, C, eq, true); }
+        return pl_t_rev;
+    };
     // ---- counts per pair, offsets in the order of the pairs (a pair without a slot has -1 + 1 = 0 stored), the total
     PanelHitsCountArgs c{};
     c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits; c.text = D.d_text; c.part = a.part;
     c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.o_adv = O.d_adv;
     hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
+    if (sr.tails) run_panel_tails(B, C, sr, D, ta, nslices, text_planes_reversed(), O);      // (before the total: it needs none)
     hits_total(B, C, O, d_plen, B.d_t_len);
     if (O.total <= 0) return O;
     const size_t nh = (size_t)O.total;
@@ -1618,7 +1688,7 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         if (!eq) ensure_reversed(B, C);
         PairView PV = pair_view(B, true);
         PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
-        PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
+        PV.pl_t = text_planes_reversed(); PV.pl_t_off = e.o_plt_off;
         launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
         hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
         HIP_CHECK(hipGetLastError());
@@ -2102,6 +2172,7 @@ static void reset_host_results(quicked_batch& B) {
     else { B.wr->panel_found.clear(); B.wr->panel_occ_off.clear(); }
     B.wr->panel_occ.clear();
     B.wr->panel_cigars = false; B.wr->panel_cig_off.clear(); B.wr->panel_cig_pool.clear();
+    B.wr->panel_tails.clear();
     B.wr->deferred_pairs = 0;
 }
 
