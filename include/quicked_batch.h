@@ -282,7 +282,8 @@ quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* sco
  * quicked_batch_panel_results, quicked_batch_panel_matrix, quicked_batch_hits, quicked_batch_hit_counts,
  * quicked_batch_locations and the CIGAR and tag getters return what they return after any run that produced none of their
  * data.  Tags are ignored.  Counters [0] and kernel_times slot [0] count both passes, as for the other search runs.  A reload
- * clears the results.  Not built: queued runs, members over 256 bases, alignments for quicked_batch_run_panel and
+ * clears the results.  QUICKED_PANEL_TAILS and QUICKED_PANEL_HEADS (below) add the members a text's end or start cuts off.
+ * Not built: queued runs, members over 256 bases, alignments for quicked_batch_run_panel and
  * quicked_batch_run_search_all (this run has them: QUICKED_PANEL_CIGARS below), statistics and MD tags per occurrence. */
 typedef struct { int32_t pattern, text_start, text_end, score; } quicked_panel_occ_t;   /* 16 bytes */
 quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode,
@@ -389,12 +390,55 @@ quicked_status_t quicked_batch_panel_hit_cigars(quicked_batch_t* batch, char* po
  * the bit on quicked_batch_run_panel, _run_panel_scan, _run_search and _run_search_all (an unknown bit there).  Every other
  * refusal of quicked_batch_run_panel_all stands (sync == 0, members over 256 bases, check != 0).
  * Counters: [2] is the row steps of the walk down the last column; [0], [1] and [3] keep their meaning.
- * Not built: tails on quicked_batch_run_panel_scan; 5' tails (a member's suffix at the text's start); one tail per member
- * instead of one per text; tail CIGARs. */
+ * Counters [6] and [7] are a QUICKED_PANEL_HEADS run's (below), 0 otherwise.
+ * Not built: tails on quicked_batch_run_panel_scan; one tail per member instead of one per text; tail CIGARs.  (5' tails, a
+ * member's suffix at the text's start, are QUICKED_PANEL_HEADS below.) */
 enum { QUICKED_PANEL_TAILS = 2048 };           /* OR-ed into mode of quicked_batch_run_panel_all (1024 stays an unknown bit) */
 typedef struct { int32_t pattern, overlap, text_start, score; } quicked_panel_tail_t;   /* 16 bytes */
 quicked_status_t quicked_batch_configure_panel_tails(quicked_batch_t* batch, int32_t min_overlap);
 quicked_status_t quicked_batch_panel_tails(quicked_batch_t* batch, quicked_panel_tail_t* out /* n */);
+/* A member cut off by the text's start (5' heads).  QUICKED_PANEL_HEADS is OR-ed into `mode` of quicked_batch_run_panel_all,
+ * beside the two IUPAC flags, QUICKED_PANEL_CIGARS and QUICKED_PANEL_TAILS; all three bits may be set in one run.  Without the
+ * bit nothing about any run changes: no launch, no allocation, no copy.  With it every result the unflagged run leaves is left
+ * unchanged -- found, stored, the records and their order, quicked_batch_scores, the statuses, counters [0] .. [3], the strings
+ * of a QUICKED_PANEL_CIGARS run, the tails of a QUICKED_PANEL_TAILS run, the refusals of the other getters -- and every text
+ * gets one record besides: the panel member whose end the text begins with.  A read whose 5' adapter, barcode or primer was
+ * partly clipped, or that starts mid-adapter, begins with the member's last r < m bases; row m of the matrix never comes within
+ * the bound there, so the occurrences above do not see it.  With the tails one run answers all three questions of a trimming
+ * tool: is the whole member there, does the read run into it at its end, does the read start inside it.
+ *
+ * The definition.  Text i has n >= 1 bases, member p has m bases and the effective bound k = min(bound, m); rev() is plain
+ * reversal, no complement (every equality of the library is position-wise symmetric); D^R is the INFIX matrix (D^R[0][j] = 0)
+ * of rev(member) against rev(text) under the run's equality, IUPAC flags included.  Row r is a head of p in i when
+ *     min_overlap <= r <= m - 1   and   D^R[r][n] <= floor(r * k / m):
+ * the member's last r bases, member[m-r:m], fit a stretch text[0:e) at the member's own error rate.  The tie rules are the
+ * tails': the member's head is the head row with the largest matched length r - D^R[r][n]; on a tie the smaller score.  The
+ * text's head is the best member's by the same two keys, then the smaller member index.  The record is {pattern, overlap = r,
+ * text_end, score = D^R[r][n]}: text_end is the largest e with ed(member[m-r:m], text[0:e)) == score -- the longest stretch,
+ * the best search's rule mirrored --, the stretch's start is always 0.  Every field is -1 where no member has a head; an empty
+ * text has none.  In one sentence: the heads of (texts, panel) are the tails of (reversed texts, reversed members) with
+ * text_end = n - text_start.  Row m is not a head; it is the occurrence scan's.
+ *
+ * The base mode may be INFIX or PREFIX: the heads' matrix is its own and does not depend on the occurrences' (PREFIX together
+ * with QUICKED_PANEL_TAILS stays QUICKED_ERROR, because of the tails).  A head of member p depends only on the first m + k
+ * columns of the text, however long the text is, and that is all the run walks for it.
+ *
+ * quicked_batch_configure_panel_heads sets min_overlap for the runs to come (default 3), independently of the tails' setting;
+ * QUICKED_ERROR outside 1 .. QUICKED_PANEL_MAX_LEN.  quicked_batch_panel_heads copies the n records; QUICKED_ERROR after any run
+ * without the bit and after a reload.  A run returns QUICKED_ERROR with text_end = -1 where the end pass did not find the
+ * head's score: the two passes disagree, which is a defect of the library and is not hidden.
+ *
+ * QUICKED_ERROR, nothing launched: the bit on quicked_batch_run_panel, _run_panel_scan, _run_search and _run_search_all (an
+ * unknown bit there).  Every other refusal of quicked_batch_run_panel_all stands (sync == 0, members over 256 bases,
+ * check != 0).
+ * Counters, in a flagged run only (0 otherwise): [6] is the block steps of the head sweep, [7] the row steps of its walk;
+ * [0] .. [3] keep their meaning and their values.  kernel_times slot [0] includes the head kernels.
+ * Not built: heads or tails on quicked_batch_run_panel_scan; one head per member instead of one per text; head and tail CIGARs;
+ * reverse-complement members; queued (sync == 0) panel runs. */
+enum { QUICKED_PANEL_HEADS = 8192 };           /* OR-ed into mode of quicked_batch_run_panel_all (128, 256, 1024 and 4096 stay unknown bits) */
+typedef struct { int32_t pattern, overlap, text_end, score; } quicked_panel_head_t;   /* 16 bytes */
+quicked_status_t quicked_batch_configure_panel_heads(quicked_batch_t* batch, int32_t min_overlap);
+quicked_status_t quicked_batch_panel_heads(quicked_batch_t* batch, quicked_panel_head_t* out /* n */);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -65,6 +65,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_run_panel_all", "quicked_batch_run_panel_scan", "quicked_batch_panel_hit_counts", "quicked_batch_panel_hit_total", "quicked_batch_panel_hits",
            "quicked_batch_panel_hit_cigar_bytes", "quicked_batch_panel_hit_cigars",
            "quicked_batch_configure_panel_tails", "quicked_batch_panel_tails",
+           "quicked_batch_configure_panel_heads", "quicked_batch_panel_heads",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -74,11 +75,13 @@ SEARCH_IUPAC, SEARCH_IUPAC_PATTERN = 16, 32      # OR-ed into a search mode: IUP
 PANEL_MATRIX = 64                                # OR-ed into a panel run's mode: keep every {score, text_end}
 PANEL_CIGARS = 512                               # OR-ed into run_panel_all's / run_panel_scan's mode: every stored occurrence's alignment
 PANEL_TAILS = 2048                               # OR-ed into run_panel_all's mode: every text's 3' tail besides (panel_tails())
+PANEL_HEADS = 8192                               # OR-ed into run_panel_all's mode: every text's 5' head besides (panel_heads())
 PANEL_MAX_PATTERNS, PANEL_MAX_LEN = 4096, 256
 PANEL_HIT_DTYPE = np.dtype([("pattern", np.int32), ("score", np.int32), ("text_start", np.int32), ("text_end", np.int32),
                             ("second_pattern", np.int32), ("second_score", np.int32)])      # quicked_panel_hit_t
 PANEL_OCC_DTYPE = np.dtype([("pattern", np.int32), ("text_start", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_panel_occ_t
 PANEL_TAIL_DTYPE = np.dtype([("pattern", np.int32), ("overlap", np.int32), ("text_start", np.int32), ("score", np.int32)])      # quicked_panel_tail_t
+PANEL_HEAD_DTYPE = np.dtype([("pattern", np.int32), ("overlap", np.int32), ("text_end", np.int32), ("score", np.int32)])      # quicked_panel_head_t
 
 _LIB = None
 
@@ -158,6 +161,11 @@ def lib():
         L.quicked_batch_configure_panel_tails.restype = C.c_int
         L.quicked_batch_panel_tails.argtypes = [C.c_void_p, C.c_void_p]
         L.quicked_batch_panel_tails.restype = C.c_int
+    if hasattr(L, "quicked_batch_panel_heads"):           # (as above)
+        L.quicked_batch_configure_panel_heads.argtypes = [C.c_void_p, C.c_int32]
+        L.quicked_batch_configure_panel_heads.restype = C.c_int
+        L.quicked_batch_panel_heads.argtypes = [C.c_void_p, C.c_void_p]
+        L.quicked_batch_panel_heads.restype = C.c_int
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -522,7 +530,7 @@ class ResidentBatch:
         """quicked_batch_run_panel_all: every occurrence of every panel member in every text, at most max_hits (1 .. 4096) stored
         per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag); PANEL_CIGARS OR-ed into
         mode aligns every stored occurrence besides (panel_hit_cigars()); PANEL_TAILS (INFIX only) reports every text's 3' tail
-        besides (panel_tails()).  Sync runs only."""
+        besides (panel_tails()); PANEL_HEADS reports every text's 5' head besides (panel_heads()).  Sync runs only."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -596,6 +604,21 @@ class ResidentBatch:
         field -1 where no member has a tail.  QuickedException after any other run"""
         out = np.zeros(max(self.n, 1), dtype=PANEL_TAIL_DTYPE)
         st = self._lib.quicked_batch_panel_tails(self._h, out.ctypes.data)
+        if st < 0:
+            raise QuickedException(st)
+        return out[:self.n]
+
+    def configure_panel_heads(self, min_overlap=3):
+        """quicked_batch_configure_panel_heads: the shortest head (1 .. PANEL_MAX_LEN) of the PANEL_HEADS runs to come; the tails'
+        setting is its own.  -> the status"""
+        return self._lib.quicked_batch_configure_panel_heads(self._h, min_overlap)
+
+    def panel_heads(self):
+        """-> a structured array of PANEL_HEAD_DTYPE, one per text, of the last run_panel_all whose mode had PANEL_HEADS: the
+        panel member cut off by the text's start -- its last `overlap` bases fit text[:text_end] at distance `score` --, every
+        field -1 where no member has a head.  QuickedException after any other run"""
+        out = np.zeros(max(self.n, 1), dtype=PANEL_HEAD_DTYPE)
+        st = self._lib.quicked_batch_panel_heads(self._h, out.ctypes.data)
         if st < 0:
             raise QuickedException(st)
         return out[:self.n]

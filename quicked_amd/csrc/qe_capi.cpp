@@ -366,13 +366,14 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
                                                     int32_t max_dist_all, int32_t max_hits, int sync) {
     const bool cigars = (mode & QUICKED_PANEL_CIGARS) != 0;                         // every stored occurrence's alignment besides
     const bool tails = (mode & QUICKED_PANEL_TAILS) != 0;                           // every text's 3' tail besides
-    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_CIGARS | QUICKED_PANEL_TAILS));      // (QUICKED_PANEL_MATRIX is "any other bit" here)
+    const bool heads = (mode & QUICKED_PANEL_HEADS) != 0;                           // every text's 5' head besides
+    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_CIGARS | QUICKED_PANEL_TAILS | QUICKED_PANEL_HEADS));      // (QUICKED_PANEL_MATRIX is "any other bit" here)
     bool too_long = false;
     if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     if (tails && (mode & 15) == QUICKED_SEARCH_PREFIX) return QUICKED_ERROR;        // D[0][n] = n there: a tail means nothing
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
-    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, -1, cigars, tails}, too_long, sync};
+    struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, -1, cigars, tails, heads}, too_long, sync};
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         int64_t texts = 0;
@@ -444,6 +445,20 @@ QE_API quicked_status_t quicked_batch_panel_tails(quicked_batch_t* batch, quicke
     const HostResults* R = hit_results(batch, &HostResults::panel_found);
     if (!R || !out || R->panel_tails.size() != (size_t)batch->n) return QUICKED_ERROR;
     memcpy(out, R->panel_tails.data(), (size_t)batch->n * sizeof(quicked_panel_tail_t));
+    return QUICKED_OK;
+}
+
+// The heads of a run with QUICKED_PANEL_HEADS, and the shortest head of the runs to come
+static_assert(sizeof(quicked_panel_head_t) == 16, "quicked_panel_head_t is four int32 (k_panel_heads_merge writes it as such)");
+QE_API quicked_status_t quicked_batch_configure_panel_heads(quicked_batch_t* batch, int32_t min_overlap) {
+    if (!batch || min_overlap < 1 || min_overlap > QUICKED_PANEL_MAX_LEN) return QUICKED_ERROR;
+    batch->head_min_overlap = min_overlap;
+    return QUICKED_OK;
+}
+QE_API quicked_status_t quicked_batch_panel_heads(quicked_batch_t* batch, quicked_panel_head_t* out) {
+    const HostResults* R = hit_results(batch, &HostResults::panel_found);
+    if (!R || !out || R->panel_heads.size() != (size_t)batch->n) return QUICKED_ERROR;
+    memcpy(out, R->panel_heads.data(), (size_t)batch->n * sizeof(quicked_panel_head_t));
     return QUICKED_OK;
 }
 

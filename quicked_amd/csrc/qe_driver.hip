@@ -55,6 +55,9 @@
 #if __has_include("qe_kernels_stub_tails.h")
 #include "qe_kernels_stub_tails.h"
 #endif
+#if __has_include("qe_kernels_stub_heads.h")
+#include "qe_kernels_stub_heads.h"
+#endif
 #endif
 
 
@@ -689,10 +692,12 @@ static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 // block steps into counter 1, operations into counter 3.  -> false: a lane's alignment did not end at (0, 0) with its score
 // A run with QUICKED_PANEL_TAILS brings every text's tail and the walk's row steps (counter 2) too.  -> false as well where a
 // tail's start pass did not find its score
+// A run with QUICKED_PANEL_HEADS brings every text's head, the head sweep's block steps (counter 6) and its walk's row steps
+// (counter 7) too.  -> false as well where a head's end pass did not find its score
 template <class Occ>
 static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
     const size_t n = (size_t)B.n, nh = (size_t)HO.total;
-    std::vector<int32_t> best; std::vector<u32> adv, adv2, al, rows;
+    std::vector<int32_t> best; std::vector<u32> adv, adv2, al, rows, hsteps;
     occ.resize(nh);
     {
         FetchBatch fb(C);
@@ -706,6 +711,11 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
             B.wr->panel_tails.resize(n);
             fb.add_bytes(B.wr->panel_tails.data(), HO.d_tails, n * sizeof(quicked_panel_tail_t));
             fb.add(rows, (const u32*)HO.d_tail_rows, HO.task_pair.size());
+        }
+        if (HO.d_heads) {
+            B.wr->panel_heads.resize(n);
+            fb.add_bytes(B.wr->panel_heads.data(), HO.d_heads, n * sizeof(quicked_panel_head_t));
+            fb.add(hsteps, (const u32*)HO.d_head_steps, 2 * HO.task_pair.size());
         }
         fb.add(found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
         fb.add(off, (const int64_t*)HO.d_off, n + 1);
@@ -721,6 +731,11 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
     for (const int64_t o : B.wr->panel_cig_off) ok = ok && o >= 0;
     if (HO.d_tails) B.counters[2] = (int64_t)sum_u32(rows);
     for (const quicked_panel_tail_t& t : B.wr->panel_tails) ok = ok && (t.pattern < 0 || t.text_start >= 0);
+    if (HO.d_heads) {
+        B.counters[6] = B.counters[7] = 0;
+        for (size_t j = 0; j < hsteps.size(); ++j) B.counters[j < HO.task_pair.size() ? 6 : 7] += (int64_t)hsteps[j];
+    }
+    for (const quicked_panel_head_t& t : B.wr->panel_heads) ok = ok && (t.pattern < 0 || t.text_end >= 0);
     return ok;
 }
 

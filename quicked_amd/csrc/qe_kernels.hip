@@ -1770,6 +1770,53 @@ __global__ __launch_bounds__(256) void k_panel_tails_finish(int nslots, const in
     if (t < nslots) panel_tails_finish_slot(t, o_pair, o_start, tails);
 }
 
+// A member cut off by the text's start (qe_panel.h; QUICKED_PANEL_HEADS): a kernel of its own beside the
+// unchanged k_panel_hits / k_panel_tails, in their launch shape -- one lane per text, four text groups per workgroup, slices of
+// the panel in blockIdx.y.  Per member a fresh INFIX sweep of the member's REVERSED planes over the lane's first min(n, m + k)
+// text columns taken backwards (read from the forward planes, reversed in registers), then the tails' walk down the column the
+// registers end in.  The member index comes from blockIdx.y and a loop counter only: length, bound, allowance and block form
+// are wave-uniform; the column count, the live blocks and the words are the lane's.  One keeper per (slice, slot).
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_heads(PanelHeadsArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    PanelView P;
+    P.pl = A.pl_m_rev; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelTailKeeper keep;
+    keep.init();
+    u32 steps = 0, rows = 0;
+    panel_text_heads<Eq>(P, p0, p1, tp, n, A.min_overlap, keep, steps, rows);      // (a lane without a text has n = 0: no column, no head)
+    if (pair >= 0) panel_heads_store_part(A, nslices, slice, slot, keep, rows, steps);
+}
+template __global__ void k_panel_heads<SearchEq3>(PanelHeadsArgs);
+template __global__ void k_panel_heads<SearchEqIupac>(PanelHeadsArgs);
+
+// one thread per text slot: the slices' head keepers merged by the key and the slot's task of the end pass
+// (PanelHeadsMergeArgs); the task's pattern, the member's last bases, laid out word-aligned (PanelHeadPlanesArgs); and, behind
+// the end pass, its largest end into the record
+__global__ __launch_bounds__(256) void k_panel_heads_merge(PanelHeadsMergeArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_heads_merge_slot(A, t);
+}
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_head_planes(PanelHeadPlanesArgs A) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_head_planes_slot<Eq>(A, t);
+}
+template __global__ void k_panel_head_planes<SearchEq3>(PanelHeadPlanesArgs);
+template __global__ void k_panel_head_planes<SearchEqIupac>(PanelHeadPlanesArgs);
+__global__ __launch_bounds__(256) void k_panel_heads_finish(int nslots, const int32_t* __restrict__ o_pair, const int32_t* __restrict__ o_start, int32_t* __restrict__ heads) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < nslots) panel_heads_finish_slot(t, o_pair, o_start, heads);
+}
+
 // Every occurrence of every member, long texts split across lanes (qe_panel.h; quicked_batch_run_panel_scan; DESIGN.md
 // 4.14.2): k_panel_hits with a WINDOW SLOT {pair, c0, c1} per lane in the place of a text slot -- the grid is window groups x
 // panel slices, the launch shape k_panel_hits'.  The member index still comes from blockIdx.y and a loop counter only: length,

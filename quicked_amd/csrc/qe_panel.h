@@ -19,7 +19,8 @@
 //
 // The second half of the file is the all-occurrences run (quicked_batch_run_panel_all): the same lanes and
 // slices with qe_search.h's valley scan in the keeper's place; behind it the 3' tails (QUICKED_PANEL_TAILS):
-// the walk down the column that run ends in; and the windowed run (quicked_batch_run_panel_scan).
+// the walk down the column that run ends in; the 5' heads (QUICKED_PANEL_HEADS): a short sweep of the
+// reversed member over the text's start, and the same walk; and the windowed run (quicked_batch_run_panel_scan).
 #pragma once
 #include <stdint.h>
 
@@ -429,22 +430,26 @@ QE_S_HD void panel_tails_store_part(const PanelTailsArgs& A, int nslices, int sl
     int32_t* q = A.tpart + (int64_t)slice * A.H.nslots + slot;
     q[0] = keep.p; q[stride] = keep.r; q[2 * stride] = keep.d; q[3 * stride] = (int32_t)rows;
 }
-QE_S_HD void panel_tails_merge_slot(const PanelTailsMergeArgs& A, int t) {
-    const int pair = A.text[t];
-    A.o_pair[t] = -1;
-    if (pair < 0) return;
-    const int64_t stride = (int64_t)A.nslices * A.nslots;
-    PanelTailKeeper keep;
+// slot t's keepers of the slices merged by the key (any order gives the same one); -> the sum of the slices' fourth field
+QE_S_HD uint32_t panel_tail_parts_merge(const int32_t* tpart, int nslices, int nslots, int t, PanelTailKeeper& keep) {
+    const int64_t stride = (int64_t)nslices * nslots;
     keep.init();
     uint32_t rows = 0;
-    for (int s = 0; s < A.nslices; ++s) {
-        const int32_t* q = A.tpart + (int64_t)s * A.nslots + t;
+    for (int s = 0; s < nslices; ++s) {
+        const int32_t* q = tpart + (int64_t)s * nslots + t;
         PanelTailKeeper o;
         o.p = q[0]; o.r = q[stride]; o.d = q[2 * stride];
         keep.merge(o);
         rows += (uint32_t)q[3 * stride];
     }
-    A.o_rows[t] = rows;
+    return rows;
+}
+QE_S_HD void panel_tails_merge_slot(const PanelTailsMergeArgs& A, int t) {
+    const int pair = A.text[t];
+    A.o_pair[t] = -1;
+    if (pair < 0) return;
+    PanelTailKeeper keep;
+    A.o_rows[t] = panel_tail_parts_merge(A.tpart, A.nslices, A.nslots, t, keep);
     if (keep.p < 0) return;
     const int n = A.t_len[pair];
     int32_t task_n, in_end, base;
@@ -491,6 +496,154 @@ QE_S_HD void panel_tails_finish_slot(int t, const int32_t* o_pair, const int32_t
     if (pair < 0) return;
     int32_t* o = tails + 4 * (int64_t)pair;
     o[2] = o_start[t] < 0 ? -1 : o[2] + o_start[t];
+}
+
+// ---- a member cut off by the text's start: 5' heads (QUICKED_PANEL_HEADS on quicked_batch_run_panel_all)
+// The definition.  D^R is the INFIX matrix of rev(member p) (m bases, effective bound k) against rev(text) (n >= 1 columns),
+// rev() plain reversal.  Row r is a head of p when min_overlap <= r <= m - 1 and D^R[r][n] <= floor(r k / m): the member's last
+// r bases fit a stretch text[0:e) at the member's own error rate.  That is the tails' rule on the reversed sequences, so the
+// walk, the key and the keeper are the tails' own (panel_tail_walk, PanelTailKeeper): what a head is and which one wins is
+// decided there and nowhere else.
+//
+// Where D^R[.][n] comes from.  Nothing computes that matrix for the occurrences, so the lane sweeps it itself -- but only its
+// last c0 = min(n, m + k) columns, which are the text's FIRST c0 columns taken backwards: a head row within its allowance has
+// d <= floor(r k / m) <= k and its stretch at most r + d <= m - 1 + k text bases, so a fresh INFIX sweep of rev(member) over
+// rev(text[0:c0)) -- the stretches inside text[0:c0) only -- gives values >= the full matrix's and equal ones wherever the full
+// value is within the allowance (4.14.2's warm-up argument).  The sweep is search_chunk under the live-block rule with no scan
+// of row m; the store then holds the column the walk wants.
+struct PanelNoScan {
+    QE_S_HD void row(SearchLane&, int32_t, uint64_t, uint64_t, int, int) {}
+    QE_S_HD void no_row(SearchLane&) {}
+};
+// sweep columns [col0, col0 + ncols) of the backward walk over text[0:c0): the forward columns c0 - 1 - col0 down to
+// c0 - col0 - ncols, read forwards from the text's planes at that bit offset and reversed in registers; bits >= ncols are zero
+template <class Eq>
+QE_S_HD void panel_head_chunk(const uint64_t* tp, int c0, int col0, int ncols, uint64_t (&t)[Eq::W]) {
+    Eq::text_chunk(tp, c0 - col0 - ncols, ncols, t);
+    for (int k = 0; k < Eq::W; ++k) t[k] = panel_reverse_bits(t[k]) >> (64 - ncols);
+}
+// one member of NB blocks at the most (pp: its REVERSED planes) against the start of one text (tp: its forward planes, n
+// columns).  The partial chunk comes first, so every later chunk is a whole word of the text's planes.  steps: block steps of
+// the sweep, rows: row steps of the walk, both added to
+template <int NB, class Eq>
+QE_S_HD void panel_member_heads(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int min_overlap, int32_t p,
+                                PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
+    const int reach = m + search_effective(bound, m), c0 = n < reach ? n : reach;
+    SearchLane L;
+    search_lane_init(L, m, c0, SEARCH_INFIX, bound, 0);
+    SearchRegStore<NB, Eq> R;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.load(pp, m);
+    search_store_init<NB>(R, L);
+    PanelNoScan none;
+    for (int col0 = 0; col0 < c0;) {
+        const int ncols = col0 ? 64 : ((c0 - 1) & 63) + 1;
+        uint64_t t[Eq::W];
+        panel_head_chunk<Eq>(tp, c0, col0, ncols, t);
+        search_chunk<NB>(R, L, t, col0, ncols, none);
+        col0 += ncols;
+    }
+    steps += L.steps;
+    panel_tail_walk<NB>(R, L, min_overlap, p, keep, rows);      // (c0 = 0: an empty text has no head)
+}
+// One text against the members [p0, p1) of P, whose planes are the members' REVERSED ones: the text's best head among them
+template <class Eq>
+QE_S_HD void panel_text_heads(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int min_overlap,
+                              PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        if (nb <= 1) panel_member_heads<1, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
+        else if (nb == 2) panel_member_heads<2, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_heads<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
+    }
+}
+
+// k_panel_heads<Eq>: k_panel_hits' grid, slots and slices over the members' reversed planes (pl_m_rev; offsets, lengths and
+// bounds the panel's) and the texts' forward planes.  Per (slice s, slot t): field f of {pattern, overlap, score, row steps,
+// block steps} of the slice's best head at hpart[(f nslices + s) nslots + t].  A slot without a text writes nothing.
+struct PanelHeadsArgs {
+    const uint64_t* pl_m_rev;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
+    int32_t n_members, per_slice;
+    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
+    int32_t nslots;  const int32_t* text;
+    int32_t min_overlap;
+    int32_t* hpart;
+};
+// One thread per text slot (k_panel_heads_merge): the slices' keepers merged by the key into heads[pair] =
+// quicked_panel_head_t as {pattern, overlap, text_end, score} (heads: -1 everywhere before), o_rows[t] / o_steps[t] = the slot's
+// row and block steps.  text_end: the columns of the end pass's window, and the slot's task of that pass -- the member's last
+// `overlap` bases against the text's first min(n, overlap + score) columns, both forwards -- goes to o_pair / o_m / o_n / o_score
+// / o_end [t] (o_pair -1: no head); the task's pattern is laid out by k_panel_head_planes at three-plane word t plane_stride
+// of a scratch pool (o_plp_off[pair]).  k_panel_heads_finish then subtracts the pass's o_start (or leaves -1).
+struct PanelHeadsMergeArgs {
+    int32_t nslots, nslices;
+    const int32_t* text;  const int32_t* hpart;  const int32_t* t_len;
+    int64_t plane_stride;
+    int32_t* heads;  uint32_t* o_rows;  uint32_t* o_steps;
+    int32_t* o_pair;  int32_t* o_m;  int32_t* o_n;  int32_t* o_score;  int32_t* o_end;  int64_t* o_plp_off;
+};
+// One thread per text slot (k_panel_head_planes<Eq>): the last `overlap` bases of the head's member -- bits [m - overlap, m) of
+// the member's FORWARD planes (Eq::W words per row, at Eq::offset(m_off[pattern]) of pl_m) -- word-aligned to
+// Eq::offset(o_plp_off[pair]) of pool, two rows of zeros behind
+struct PanelHeadPlanesArgs {
+    int32_t nslots;
+    const int32_t* o_pair;  const int32_t* heads;
+    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int64_t* o_plp_off;
+    uint64_t* pool;
+};
+
+QE_S_HD void panel_heads_store_part(const PanelHeadsArgs& A, int nslices, int slice, int slot, const PanelTailKeeper& keep, uint32_t rows, uint32_t steps) {
+    const int64_t stride = (int64_t)nslices * A.nslots;
+    int32_t* q = A.hpart + (int64_t)slice * A.nslots + slot;
+    q[0] = keep.p; q[stride] = keep.r; q[2 * stride] = keep.d; q[3 * stride] = (int32_t)rows; q[4 * stride] = (int32_t)steps;
+}
+QE_S_HD void panel_heads_merge_slot(const PanelHeadsMergeArgs& A, int t) {
+    const int pair = A.text[t];
+    A.o_pair[t] = -1;
+    if (pair < 0) return;
+    PanelTailKeeper keep;
+    A.o_rows[t] = panel_tail_parts_merge(A.hpart, A.nslices, A.nslots, t, keep);
+    uint32_t steps = 0;
+    for (int s = 0; s < A.nslices; ++s) steps += (uint32_t)A.hpart[((int64_t)4 * A.nslices + s) * A.nslots + t];
+    A.o_steps[t] = steps;
+    if (keep.p < 0) return;
+    // the best search's start-pass form walks the in_end columns that end at column task_n: both the window, from column 0
+    const int n = A.t_len[pair], w = search_hit_window(keep.r, n, keep.d);
+    A.o_pair[t] = pair; A.o_m[t] = keep.r; A.o_n[t] = w; A.o_score[t] = keep.d; A.o_end[t] = w;
+    A.o_plp_off[pair] = (int64_t)t * A.plane_stride;
+    int32_t* o = A.heads + 4 * (int64_t)pair;
+    o[0] = keep.p; o[1] = keep.r; o[2] = w; o[3] = keep.d;
+}
+// the member's last `len` bases: row `row` of the task's pattern is bits [m - len + 64 row, + 64) of the forward planes, cut
+// at the member's end; rows past the suffix are zeros
+template <class Eq>
+QE_S_HD void panel_head_planes_slot(const PanelHeadPlanesArgs& A, int t) {
+    const int pair = A.o_pair[t];
+    if (pair < 0) return;
+    const int p = A.heads[4 * (int64_t)pair], len = A.heads[4 * (int64_t)pair + 1], nw = (len + 63) >> 6, m = A.m_len[p];
+    const uint64_t* src = A.pl_m + Eq::offset(A.m_off[p]);
+    uint64_t* dst = A.pool + Eq::offset(A.o_plp_off[pair]);
+    for (int row = 0; row < nw + 2; ++row) {
+        uint64_t x[Eq::W];
+        for (int k = 0; k < Eq::W; ++k) x[k] = 0;
+        if (row < nw) {
+            const int left = len - 64 * row, ncols = left < 64 ? left : 64;
+            search_text_words<Eq::W>(src, m - left, ncols, x);
+            if (ncols < 64) for (int k = 0; k < Eq::W; ++k) x[k] &= ((uint64_t)1 << ncols) - 1;
+        }
+        for (int k = 0; k < Eq::W; ++k) dst[Eq::W * (int64_t)row + k] = x[k];
+    }
+}
+// k_panel_heads_finish's slot t: the end pass's largest end is its window less o_start
+QE_S_HD void panel_heads_finish_slot(int t, const int32_t* o_pair, const int32_t* o_start, int32_t* heads) {
+    const int pair = o_pair[t];
+    if (pair < 0) return;
+    int32_t* o = heads + 4 * (int64_t)pair;
+    o[2] = o_start[t] < 0 ? -1 : o[2] - o_start[t];
 }
 
 // ---- every occurrence of every member, long texts split across lanes (quicked_batch_run_panel_scan)

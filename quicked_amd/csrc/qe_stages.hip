@@ -1130,6 +1130,9 @@ struct HitsOut {                                   // of both all-occurrences ru
     // QUICKED_PANEL_TAILS (run_panel_tails): every pair's quicked_panel_tail_t (-1 in every field: none) and the row steps of
     // the walk per slot (task_pair.size() of them)
     int32_t* d_tails = nullptr; u32* d_tail_rows = nullptr;
+    // QUICKED_PANEL_HEADS (run_panel_heads): every pair's quicked_panel_head_t (-1 in every field: none) and, per slot, the
+    // block steps of the head sweep | the row steps of its walk (2 x task_pair.size() of them)
+    int32_t* d_heads = nullptr; u32* d_head_steps = nullptr;
 };
 // The per-pair arrays of an all-occurrences run -- found (0) | smallest score (-1) | stored - 1 (-1: the scan then counts 0) --,
 // the offsets and `nadv` step counters.  -> the stored counts, for the forward pass to fill
@@ -1590,6 +1593,73 @@ static void run_panel_tails(quicked_batch& B, Context& C, const SearchRun& sr, c
     HIP_CHECK(hipGetLastError());
 }
 
+// The heads of an all-occurrences panel run (QUICKED_PANEL_HEADS; qe_panel.h): k_panel_heads<Eq> in
+// k_panel_hits' launch shape over the members' reversed planes and the texts' forward planes leaves one keeper per (slice,
+// slot); k_panel_heads_merge merges them per text and writes the end-pass task of every text that has a head;
+// k_panel_head_planes<Eq> lays the task's pattern -- the member's last `overlap` bases, forwards -- out in a scratch pool of one
+// stretch per slot (the panel's tallest member and two rows of zeros); the end pass is the unchanged k_search<4, Eq> in its
+// start-pass form over those planes and the texts' FORWARD planes, from column 0: its largest end is text_end, so it wants no
+// reversed copy of the texts; k_panel_heads_finish writes it into the record.  The kernels are timed as kind 0.  Nothing here
+// waits for the host, depends on the occurrences' total or reads what the occurrence kernel wrote.  The steps go to counters
+// 6 and 7, never into counter 0.
+static size_t panel_heads_fixed_bytes(const quicked_batch& B, const SearchRun& sr, size_t nslots, size_t nslices) {
+    if (!sr.heads) return 0;
+    const size_t n = (size_t)B.n, plane_words = (size_t)iupac_offset(3 * (int64_t)panel_tallest_rows(*sr.panel)) * nslots + 8;
+    // (a PREFIX run packs no reversed panel planes of its own)
+    const size_t rev = sr.mode == SEARCH_INFIX ? 0 : (size_t)iupac_offset((int64_t)panel_plane_words(*sr.panel) + 24) * sizeof(u64);
+    return rev + 5 * nslices * nslots * sizeof(int32_t) + 4 * n * sizeof(int32_t) + 9 * nslots * sizeof(int32_t) + n * sizeof(int64_t) + plane_words * sizeof(u64) + 8 * 512;
+}
+static void run_panel_heads(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const PanelHitsArgs& a, int nslices, const u64* pl_m_rev, HitsOut& O) {
+    const size_t n = (size_t)B.n, nslots = D.nslots;
+    const int eq = sr.eq;
+    PanelHeadsArgs h{};
+    h.pl_m_rev = pl_m_rev; h.m_off = a.m_off; h.m_len = a.m_len; h.m_bound = a.m_bound;
+    h.n_members = a.n_members; h.per_slice = a.per_slice;
+    h.pl_t = a.pl_t; h.pl_t_off = a.pl_t_off; h.t_len = a.t_len;
+    h.nslots = a.nslots; h.text = a.text; h.min_overlap = B.head_min_overlap;
+    h.hpart = C.scratch_p->take<int32_t>(5 * (size_t)nslices * nslots);
+    {
+        TimedLaunches tl(C, 0);
+        // k_search_panel's launch shape, as k_panel_hits
+        const dim3 grid((unsigned)((D.ngroups + 3) / 4), (unsigned)nslices);
+        if (eq) hipLaunchKernelGGL(k_panel_heads<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, h);
+        else hipLaunchKernelGGL(k_panel_heads<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, h);
+        HIP_CHECK(hipGetLastError());
+        tl.end();
+    }
+    O.d_heads = C.scratch_p->take<int32_t>(4 * n);
+    HIP_CHECK(hipMemsetAsync(O.d_heads, 0xFF, 4 * n * sizeof(int32_t), C.stream));
+    O.d_head_steps = C.scratch_p->take<u32>(2 * nslots);
+    HIP_CHECK(hipMemsetAsync(O.d_head_steps, 0, 2 * nslots * sizeof(u32), C.stream));
+    PanelHeadsMergeArgs g{};
+    g.nslots = (int32_t)nslots; g.nslices = nslices; g.text = D.d_text; g.hpart = h.hpart; g.t_len = B.d_t_len;
+    g.plane_stride = 3 * (int64_t)panel_tallest_rows(*sr.panel);
+    g.heads = O.d_heads; g.o_steps = O.d_head_steps; g.o_rows = O.d_head_steps + nslots;
+    int32_t* q = C.scratch_p->take<int32_t>(7 * nslots);
+    g.o_pair = q; g.o_m = q + nslots; g.o_n = q + 2 * nslots; g.o_score = q + 3 * nslots; g.o_end = q + 4 * nslots;
+    int32_t* o_start = q + 5 * nslots;
+    u32* o_adv = (u32*)(q + 6 * nslots);
+    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(o_adv, 0, nslots * sizeof(u32), C.stream));
+    g.o_plp_off = C.scratch_p->take<int64_t>(n);
+    HIP_CHECK(hipMemsetAsync(g.o_plp_off, 0, n * sizeof(int64_t), C.stream));
+    const dim3 grid((unsigned)((nslots + 255) / 256));
+    hipLaunchKernelGGL(k_panel_heads_merge, grid, dim3(256), 0, C.stream, g);
+    PanelHeadPlanesArgs w{};
+    w.nslots = (int32_t)nslots; w.o_pair = g.o_pair; w.heads = O.d_heads;
+    w.pl_m = a.pl_m; w.m_off = D.d_pl_off; w.m_len = D.d_len; w.o_plp_off = g.o_plp_off;
+    w.pool = C.scratch_p->take<u64>((size_t)(eq ? iupac_offset(g.plane_stride) : g.plane_stride) * nslots + 8);
+    if (eq) hipLaunchKernelGGL(k_panel_head_planes<SearchEqIupac>, grid, dim3(256), 0, C.stream, w);
+    else hipLaunchKernelGGL(k_panel_head_planes<SearchEq3>, grid, dim3(256), 0, C.stream, w);
+    HIP_CHECK(hipGetLastError());
+    PairView PV = pair_view(B, false);
+    PV.pl_p = w.pool; PV.pl_p_off = g.o_plp_off;
+    PV.pl_t = a.pl_t; PV.pl_t_off = B.d_plt_off;
+    launch_start_pass(C, eq, PV, nslots, g.o_pair, g.o_m, g.o_n, g.o_score, g.o_end, o_start, o_adv);
+    hipLaunchKernelGGL(k_panel_heads_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)g.o_pair, (const int32_t*)o_start, O.d_heads);
+    HIP_CHECK(hipGetLastError());
+}
+
 // Every occurrence of every member (quicked_batch_run_panel_all): the panel upload and pack of a panel run,
 // k_panel_hits over text groups x slices -- per (slice, slot) its counts and up to max_hits raw records --, k_panel_hits_count
 // (found / smallest score / stored per pair), the offset scan over the stored counts in the order of the pairs and -- the one
@@ -1615,7 +1685,7 @@ static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, c
     const size_t n = (size_t)B.n, nslices = (size_t)panel_hits_slices(C, nslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
     b += nslots * 8 + n * 12 + (n + 1) * 8;
-    return b + panel_align_fixed_bytes(B, sr) + panel_tails_fixed_bytes(B, sr, nslots, nslices);
+    return b + panel_align_fixed_bytes(B, sr) + panel_tails_fixed_bytes(B, sr, nslots, nslices) + panel_heads_fixed_bytes(B, sr, nslots, nslices);
 }
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
@@ -1657,12 +1727,19 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         if (!pl_t_rev) { if (!eq) ensure_reversed(B, C); pl_t_rev = panel_text_planes(B, C, eq, true); }
         return pl_t_rev;
     };
+    // ... and the panel's, for the occurrences' start pass and the heads' sweep
+    const u64* pl_m_rev = nullptr;
+    auto panel_planes_reversed = [&]() {
+        if (!pl_m_rev) pl_m_rev = panel_planes(B, C, D, K, eq, true);
+        return pl_m_rev;
+    };
     // ---- counts per pair, offsets in the order of the pairs (a pair without a slot has -1 + 1 = 0 stored), the total
     PanelHitsCountArgs c{};
     c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits; c.text = D.d_text; c.part = a.part;
     c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.o_adv = O.d_adv;
     hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
     if (sr.tails) run_panel_tails(B, C, sr, D, ta, nslices, text_planes_reversed(), O);      // (before the total: it needs none)
+    if (sr.heads) run_panel_heads(B, C, sr, D, a, nslices, panel_planes_reversed(), O);      // (likewise; no reversed text planes)
     hits_total(B, C, O, d_plen, B.d_t_len);
     if (O.total <= 0) return O;
     const size_t nh = (size_t)O.total;
@@ -1687,7 +1764,7 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         // ---- the start pass: one lane per stored occurrence over its window, reversed
         if (!eq) ensure_reversed(B, C);
         PairView PV = pair_view(B, true);
-        PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
+        PV.pl_p = panel_planes_reversed(); PV.pl_p_off = e.o_plp_off;
         PV.pl_t = text_planes_reversed(); PV.pl_t_off = e.o_plt_off;
         launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
         hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
@@ -2173,6 +2250,7 @@ static void reset_host_results(quicked_batch& B) {
     B.wr->panel_occ.clear();
     B.wr->panel_cigars = false; B.wr->panel_cig_off.clear(); B.wr->panel_cig_pool.clear();
     B.wr->panel_tails.clear();
+    B.wr->panel_heads.clear();
     B.wr->deferred_pairs = 0;
 }
 
