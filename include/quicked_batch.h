@@ -240,7 +240,8 @@ quicked_status_t quicked_batch_hits(quicked_batch_t* batch, quicked_hit_t* hits,
  * n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0; a negative bound; with the matrix flag, (texts) x
  * n_patterns above 2^28 (every text of the batch has a row in the matrix, the empty ones too).
  * QUICKED_UNIMPLEMENTED, nothing queued: a member longer than QUICKED_PANEL_MAX_LEN bases (the register form's limit); sync == 0;
- * a batch configured with check != 0 (as for the other search runs).
+ * a batch configured with check != 0 (as for the other search runs).  (sync == 0 is accepted on a batch object that
+ * quicked_batch_configure_panel_queue, below, switched on -- never with QUICKED_PANEL_MATRIX.)
  * No alignments: the tags of quicked_batch_configure_tags are ignored; the CIGAR, tag, location and hit getters return what
  * they return after any run that produced none of their data.  The two panel getters return QUICKED_ERROR after any run that
  * was not a panel run.  Counters [0] and kernel_times slot [0] count the passes' block steps and launches, as for a search
@@ -277,13 +278,14 @@ quicked_status_t quicked_batch_panel_matrix(quicked_batch_t* batch, int32_t* sco
  * QUICKED_PANEL_CIGARS (QUICKED_PANEL_MATRIX too: it has no meaning here); n_patterns outside 1 .. QUICKED_PANEL_MAX_PATTERNS; a member of length 0;
  * a negative bound; max_hits outside 1 .. 4096; (non-empty texts) x max_hits above 2^26.
  * QUICKED_UNIMPLEMENTED, nothing queued: a member longer than QUICKED_PANEL_MAX_LEN bases; sync == 0 (the host reads the total
- * between the passes); a batch configured with check != 0.
+ * between the passes; a batch object that quicked_batch_configure_panel_queue, below, switched on gives the room instead and
+ * is accepted); a batch configured with check != 0.
  * The three getters below return QUICKED_ERROR (the total: -1) after any run that was not of this kind;
  * quicked_batch_panel_results, quicked_batch_panel_matrix, quicked_batch_hits, quicked_batch_hit_counts,
  * quicked_batch_locations and the CIGAR and tag getters return what they return after any run that produced none of their
  * data.  Tags are ignored.  Counters [0] and kernel_times slot [0] count both passes, as for the other search runs.  A reload
  * clears the results.  QUICKED_PANEL_TAILS and QUICKED_PANEL_HEADS (below) add the members a text's end or start cuts off.
- * Not built: queued runs, members over 256 bases, alignments for quicked_batch_run_panel and
+ * Not built: members over 256 bases, alignments for quicked_batch_run_panel and
  * quicked_batch_run_search_all (this run has them: QUICKED_PANEL_CIGARS below), statistics and MD tags per occurrence. */
 typedef struct { int32_t pattern, text_start, text_end, score; } quicked_panel_occ_t;   /* 16 bytes */
 quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int mode,
@@ -434,11 +436,51 @@ quicked_status_t quicked_batch_panel_tails(quicked_batch_t* batch, quicked_panel
  * Counters, in a flagged run only (0 otherwise): [6] is the block steps of the head sweep, [7] the row steps of its walk;
  * [0] .. [3] keep their meaning and their values.  kernel_times slot [0] includes the head kernels.
  * Not built: heads or tails on quicked_batch_run_panel_scan; one head per member instead of one per text; head and tail CIGARs;
- * reverse-complement members; queued (sync == 0) panel runs. */
+ * reverse-complement members.  (For queued (sync == 0) panel runs see quicked_batch_configure_panel_queue below.) */
 enum { QUICKED_PANEL_HEADS = 8192 };           /* OR-ed into mode of quicked_batch_run_panel_all (128, 256, 1024 and 4096 stay unknown bits) */
 typedef struct { int32_t pattern, overlap, text_end, score; } quicked_panel_head_t;   /* 16 bytes */
 quicked_status_t quicked_batch_configure_panel_heads(quicked_batch_t* batch, int32_t min_overlap);
 quicked_status_t quicked_batch_panel_heads(quicked_batch_t* batch, quicked_panel_head_t* out /* n */);
+/* Queued panel runs.  Every panel run is sync != 0 only on a batch object as it is created.  A demultiplexing or trimming job --
+ * thousands of batches against one fixed panel -- wants what pair runs have: runs that rotate over sets of {stream, pool,
+ * planes}, a thread that reloads the next batch object meanwhile, quicked_batch_fetch later.  That is opt-in per batch object:
+ *
+ * quicked_batch_configure_panel_queue(batch, max_total).  0, the default of every batch, is off: every panel run with
+ * sync == 0 answers QUICKED_UNIMPLEMENTED with nothing queued.  1 .. 2^26 is on.  Anything else, or a NULL batch, is
+ * QUICKED_ERROR and leaves the setting unchanged.  Runs with sync != 0 never look at the setting: no launch, no allocation, no
+ * copy of theirs changes.  A reload keeps the setting.
+ *
+ * With the setting on, sync == 0 is accepted by quicked_batch_run_panel (PREFIX and INFIX, both IUPAC flags) and by
+ * quicked_batch_run_panel_all (PREFIX and INFIX, both IUPAC flags, QUICKED_PANEL_TAILS, QUICKED_PANEL_HEADS, in every combination
+ * the sync run accepts).  Every QUICKED_ERROR rule of the two runs comes first, as before; a member over 256 bases and
+ * check != 0 stay QUICKED_UNIMPLEMENTED.  The run returns what a queued quicked_batch_run_search returns.  The panel and
+ * max_dist are read during the call: the caller may free them on return.  Between the call and quicked_batch_fetch every
+ * getter answers exactly as before the call -- panel getters, scores, counters, and which kind of run the last one was.  The
+ * rules of queued runs hold: the results move into the batch's own result arena at the end of the run; any number of runs of
+ * OTHER batch objects may be queued before the fetch; the batch's next run, a reload or destroy discards the run; any thread
+ * may fetch.
+ *
+ * What the fetch brings.  quicked_batch_run_panel: everything the sync run leaves, bit for bit.  quicked_batch_run_panel_all:
+ * let W be the total the sync run would store, its hit_off[n].  found, quicked_batch_scores, the statuses, the tails, the
+ * heads and counters [2], [6], [7] are the sync run's whatever max_total is.  If W <= max_total so is everything else: stored,
+ * hit_off, every record, counter [0].  If W > max_total the fetch still returns QUICKED_OK and the records are the first
+ * max_total of the sync run's array -- which is in the order of the pairs, then (pattern, text_end) --:
+ *     hit_off'[i] = min(hit_off[i], max_total),   stored'[i] = hit_off'[i + 1] - hit_off'[i],
+ * and counter [0] counts the block steps really walked.  This is the library's cap rule one level up: a cap per text shows as
+ * stored < found, a cap per run as wanted > total.  quicked_batch_panel_queue_wanted returns W after such a fetch, and -1
+ * after anything else: a sync run, a fetched quicked_batch_run_panel, a reload, before the fetch.
+ * The run takes its records' room -- min(max_total, non-empty texts x max_hits) of them, 16 bytes each, 60 with INFIX -- from
+ * its pool whatever W turns out to be, and the start pass launches a lane per record of that room: lanes past W leave at once
+ * (DESIGN.md 4.14.6 has what they cost).  max_total also sizes the batch object's own result arena, where the run's results wait
+ * for the fetch: 20 bytes per record of that room with INFIX, 16 with PREFIX -- up to 1.3 GB at 2^26 --, allocated at the first
+ * queued run that needs it and kept for the object's life.  A caller that rotates several batch objects budgets for one each.
+ *
+ * QUICKED_UNIMPLEMENTED with sync == 0 as before, nothing queued, setting on or off: QUICKED_PANEL_MATRIX; QUICKED_PANEL_CIGARS
+ * (the host reads the strings' total); quicked_batch_run_panel_scan; quicked_batch_run_search_all.
+ * Not built: queued runs with the matrix or the strings, of the windowed run and of quicked_batch_run_search_all; a room that
+ * grows by itself (a run that overflowed is run again with max_total >= wanted). */
+quicked_status_t quicked_batch_configure_panel_queue(quicked_batch_t* batch, int64_t max_total);
+int64_t          quicked_batch_panel_queue_wanted(quicked_batch_t* batch);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -66,6 +66,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_panel_hit_cigar_bytes", "quicked_batch_panel_hit_cigars",
            "quicked_batch_configure_panel_tails", "quicked_batch_panel_tails",
            "quicked_batch_configure_panel_heads", "quicked_batch_panel_heads",
+           "quicked_batch_configure_panel_queue", "quicked_batch_panel_queue_wanted",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -166,6 +167,11 @@ def lib():
         L.quicked_batch_configure_panel_heads.restype = C.c_int
         L.quicked_batch_panel_heads.argtypes = [C.c_void_p, C.c_void_p]
         L.quicked_batch_panel_heads.restype = C.c_int
+    if hasattr(L, "quicked_batch_configure_panel_queue"):      # (as above)
+        L.quicked_batch_configure_panel_queue.argtypes = [C.c_void_p, C.c_int64]
+        L.quicked_batch_configure_panel_queue.restype = C.c_int
+        L.quicked_batch_panel_queue_wanted.argtypes = [C.c_void_p]
+        L.quicked_batch_panel_queue_wanted.restype = C.c_int64
     L.quicked_batch_sync.argtypes = [C.c_void_p]
     L.quicked_batch_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_cigar_bytes.restype = C.c_int64
@@ -501,8 +507,10 @@ class ResidentBatch:
             if md.shape != (k,):
                 raise ValueError("max_dist: one bound per panel member")
             st = self._lib.quicked_batch_run_panel(self._h, mode, k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data, md.ctypes.data, 0, 1 if sync else 0)
-        if st not in (QUICKED_ERROR, QUICKED_UNIMPLEMENTED):
-            self._panel_k = k      # what panel_matrix() sizes its arrays with: the panel of the last run that got past the argument checks
+        if sync and st not in (QUICKED_ERROR, QUICKED_UNIMPLEMENTED):
+            # what panel_matrix() sizes its arrays with: the panel of the last run that got past the argument checks (a queued run
+            # has no matrix, and the getters show the run before it until the fetch)
+            self._panel_k = k
         return st
 
     def panel_results(self):
@@ -530,7 +538,8 @@ class ResidentBatch:
         """quicked_batch_run_panel_all: every occurrence of every panel member in every text, at most max_hits (1 .. 4096) stored
         per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag); PANEL_CIGARS OR-ed into
         mode aligns every stored occurrence besides (panel_hit_cigars()); PANEL_TAILS (INFIX only) reports every text's 3' tail
-        besides (panel_tails()); PANEL_HEADS reports every text's 5' head besides (panel_heads()).  Sync runs only."""
+        besides (panel_tails()); PANEL_HEADS reports every text's 5' head besides (panel_heads()).  sync=False needs
+        configure_panel_queue() first and no PANEL_CIGARS; fetch() then brings the results."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -607,6 +616,16 @@ class ResidentBatch:
         if st < 0:
             raise QuickedException(st)
         return out[:self.n]
+
+    def configure_panel_queue(self, max_total):
+        """quicked_batch_configure_panel_queue: 0 (the default) keeps run_panel / run_panel_all sync only; 1 .. 2**26 lets this
+        batch object queue them (sync=False) and is the room for the records of a queued run_panel_all.  -> the status"""
+        return self._lib.quicked_batch_configure_panel_queue(self._h, int(max_total))
+
+    def panel_queue_wanted(self):
+        """-> the total a fetched queued run_panel_all would have stored without max_total (above it: the records are the first
+        max_total of them), -1 after anything else"""
+        return int(self._lib.quicked_batch_panel_queue_wanted(self._h))
 
     def configure_panel_heads(self, min_overlap=3):
         """quicked_batch_configure_panel_heads: the shortest head (1 .. PANEL_MAX_LEN) of the PANEL_HEADS runs to come; the tails'

@@ -126,9 +126,11 @@ struct quicked_batch {
         // ... run with QUICKED_PANEL_HEADS: panel_heads [n], every text's head or -1 in every field (quicked_batch_panel_heads);
         // else empty
         std::vector<quicked_panel_head_t> panel_heads;
+        // ... fetched from a queued run (quicked_batch_configure_panel_queue): the total W the sync run would have stored; else -1
+        int64_t panel_queue_wanted = -1;
         int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int64_t deferred_pairs = 0;               // QuickEd: pairs that were aligned after the run (quicked_batch_deferred_pairs)
-        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; panel_found.clear(); panel_occ_off.clear(); panel_occ.clear(); panel_cigars = false; panel_cig_off.clear(); panel_cig_pool.clear(); panel_tails.clear(); panel_heads.clear(); deferred_pairs = 0; for (auto& c : counters) c = 0; }
+        void clear() { score.clear(); status.clear(); cigar_off.clear(); cigar_pool.size = 0; check_ok.clear(); stats.clear(); md_off.clear(); md_pool.size = 0; text_start.clear(); text_end.clear(); found.clear(); hit_off.clear(); hits.clear(); panel_hits.clear(); panel_score.clear(); panel_end.clear(); panel_members = 0; panel_found.clear(); panel_occ_off.clear(); panel_occ.clear(); panel_cigars = false; panel_cig_off.clear(); panel_cig_pool.clear(); panel_tails.clear(); panel_heads.clear(); panel_queue_wanted = -1; deferred_pairs = 0; for (auto& c : counters) c = 0; }
     } res[2];
     int vis = 0;
     HostResults* wr = &res[0];
@@ -140,6 +142,7 @@ struct quicked_batch {
     int tags = 0;                                 // QUICKED_TAG_* of the runs to come (quicked_batch_configure_tags)
     int32_t tail_min_overlap = 3;                 // the shortest tail of the QUICKED_PANEL_TAILS runs to come (quicked_batch_configure_panel_tails)
     int32_t head_min_overlap = 3;                 // the shortest head of the QUICKED_PANEL_HEADS runs to come (quicked_batch_configure_panel_heads)
+    int64_t panel_queue_total = 0;                // 0: panel runs are sync only; else the room for a queued run's records (quicked_batch_configure_panel_queue)
     // ... of the run in progress: `tags` for a sync != 0 run that aligns, else 0 (run_batch) -- what format_segments and the
     // host-driven flows of that run read, whatever the caller configures meanwhile
     int run_tags = 0;
@@ -240,7 +243,8 @@ struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; cons
 // tail is the batch's tail_min_overlap)
 // ... and heads: QUICKED_PANEL_HEADS, every text's best member cut off by the text's start besides (run_panel_heads; the
 // shortest head is the batch's head_min_overlap)
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; bool cigars = false; bool tails = false; bool heads = false; };
+// ... and queue_total > 0: a panel run queued with sync == 0 (quicked_batch_configure_panel_queue): the room for its records
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; bool cigars = false; bool tails = false; bool heads = false; int64_t queue_total = 0; };
 // the window slots of a batch at `window` columns per lane: every non-empty text in ceil(n / window) of them
 inline int64_t panel_scan_slots(const quicked_batch& B, int64_t window) {
     int64_t slots = 0;

@@ -339,8 +339,10 @@ QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode
         if (x->sr.panel->matrix && B->n * (int64_t)x->sr.panel->n_patterns > ((int64_t)1 << 28)) return QUICKED_ERROR;
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
-        if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the results are reduced and read at the run's end
-        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
+        // queued only on a batch configured for it (quicked_batch_configure_panel_queue), and never with the matrix
+        if (!x->sync && (B->panel_queue_total == 0 || x->sr.panel->matrix)) return QUICKED_UNIMPLEMENTED;
+        if (!x->sync) x->sr.queue_total = B->panel_queue_total;
+        return run_batch(*B, banded_params(true), x->sync != 0, nullptr, &x->sr);
     }, &arg);
 }
 
@@ -381,9 +383,24 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
         if (texts * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;      // the room for the stored occurrences
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
-        if (!x->sync) return QUICKED_UNIMPLEMENTED;                                 // the start pass is sized from a total the host reads
-        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
+        // queued only on a batch configured for it, which sizes the start pass from its max_total instead of the total the host
+        // reads; never with the strings, whose total the host reads too
+        if (!x->sync && (B->panel_queue_total == 0 || x->sr.cigars)) return QUICKED_UNIMPLEMENTED;
+        if (!x->sync) x->sr.queue_total = B->panel_queue_total;
+        return run_batch(*B, banded_params(true), x->sync != 0, nullptr, &x->sr);
     }, &arg);
+}
+
+// Queued panel runs, per batch object: the room for a queued all-occurrences run's records (0: panel runs are sync only), and
+// the total such a run would have stored without that limit
+QE_API quicked_status_t quicked_batch_configure_panel_queue(quicked_batch_t* batch, int64_t max_total) {
+    if (!batch || max_total < 0 || max_total > ((int64_t)1 << 26)) return QUICKED_ERROR;
+    batch->panel_queue_total = max_total;
+    return QUICKED_OK;
+}
+QE_API int64_t quicked_batch_panel_queue_wanted(quicked_batch_t* batch) {
+    const HostResults* R = hit_results(batch, &HostResults::panel_found);
+    return R ? R->panel_queue_wanted : -1;
 }
 
 // Windowed panel search: run_panel_all's checks, the window's, and the room for the stored occurrences per window slot

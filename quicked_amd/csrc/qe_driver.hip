@@ -58,6 +58,9 @@
 #if __has_include("qe_kernels_stub_heads.h")
 #include "qe_kernels_stub_heads.h"
 #endif
+#if __has_include("qe_kernels_stub_queue.h")
+#include "qe_kernels_stub_queue.h"
+#endif
 #endif
 
 
@@ -636,10 +639,27 @@ static void stash_results(quicked_batch& B, Context& C, PendingFetch& F) {
         stash_add(items, F.d_leaf_adv, nl * 4); stash_add(items, F.d_leaf_steps, nl * 4);
     }
     if (F.fast) { stash_add(items, F.d_cut, nq * 4); stash_add(items, F.d_skip, nq * 4); stash_add(items, F.d_stage_steps, nq * 4); }
+    const size_t n = (size_t)B.n;
+    if (F.kind == 3) {
+        PanelOut& P = *F.PO;
+        stash_add(items, P.d_hits, n * sizeof(quicked_panel_hit_t)); stash_add(items, P.d_adv, P.text.size() * 4); stash_add(items, P.d_adv2, P.text.size() * 4);
+    }
+    // an all-occurrences panel run: the arrays per pair and per slot whole, the records and their step counts -- room for `cap`
+    // of them -- to their real length below
+    HitsOut* const H = F.kind == 4 ? F.HO.get() : nullptr;
+    if (H) {
+        const size_t ns = H->task_pair.size();
+        stash_add(items, H->d_found, n * 4); stash_add(items, H->d_best, n * 4); stash_add(items, H->d_off, (n + 1) * 8); stash_add(items, H->d_adv, ns * 4);
+        stash_add(items, H->d_queue, 32);
+        stash_add(items, H->d_tails, n * sizeof(quicked_panel_tail_t)); stash_add(items, H->d_tail_rows, ns * 4);
+        stash_add(items, H->d_heads, n * sizeof(quicked_panel_head_t)); stash_add(items, H->d_head_steps, 2 * ns * 4);
+    }
     const bool strings = F.kind == 2 && F.want_strings && F.AO.pool && F.AO.total;
     size_t need = 256;
     for (const StashItem& it : items) need += (it.bytes + 255) & ~(size_t)255;
     if (strings) need += ((F.AO.pool_bytes + 255) & ~(size_t)255) + 256;
+    const size_t rec_bytes = H ? ((size_t)H->cap * 16 + 255) & ~(size_t)255 : 0, adv2_bytes = (H && H->d_adv2) ? ((size_t)H->cap * 4 + 255) & ~(size_t)255 : 0;
+    need += rec_bytes + adv2_bytes;
     if (B.result_bytes < need) {
         if (B.result_arena) { HIP_CHECK(hipDeviceSynchronize()); device_free(B.result_arena, B.device); B.result_arena = nullptr; B.result_bytes = 0; }
         const size_t cap = need + need / 8;
@@ -676,6 +696,17 @@ static void stash_results(quicked_batch& B, Context& C, PendingFetch& F) {
         F.AO.total = d_total; F.AO.pool = dst;
     }
     flush();
+    if (H) {
+        // (behind the flush: the byte counts are read from their place in the arena)
+        int32_t* recs = (int32_t*)(B.result_arena + top); top += rec_bytes;
+        hipLaunchKernelGGL(k_copy_total, dim3(1024), dim3(256), 0, C.stream, (uint4*)recs, (const uint4*)H->d_hits, (const int64_t*)(H->d_queue + 1), (int64_t)(rec_bytes >> 4));
+        H->d_hits = recs;
+        if (H->d_adv2) {
+            u32* adv2 = (u32*)(B.result_arena + top); top += adv2_bytes;
+            hipLaunchKernelGGL(k_copy_total, dim3(256), dim3(256), 0, C.stream, (uint4*)adv2, (const uint4*)H->d_adv2, (const int64_t*)(H->d_queue + 2), (int64_t)(adv2_bytes >> 4));
+            H->d_adv2 = adv2;
+        }
+    }
 }
 
 // sets of {streams, pools, planes} that rotate for a batch of n pairs: enough runs in flight for ~2048 waves (two per SIMD)
@@ -696,7 +727,16 @@ static void finisher_submit(quicked_batch& B, const std::shared_ptr<void>& pf);
 // (counter 7) too.  -> false as well where a head's end pass did not find its score
 template <class Occ>
 static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vector<int32_t>& found, std::vector<int64_t>& off, std::vector<Occ>& occ) {
-    const size_t n = (size_t)B.n, nh = (size_t)HO.total;
+    const size_t n = (size_t)B.n;
+    // (a queued run's total: the last of its offsets -- clamped to the run's room -- and the unclamped one beside them)
+    if (HO.total < 0) {
+        std::vector<int64_t> q;
+        FetchBatch fb(C);
+        fb.add(off, (const int64_t*)HO.d_off, n + 1); fb.add(q, (const int64_t*)HO.d_queue, 1);
+        fb.sync();
+        B.wr->panel_queue_wanted = q[0];
+    }
+    const size_t nh = (size_t)(HO.total < 0 ? off[n] : HO.total);
     std::vector<int32_t> best; std::vector<u32> adv, adv2, al, rows, hsteps;
     occ.resize(nh);
     {
@@ -718,7 +758,7 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
             fb.add(hsteps, (const u32*)HO.d_head_steps, 2 * HO.task_pair.size());
         }
         fb.add(found, (const int32_t*)HO.d_found, n); fb.add(best, (const int32_t*)HO.d_best, n);
-        fb.add(off, (const int64_t*)HO.d_off, n + 1);
+        if (HO.total >= 0) fb.add(off, (const int64_t*)HO.d_off, n + 1);
         fb.add(adv, (const u32*)HO.d_adv, HO.task_pair.size());
         if (HO.d_adv2) fb.add(adv2, (const u32*)HO.d_adv2, nh);
         fb.add_bytes(occ.data(), HO.d_hits, nh * sizeof(Occ));
@@ -737,6 +777,23 @@ static bool fetch_hits(quicked_batch& B, Context& C, const HitsOut& HO, std::vec
     }
     for (const quicked_panel_head_t& t : B.wr->panel_heads) ok = ok && (t.pattern < 0 || t.text_end >= 0);
     return ok;
+}
+
+// The one read-back of a panel run: every text's quicked_panel_hit_t, in the order of the pairs, the best member's score as the
+// text's score, the block steps of both passes into counter 0, and -- QUICKED_PANEL_MATRIX -- every {d, text_end}
+static void fetch_panel(quicked_batch& B, Context& C, const PanelOut& PO, size_t members) {
+    const size_t n = (size_t)B.n, nk = n * members;
+    std::vector<u32> adv, adv2;
+    {
+        FetchBatch fb(C);
+        fb.add_bytes(B.wr->panel_hits.data(), PO.d_hits, n * sizeof(quicked_panel_hit_t));
+        fb.add(adv, (const u32*)PO.d_adv, PO.text.size());
+        if (PO.d_adv2) fb.add(adv2, (const u32*)PO.d_adv2, PO.text.size());
+        if (PO.d_mscore) { fb.add_bytes(B.wr->panel_score.data(), PO.d_mscore, nk * sizeof(int32_t)); fb.add_bytes(B.wr->panel_end.data(), PO.d_mend, nk * sizeof(int32_t)); }
+        fb.sync();
+    }
+    B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
+    for (const int32_t pr : PO.text) if (pr >= 0) { B.wr->score[pr] = B.wr->panel_hits[(size_t)pr].score; B.wr->status[pr] = QUICKED_OK; }
 }
 
 quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fetch, const BoundedRun* bd, const SearchRun* sr) {
@@ -881,9 +938,13 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     B.run_tags = (fetch && !p.only_score) ? B.tags : 0;      // alignment tags: sync != 0 runs that align (quicked_batch.h)
     using Kind = quicked_batch::SearchKind;
     const Kind kind = !sr ? Kind::None : sr->panel ? (sr->max_hits > 0 ? Kind::PanelAll : Kind::Panel) : (sr->max_hits > 0 ? Kind::All : Kind::Best);
-    B.search_kind = kind;
-    B.panel_members = kind == Kind::Panel ? sr->panel->n_patterns : 0;
-    B.panel_matrix = kind == Kind::Panel && sr->panel->matrix;
+    // (a queued panel run leaves what kind the last run was to its fetch, like every result: fetch_pending)
+    const bool queued_panel = !fetch && sr && sr->panel;
+    if (!queued_panel) {
+        B.search_kind = kind;
+        B.panel_members = kind == Kind::Panel ? sr->panel->n_patterns : 0;
+        B.panel_matrix = kind == Kind::Panel && sr->panel->matrix;
+    }
     // sync == 0 leaves the host-side results of the last fetched run untouched (quicked_batch_fetch brings this run's)
     B.pending_fetch.reset();
     B.shadow_ready = false;                    // an early finish of the previous queued run is superseded
@@ -941,35 +1002,33 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     QE_TRACE_POINT("task list");
     bool no_search_task = true;
     for (const TaskList& l : SLs.L) no_search_task = no_search_task && l.pair.empty();
-    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task && no_panel_task) { C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u(); return QUICKED_EMPTY_SEQUENCE; }
+    if (L.pair.empty() && Ld.pair.empty() && Lg.pair.empty() && beyond.empty() && no_search_task && no_panel_task) {
+        C.staging = false; HIP_CHECK(hipStreamSynchronize(C.stream)); C.phase_u();
+        // (a queued panel run without a text: the fetch still shows what the sync run leaves, the getters of its kind at "none")
+        if (queued_panel) { pf->kind = kind == Kind::Panel ? 3 : 4; pf->panel_members = sr->panel->n_patterns; pf->no_text = true; B.pending_fetch = pfp; }
+        return QUICKED_EMPTY_SEQUENCE;
+    }
     StageResult R;
 
     if (sr && sr->panel && sr->max_hits > 0) {
-        // All-occurrences panel run (sync only): found / smallest score / offsets per text and the stored occurrences, already in
-        // the order of the texts and (pattern, text_end) within a text, in one read-back
+        // All-occurrences panel run: found / smallest score / offsets per text and the stored occurrences, already in the order
+        // of the texts and (pattern, text_end) within a text, in one read-back -- at the run's end, or, queued on a batch
+        // configured for it, in its fetch (pending-fetch kind 4)
         enter_a();
         // (window >= 0: the same results from window slots, quicked_batch_run_panel_scan)
         // (with QUICKED_PANEL_CIGARS: the getters of the strings answer after this run, whether or not it stored an occurrence)
-        B.wr->panel_cigars = sr->cigars;
-        const bool aligned = fetch_hits(B, C, sr->window >= 0 ? run_search_panel_scan(B, C, *sr) : run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
-        ret = aligned ? QUICKED_OK : QUICKED_ERROR;
-    } else if (sr && sr->panel) {
-        // Panel run (sync only): one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX -- every
-        // {d, text_end}, in one read-back
-        enter_a();
-        const PanelOut PO = run_search_panel(B, C, *sr);
-        const size_t n = (size_t)B.n, nk = n * (size_t)sr->panel->n_patterns;
-        std::vector<u32> adv, adv2;
-        {
-            FetchBatch fb(C);
-            fb.add_bytes(B.wr->panel_hits.data(), PO.d_hits, n * sizeof(quicked_panel_hit_t));
-            fb.add(adv, (const u32*)PO.d_adv, PO.text.size());
-            if (PO.d_adv2) fb.add(adv2, (const u32*)PO.d_adv2, PO.text.size());
-            if (PO.d_mscore) { fb.add_bytes(B.wr->panel_score.data(), PO.d_mscore, nk * sizeof(int32_t)); fb.add_bytes(B.wr->panel_end.data(), PO.d_mend, nk * sizeof(int32_t)); }
-            fb.sync();
+        if (pf) { pf->kind = 4; pf->HO = std::make_shared<HitsOut>(run_search_panel_hits(B, C, *sr)); ret = QUICKED_OK; }      // (never the scan, never with strings)
+        else {
+            B.wr->panel_cigars = sr->cigars;
+            const bool aligned = fetch_hits(B, C, sr->window >= 0 ? run_search_panel_scan(B, C, *sr) : run_search_panel_hits(B, C, *sr), B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
+            ret = aligned ? QUICKED_OK : QUICKED_ERROR;
         }
-        B.counters[0] = (int64_t)(sum_u32(adv) + sum_u32(adv2));
-        for (const int32_t pr : PO.text) if (pr >= 0) { B.wr->score[pr] = B.wr->panel_hits[(size_t)pr].score; B.wr->status[pr] = QUICKED_OK; }
+    } else if (sr && sr->panel) {
+        // Panel run: one quicked_panel_hit_t per text, in the order of the pairs, and -- QUICKED_PANEL_MATRIX, sync only -- every
+        // {d, text_end}, in one read-back at the run's end or, queued, in its fetch (pending-fetch kind 3)
+        enter_a();
+        if (pf) { pf->kind = 3; pf->PO = std::make_shared<PanelOut>(run_search_panel(B, C, *sr)); }
+        else fetch_panel(B, C, run_search_panel(B, C, *sr), (size_t)sr->panel->n_patterns);
         ret = QUICKED_OK;
     } else if (sr && sr->max_hits > 0) {
         // All-occurrences run (sync only): found / smallest score / offsets per pair and the stored occurrences, already in the
@@ -1169,6 +1228,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
     B.ev_done_set[par] = true;
     if (pf && pf->kind != 0) {
         pf->parity = par;
+        if (queued_panel) pf->panel_members = sr->panel->n_patterns;
         for (int q = 0; q < 8; ++q) pf->counters[q] = B.counters[q];
         B.pending_fetch = pfp;
         B.fin_status = QUICKED_OK;
@@ -1204,11 +1264,15 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
     std::shared_ptr<void> hold = B.pending_fetch;
     PendingFetch& F = *static_cast<PendingFetch*>(hold.get());
     B.pending_fetch.reset();
-    HIP_CHECK(B.done_sync(F.parity));
+    if (!F.no_text) HIP_CHECK(B.done_sync(F.parity));
     C.phase_u();
-    B.search_kind = F.search ? quicked_batch::SearchKind::Best : quicked_batch::SearchKind::None;      // (all-occurrences and panel runs are never queued)
+    using Kind = quicked_batch::SearchKind;
+    B.search_kind = F.kind == 3 ? Kind::Panel : F.kind == 4 ? Kind::PanelAll : F.search ? Kind::Best : Kind::None;      // (all-occurrences runs of pairs are never queued)
+    B.panel_members = F.kind == 3 ? F.panel_members : 0;
+    B.panel_matrix = false;                    // (nor is QUICKED_PANEL_MATRIX)
     reset_host_results(B);
     for (int q = 0; q < 8; ++q) B.counters[q] = F.counters[q];
+    if (F.no_text) { if (F.kind == 4) B.wr->panel_queue_wanted = 0; fetch_finalize(B, false); return QUICKED_OK; }      // (nothing ran: every counter 0)
     if (F.kind == 1) {
         const size_t nt = F.task_pair.size();
         std::vector<int32_t> sc, ab, ts, te; std::vector<u32> w; std::vector<unsigned long long> nar;
@@ -1240,6 +1304,12 @@ static quicked_status_t fetch_pending(quicked_batch& B, FastLeft* left = nullptr
         }
         B.counters[F.counter_slot] += (int64_t)sum_u32(w);
         for (int32_t x : ab) B.counters[6] += (x != 0);
+    } else if (F.kind == 3) {
+        fetch_panel(B, C, *F.PO, (size_t)F.panel_members);
+    } else if (F.kind == 4) {
+        const bool found_all = fetch_hits(B, C, *F.HO, B.wr->panel_found, B.wr->panel_occ_off, B.wr->panel_occ);
+        fetch_finalize(B, false);
+        return found_all ? QUICKED_OK : QUICKED_ERROR;
     } else {
         if (F.d_leaf_adv) {
             const size_t nt = F.leaf_pair.size();

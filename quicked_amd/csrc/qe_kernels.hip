@@ -1719,6 +1719,20 @@ __global__ __launch_bounds__(256) void k_panel_hits_finish(int64_t total, const 
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j < total) panel_hits_finish_one(j, o_start, hits);
 }
+// the three steps of the queued run behind the offset scan (qe_panel.h: the total stays on the device): the expand step below
+// `cap`, the finish step below min(*total, cap), the offsets' clamp
+__global__ __launch_bounds__(256) void k_panel_queue_expand(PanelHitsExpandArgs A, int64_t cap) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < A.nslots) panel_queue_expand_slot(A, t, cap);
+}
+__global__ __launch_bounds__(256) void k_panel_queue_finish(const int64_t* __restrict__ total, int64_t cap, const int32_t* __restrict__ o_start, int32_t* __restrict__ hits) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < cap) panel_queue_finish_one(j, total, cap, o_start, hits);
+}
+__global__ __launch_bounds__(256) void k_panel_queue_clamp(int64_t n, int64_t cap, int64_t* __restrict__ off, int64_t* __restrict__ q) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i <= n) panel_queue_clamp_one(i, n, cap, off, q);
+}
 
 // A member cut off by the text's end (qe_panel.h; QUICKED_PANEL_TAILS): k_panel_hits -- its grid, slots,
 // slices, scan and stores, through the argument block it takes -- and, after every member's walk of the text, the walk down

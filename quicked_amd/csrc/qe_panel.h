@@ -279,7 +279,9 @@ QE_S_HD void panel_hits_count_slot(const PanelHitsCountArgs& A, int t) {
     A.found[pair] = found; A.best[pair] = best; A.len[pair] = stored - 1;
     A.o_adv[t] = steps;
 }
-QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) {
+// CAPPED (a queued run, panel_queue_expand_slot below): nothing is written at an index >= cap
+template <bool CAPPED>
+QE_S_HD void panel_hits_expand_slot_of(const PanelHitsExpandArgs& A, int t, int64_t cap) {
     const int pair = A.text[t];
     if (pair < 0) return;
     const int64_t stride = (int64_t)A.nslices * A.nslots;
@@ -290,6 +292,7 @@ QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) {
         const int32_t have = A.part[(int64_t)s * A.nslots + t + stride];
         const PanelRawHit* raw = A.raw + ((int64_t)s * A.nslots + t) * A.max_hits;
         for (int i = 0; i < have && left > 0; ++i, ++j, --left) {
+            if (CAPPED && j >= cap) return;
             const PanelRawHit h = raw[i];
             int32_t* o = A.hits + 4 * j;
             int32_t start = 0;
@@ -305,9 +308,31 @@ QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) {
         }
     }
 }
+QE_S_HD void panel_hits_expand_slot(const PanelHitsExpandArgs& A, int t) { panel_hits_expand_slot_of<false>(A, t, 0); }
 // k_panel_hits_finish's occurrence j: the start pass's o_start is relative to the occurrence's window
 QE_S_HD void panel_hits_finish_one(int64_t j, const int32_t* o_start, int32_t* hits) {
     hits[4 * j + 1] = o_start[j] < 0 ? -1 : hits[4 * j + 1] + o_start[j];
+}
+
+// ---- the same run queued (quicked_batch_configure_panel_queue): no host read between the passes, so the
+// arrays the total W = off[n] sizes in the sync run are taken at cap = min(max_total, texts x max_hits) instead, and every step
+// behind the offset scan keeps below cap on its own.  The records are in the order of the pairs, so what fits is the first
+// min(W, cap) of the sync run's array whatever the slots' order is.
+// k_panel_queue_expand's slot: panel_hits_expand_slot, writing records and start-pass tasks at indices < cap only.  The pass
+// then runs over cap task slots whose o_pair was preset to -1: a lane that was never written does nothing.
+QE_S_HD void panel_queue_expand_slot(const PanelHitsExpandArgs& A, int t, int64_t cap) { panel_hits_expand_slot_of<true>(A, t, cap); }
+// k_panel_queue_finish's occurrence j of cap: panel_hits_finish_one below min(*total, cap), the total read on the device
+QE_S_HD void panel_queue_finish_one(int64_t j, const int64_t* total, int64_t cap, const int32_t* o_start, int32_t* hits) {
+    const int64_t stored = *total < cap ? *total : cap;
+    if (j < stored) panel_hits_finish_one(j, o_start, hits);
+}
+// k_panel_queue_clamp's element i of 0 .. n: off[i] = min(off[i], cap) -- stored'[i] = off'[i + 1] - off'[i] follows --, and
+// element n keeps what the fetch wants beside it: q[0] = W, q[1] / q[2] = the bytes of the stored records / of their step
+// counts, for the copies to their real length (k_copy_total)
+QE_S_HD void panel_queue_clamp_one(int64_t i, int64_t n, int64_t cap, int64_t* off, int64_t* q) {
+    const int64_t v = off[i], c = v < cap ? v : cap;
+    if (i == n) { q[0] = v; q[1] = c * 16; q[2] = c * 4; }
+    off[i] = c;
 }
 
 // ---- a member cut off by the text's end: 3' tails (QUICKED_PANEL_TAILS on quicked_batch_run_panel_all)

@@ -652,8 +652,10 @@ static_assert(sizeof(TagStats) == sizeof(quicked_pair_stats_t) && sizeof(TagStat
 
 // Results of a sync == 0 run, still on the device: what quicked_batch_fetch() copies once the run is over.  The device
 // pointers are those of the batch's result arena (stash_results): valid until the batch's next run, reload or destroy.
+struct PanelOut; struct HitsOut;              // (the panel runners', below)
 struct PendingFetch {
-    int kind = 0;                             // 1: one score per task (score-only BandEd / WindowEd); 2: alignments (segments)
+    int kind = 0;                             // 1: one score per task (score-only BandEd / WindowEd); 2: alignments (segments);
+                                              // 3: a panel run; 4: an all-occurrences panel run (below)
     quicked_status_t ok_status = QUICKED_WIP;
     bool want_strings = false;
     // kind 1
@@ -676,6 +678,10 @@ struct PendingFetch {
     std::vector<int32_t> pair_bound;          // bounded runs: every pair's bound (the fetch thresholds the pairs it hands to the QuickEd flow)
     bool search = false;                      // a search run (kind 1): locations per task next to the scores
     const int32_t* d_start = nullptr; const int32_t* d_end = nullptr;
+    // kind 3: a panel run (PO), kind 4: an all-occurrences panel run (HO), queued on a batch configured for it
+    // (quicked_batch_configure_panel_queue).  The getters show the run, and what kind it was, only once it is fetched: the
+    // kind travels here.  no_text: every text is empty, nothing was launched
+    std::shared_ptr<PanelOut> PO; std::shared_ptr<HitsOut> HO; int32_t panel_members = 0; bool no_text = false;
 };
 
 // One wavefront per alignment (k_banded_wave) is for few, long alignments: up to ~1000 tasks every task gets a wave of its
@@ -1133,6 +1139,9 @@ struct HitsOut {                                   // of both all-occurrences ru
     // QUICKED_PANEL_HEADS (run_panel_heads): every pair's quicked_panel_head_t (-1 in every field: none) and, per slot, the
     // block steps of the head sweep | the row steps of its walk (2 x task_pair.size() of them)
     int32_t* d_heads = nullptr; u32* d_head_steps = nullptr;
+    // a queued panel run (quicked_batch_configure_panel_queue): total = -1 -- the fetch takes it from the offsets --, the records'
+    // room, and {W, the records' bytes, the step counts' bytes} on the device (k_panel_queue_clamp)
+    int64_t cap = 0; int64_t* d_queue = nullptr;
 };
 // The per-pair arrays of an all-occurrences run -- found (0) | smallest score (-1) | stored - 1 (-1: the scan then counts 0) --,
 // the offsets and `nadv` step counters.  -> the stored counts, for the forward pass to fill
@@ -1148,10 +1157,14 @@ static int32_t* hits_arrays(Context& C, HitsOut& O, size_t n, size_t nadv) {
 }
 // ... and behind the forward pass the offsets in the order of the pairs (every pair counts: d_seq_len, lengths that are never
 // negative, stands in for the scan's list of tasks) with the total behind them -- the one thing the host reads in between
-static void hits_total(const quicked_batch& B, Context& C, HitsOut& O, const int32_t* d_len, const int32_t* d_seq_len) {
+static void hits_offsets(const quicked_batch& B, Context& C, HitsOut& O, const int32_t* d_len, const int32_t* d_seq_len) {
     const size_t n = (size_t)B.n;
     hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, C.stream, d_len, d_seq_len, O.d_off, O.d_off + n, (int)n);
     HIP_CHECK(hipGetLastError());
+}
+static void hits_total(const quicked_batch& B, Context& C, HitsOut& O, const int32_t* d_len, const int32_t* d_seq_len) {
+    const size_t n = (size_t)B.n;
+    hits_offsets(B, C, O, d_len, d_seq_len);
     std::vector<int64_t> tot;
     FetchBatch fb(C);
     fb.add(tot, (const int64_t*)(O.d_off + n), 1);
@@ -1667,6 +1680,10 @@ static void run_panel_heads(quicked_batch& B, Context& C, const SearchRun& sr, c
 // their places and, INFIX, writes one start-pass task per occurrence; the pass is the unchanged k_search<4, Eq> in its
 // start-pass form with task j's pair = j and two arrays of `total` plane offsets (the member's into the reversed panel planes,
 // the text's); k_panel_hits_finish adds its o_start.  Both passes are timed as kind 0.
+// A queued run (SearchRun::queue_total) reads nothing in between: the total stays at d_off[n], the arrays it
+// sizes are taken at panel_queue_cap, k_panel_queue_expand writes below that cap only, the start pass runs over cap task slots
+// whose pair was preset to -1, k_panel_queue_finish takes min(total, cap) from the device and k_panel_queue_clamp clamps the
+// offsets, with the total the run wanted beside them.
 //
 // The raw buffer is nslices x nslots x max_hits records of 12 bytes: the slice count is lowered until that fits
 // QE_PANEL_HITS_RAW_KB (1 GiB unset; one slice always fits it under the 2^26 rule of the entry point).
@@ -1676,15 +1693,23 @@ static int panel_hits_slices(const Context& C, size_t nslots, int K, int max_hit
     const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(1, per_slice_bytes));
     return (int)std::min<size_t>((size_t)panel_slices(C, nslots / 64, K), fit);
 }
+// the room a queued run takes for its records: min(max_total, non-empty texts x max_hits) -- no run stores more than the latter
+static int64_t panel_queue_cap(const quicked_batch& B, const SearchRun& sr) {
+    int64_t texts = 0;
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    return std::min<int64_t>(sr.queue_total, texts * (int64_t)sr.max_hits);
+}
 // what such a run takes from its pool before the total is known (the planner's fixed needs): panel_shared_bytes, the slice
 // partials and the raw buffer at the slices the host would choose, the per-pair arrays.  The arrays sized by the total (16
 // bytes per stored occurrence, 60 with the start pass) are not known before the run and are not planned, as in an
-// all-occurrences search run
+// all-occurrences search run; a queued run takes them at its cap, which is known, and they are planned
 static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, const SearchRun& sr) {
     size_t nslots = 0, b = panel_shared_bytes(B, sr, nslots);
     const size_t n = (size_t)B.n, nslices = (size_t)panel_hits_slices(C, nslots, sr.panel->n_patterns, sr.max_hits);
     b += nslices * nslots * (4 * sizeof(int32_t) + (size_t)sr.max_hits * sizeof(PanelRawHit));
     b += nslots * 8 + n * 12 + (n + 1) * 8;
+    // (a queued run takes them at its cap, which is known: panel_queue_cap)
+    if (sr.queue_total > 0) b += (size_t)panel_queue_cap(B, sr) * (sr.mode == SEARCH_INFIX ? 60 : 16) + 8 * 512;
     return b + panel_align_fixed_bytes(B, sr) + panel_tails_fixed_bytes(B, sr, nslots, nslices) + panel_heads_fixed_bytes(B, sr, nslots, nslices);
 }
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
@@ -1740,9 +1765,12 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
     if (sr.tails) run_panel_tails(B, C, sr, D, ta, nslices, text_planes_reversed(), O);      // (before the total: it needs none)
     if (sr.heads) run_panel_heads(B, C, sr, D, a, nslices, panel_planes_reversed(), O);      // (likewise; no reversed text planes)
-    hits_total(B, C, O, d_plen, B.d_t_len);
-    if (O.total <= 0) return O;
-    const size_t nh = (size_t)O.total;
+    // (a queued run: the total stays on the device and the arrays it sizes are taken at the run's cap instead)
+    const bool queued = sr.queue_total > 0;
+    if (queued) { hits_offsets(B, C, O, d_plen, B.d_t_len); O.total = -1; O.cap = panel_queue_cap(B, sr); }
+    else hits_total(B, C, O, d_plen, B.d_t_len);
+    if (!queued && O.total <= 0) return O;
+    const size_t nh = (size_t)(queued ? O.cap : O.total);
     O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
     PanelHitsExpandArgs e{};
     e.nslots = (int32_t)nslots; e.nslices = nslices; e.max_hits = max_hits; e.infix = infix ? 1 : 0;
@@ -1753,12 +1781,14 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         int32_t* q = C.scratch_p->take<int32_t>(6 * nh);
         e.o_pair = q; e.o_m = q + nh; e.o_n = q + 2 * nh; e.o_score = q + 3 * nh; e.o_end = q + 4 * nh; o_start = q + 5 * nh;
         HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
+        if (queued) HIP_CHECK(hipMemsetAsync(e.o_pair, 0xFF, nh * sizeof(int32_t), C.stream));      // the task slots past the total: no pair, so no lane
         e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
         e.o_plt_off = e.o_plp_off + nh;
         O.d_adv2 = C.scratch_p->take<u32>(nh);
         HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
     }
-    hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
+    if (queued) hipLaunchKernelGGL(k_panel_queue_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e, (int64_t)O.cap);
+    else hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
     HIP_CHECK(hipGetLastError());
     if (infix) {
         // ---- the start pass: one lane per stored occurrence over its window, reversed
@@ -1767,7 +1797,14 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         PV.pl_p = panel_planes_reversed(); PV.pl_p_off = e.o_plp_off;
         PV.pl_t = text_planes_reversed(); PV.pl_t_off = e.o_plt_off;
         launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
-        hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
+        if (queued) hipLaunchKernelGGL(k_panel_queue_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (const int64_t*)(O.d_off + (size_t)B.n), (int64_t)O.cap, (const int32_t*)o_start, O.d_hits);
+        else hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (queued) {
+        // ---- the offsets clamped to the cap, W and the real lengths of the records and their step counts beside them
+        O.d_queue = C.scratch_p->take<int64_t>(4);
+        hipLaunchKernelGGL(k_panel_queue_clamp, dim3((unsigned)(((size_t)B.n + 256) / 256)), dim3(256), 0, C.stream, (int64_t)B.n, (int64_t)O.cap, O.d_off, O.d_queue);
         HIP_CHECK(hipGetLastError());
     }
     if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
@@ -2251,6 +2288,7 @@ static void reset_host_results(quicked_batch& B) {
     B.wr->panel_cigars = false; B.wr->panel_cig_off.clear(); B.wr->panel_cig_pool.clear();
     B.wr->panel_tails.clear();
     B.wr->panel_heads.clear();
+    B.wr->panel_queue_wanted = -1;
     B.wr->deferred_pairs = 0;
 }
 
