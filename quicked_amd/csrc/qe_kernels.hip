@@ -490,12 +490,101 @@ __device__ __forceinline__ void run64_tall(u64 (&P)[K], u64 (&M)[K], const u64 (
     houtM = mk64(oMlo, oMhi);
 }
 
+// Eq from a table (qe_types.h: peq_*; DESIGN.md 4.1, "Eq from a table").  E = the wave's table + lane: entry (sym, k) of this
+// lane at E[(sym * peq_sym_stride() + k * peq_slot_stride()) / 8].  peq_build writes the four entries of every slot of a pass
+// (a = b = 0 for a dead slot: defined values, which the score identity of slots_pass takes like any other Eq).
+template <int K>
+__device__ __forceinline__ void peq_build(u64* E, const u64 (&a)[K], const u64 (&b)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int sym = 0; sym < 4; ++sym) E[(sym * peq_sym_stride() + k * peq_slot_stride()) / 8] = peq_entry(a[k], b[k], sym);
+    }
+}
+// run64_tall with Eq read from that table instead of computed from the planes: per column the lane's row of the table from
+// bit c of T0 / T1, per slot one ds_read_b64 at the slot's immediate offset.  PF: the reads of the NEXT column pair are issued
+// before the current pair computes (the loop is unrolled by two pairs so that the two sets of registers swap without moves;
+// the pair after a half's last wraps to its first: a read of the lane's own rows, not used); PF = 0 reads the pair at the
+// top of its own iteration.  Everything after Eq is run64_tall's, hence the same bits.
+template <int K, int PF>
+__device__ __forceinline__ void run64_tall_peq(u64 (&P)[K], u64 (&M)[K], const u64* E, u64 T0, u64 T1, u64 hinP, u64 hinM, u64& houtP, u64& houtM) {
+    u32 Plo[K], Phi[K], Mlo[K], Mhi[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { Plo[k] = lo32(P[k]); Phi[k] = hi32(P[k]); Mlo[k] = lo32(M[k]); Mhi[k] = hi32(M[k]); }
+    u32 oPlo = 0, oPhi = 0, oMlo = 0, oMhi = 0;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+        const u32 t0 = half ? hi32(T0) : lo32(T0), t1 = half ? hi32(T1) : lo32(T1);
+        const u32 hp = half ? hi32(hinP) : lo32(hinP), hm = half ? hi32(hinM) : lo32(hinM);
+        u32 gP = 0, gM = 0;
+        auto read_pair = [&](u64 (&e)[2][K], int c) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const u32 sym = __builtin_amdgcn_ubfe(t0, (u32)(c + j), 1u) + 2u * __builtin_amdgcn_ubfe(t1, (u32)(c + j), 1u);
+                const u64* row = E + sym * (u32)(peq_sym_stride() / 8);
+#pragma unroll
+                for (int k = 0; k < K; ++k) e[j][k] = row[k * (peq_slot_stride() / 8)];
+            }
+        };
+        u64 e[2][K];
+        if (PF) read_pair(e, 0);
+        constexpr int PAIRS = PF ? 2 : 1;                // column pairs per unrolled iteration
+#pragma unroll PAIRS
+        for (int c = 0; c < 32; c += 2) {
+            u64 nx[2][K];
+            if (PF) read_pair(nx, (c + 2) & 31);
+            else read_pair(e, c);
+            u32 cP[2], cM[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                cP[j] = __builtin_amdgcn_ubfe(hp, (u32)(c + j), 1u);
+                cM[j] = __builtin_amdgcn_ubfe(hm, (u32)(c + j), 1u);
+            }
+#pragma unroll
+            for (int s = 0; s <= K; ++s) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {            // column c + j at slot s - j; the lowest slot collects c before c + 1
+                    const int k = s - j;
+                    if (k < 0 || k >= K) continue;
+                    const u32 elo = lo32(e[j][k]), ehi = hi32(e[j][k]);
+                    if (k + 1 < K) {
+                        u32 phhi, mhhi;
+                        block_step_core(elo, ehi, Plo[k], Phi[k], Mlo[k], Mhi[k], cP[j], cM[j], phhi, mhhi);
+                        cP[j] = phhi >> 31; cM[j] = mhhi >> 31;
+                    } else {
+                        block_step_collect(elo, ehi, Plo[k], Phi[k], Mlo[k], Mhi[k], cP[j], cM[j], gP, gM);
+                    }
+                }
+            }
+            if (PF) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) e[j][k] = nx[j][k];
+                }
+            }
+        }
+        const u32 rP = __builtin_bitreverse32(gP), rM = __builtin_bitreverse32(gM);
+        if (half) { oPhi = rP; oMhi = rM; } else { oPlo = rP; oMlo = rM; }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) { P[k] = mk64(Plo[k], Phi[k]); M[k] = mk64(Mlo[k], Mhi[k]); }
+    houtP = mk64(oPlo, oPhi);
+    houtM = mk64(oMlo, oMhi);
+}
+
 // slots_pass around a tall pass, k_banded<false, true>'s layout (64 lanes per row, scores[] the ring): every read of the
 // pass -- Pv, Mv, scores[] and the pattern planes of all live slots -- is issued before the first block step; the planes as
 // raw words, shifted afterwards (`unaligned`, wave-uniform: some lane's pattern starts inside a word), so that no load
 // waits inside a branch.  Stores and the scores chain as in slots_pass.
-template <int K>
-__device__ __forceinline__ void slots_pass_tall(int nl, int i, int r, u64* Pv, u64* Mv, int32_t* S, const u64* pp, int p0, bool unaligned,
+// RING = false: scores[] by absolute block row (the group workspace).  PEQ: the table form -- the planes go into the wave's Eq
+// table E (peq_build) and the pass reads Eq from it (run64_tall_peq); a and b are dead from there on.
+#ifndef QE_PEQ_PREFETCH
+#define QE_PEQ_PREFETCH 0    // run64_tall_peq's PF: 0 the pair's reads at the top of its iteration, 1 the next pair's in flight (measured no faster,
+                             // profiles/score_peq.md section 2, and at K = 10 it spills)
+#endif
+template <int K, bool RING = true, bool PEQ = false>
+__device__ __forceinline__ void slots_pass_tall(int nl, int i, int r, u64* Pv, u64* Mv, int32_t* S, u64* E, const u64* pp, int p0, bool unaligned,
                                                 u64 T0, u64 T1, u64& hinP, u64& hinM, u32& adv) {
     u64 P[K], M[K], a[K], b[K], a1[K], b1[K];
     int sc[K], v0[K];
@@ -504,7 +593,7 @@ __device__ __forceinline__ void slots_pass_tall(int nl, int i, int r, u64* Pv, u
     for (int k = 0; k < K; ++k) {
         P[k] = 0; M[k] = 0; a[k] = 0; b[k] = 0; a1[k] = 0; b1[k] = 0; sc[k] = 0;
         if (k < nl) {
-            P[k] = Pv[(int64_t)(i + k) * 64]; M[k] = Mv[(int64_t)(i + k) * 64]; sc[k] = S[(int64_t)score_lds_row(r + k) * 64];
+            P[k] = Pv[(int64_t)(i + k) * 64]; M[k] = Mv[(int64_t)(i + k) * 64]; sc[k] = S[(int64_t)(RING ? score_lds_row(r + k) : r + k) * 64];
             const u64* w = pp + 3 * (int64_t)((p0 >> 6) + r + k);
             a[k] = w[0]; b[k] = w[1];
             if (unaligned) { a1[k] = w[3]; b1[k] = w[4]; }
@@ -520,13 +609,16 @@ __device__ __forceinline__ void slots_pass_tall(int nl, int i, int r, u64* Pv, u
 #pragma unroll
     for (int k = 0; k < K; ++k) v0[k] = __popcll(P[k]) - __popcll(M[k]);
     u64 houtP, houtM;
-    run64_tall<K>(P, M, a, b, T0, T1, hinP, hinM, houtP, houtM);
+    if constexpr (PEQ) {
+        peq_build<K>(E, a, b);
+        run64_tall_peq<K, QE_PEQ_PREFETCH>(P, M, E, T0, T1, hinP, hinM, houtP, houtM);
+    } else run64_tall<K>(P, M, a, b, T0, T1, hinP, hinM, houtP, houtM);
     if (nl > 0) {
         int d = __popcll(houtP) - __popcll(houtM);          // sum of the bottom-row deltas of slot k, from the lowest up
 #pragma unroll
         for (int k = K - 1; k >= 0; --k) {
             if (k < nl) {
-                S[(int64_t)score_lds_row(r + k) * 64] = sc[k] + d;
+                S[(int64_t)(RING ? score_lds_row(r + k) : r + k) * 64] = sc[k] + d;
                 Pv[(int64_t)(i + k - 1) * 64] = P[k]; Mv[(int64_t)(i + k - 1) * 64] = M[k];   // band shift (bpm_banded.c:903-909)
             }
             d -= (__popcll(P[k]) - __popcll(M[k])) - v0[k];
@@ -1107,9 +1199,14 @@ __device__ __forceinline__ GroupWs group_ws(uint8_t* ws, int64_t off, int ns, in
 // live in its slice of the workgroup's LDS instead of the group workspace -- scores[] as a ring (qe_types.h: score_lds_*).
 // Same walk, same values; the kernel then has global loads only (the planes), and nothing waits behind a store.
 constexpr bool QE_K_BANDED_LDS = true;                // the LDS form below exists (the host-only build's kernels header says false)
-template <bool FILL, bool LDS = false>
+// PEQ (score-only, the same launch; DESIGN.md 4.1, "Eq from a table"): a wave's slice of the LDS holds the Eq table of its tall
+// passes (qe_types.h: peq_*) and the band state lives in the group workspace, scores[] by absolute row, as in every other
+// launch.  The 4 / 2 / 1 passes and the single-slot forms compute Eq from the planes as ever.
+#define QE_K_BANDED_PEQ 1                             // k_banded<false, false, true> exists (the host-only build's kernels header has no such form)
+template <bool FILL, bool LDS = false, bool PEQ = false>
 __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
     static_assert(!(FILL && LDS), "the fill's state stays in the group workspace");
+    static_assert(!(PEQ && (FILL || LDS)), "the table form: score-only, state in the group workspace");
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, t = g * 64 + lane;
     if (g * 64 >= A.T.ntasks) return;
     int pair = (t < A.T.ntasks) ? A.T.pair[t] : -1;
@@ -1156,6 +1253,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
     u64* const Pv = W.Pv + 64 + lane;        // slot s lives at Pv[s * 64]; slot -1 is addressable
     u64* const Mv = W.Mv + 64 + lane;
     int32_t* const S = W.S + lane;           // scores[] indexed by absolute block row (bpm_banded.c:180-197), LDS: by srow() of it
+    u64* const E = PEQ ? (u64*)((uint8_t*)qe_dyn_lds + (size_t)QE_WAVE_IN_BLOCK() * (size_t)peq_bytes()) + lane : nullptr;      // this wave's Eq table
     auto srow = [](int r) { return (int64_t)(LDS ? score_lds_row(r) : r) * 64; };
     // fill: per group  cp[QE_CPC nch][ns][64] = {Pv, Mv} after every QE_CP_COLS-th stored column (in the slot numbering of the
     // chunk that starts at / contains it), then  hw[nch][ns][64] = the carry-in words of every (chunk, slot)
@@ -1230,17 +1328,17 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
                 if (i == first) { hinP = QE_ONES; hinM = 0; }
                 // score_pass_height: in the LDS form one pass at the height of the chunk's walk (tall_height; a taller walk: its
                 // head) where no lane needs the general form or starts inside it; otherwise, and for what is left, 4 or 2 slots
-                const int K = __builtin_amdgcn_readfirstlane(score_pass_height(x, i0, i1, LDS && A.score_tall, planned));
+                const int K = __builtin_amdgcn_readfirstlane(score_pass_height(x, i0, i1, (LDS || PEQ) && A.score_tall, planned));
                 switch (K) {
                 case 0: break;
                 case 2: slots_pass<2, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); break;
                 case 4: slots_pass<4, LDS>(nl, i, r, Pv, Mv, S, S, 64, pp, p0, T0, T1, hinP, hinM, adv); break;
-                case 5: if constexpr (LDS) slots_pass_tall<5>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                case 6: if constexpr (LDS) slots_pass_tall<6>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                case 7: if constexpr (LDS) slots_pass_tall<7>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                case 8: if constexpr (LDS) slots_pass_tall<8>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                case 9: if constexpr (LDS) slots_pass_tall<9>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
-                default: if constexpr (LDS) slots_pass_tall<10>(nl, i, r, Pv, Mv, S, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 5: if constexpr (LDS || PEQ) slots_pass_tall<5, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 6: if constexpr (LDS || PEQ) slots_pass_tall<6, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 7: if constexpr (LDS || PEQ) slots_pass_tall<7, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 8: if constexpr (LDS || PEQ) slots_pass_tall<8, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                case 9: if constexpr (LDS || PEQ) slots_pass_tall<9, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
+                default: if constexpr (LDS || PEQ) slots_pass_tall<10, LDS, PEQ>(nl, i, r, Pv, Mv, S, E, pp, p0, unaligned, T0, T1, hinP, hinM, adv); break;
                 }
                 if (K) { x += K - 1; continue; }
             }
@@ -1378,6 +1476,7 @@ __global__ __launch_bounds__(512) void k_banded(BandedArgs A) {
 template __global__ void k_banded<false>(BandedArgs);
 template __global__ void k_banded<true>(BandedArgs);
 template __global__ void k_banded<false, true>(BandedArgs);
+template __global__ void k_banded<false, false, true>(BandedArgs);
 
 // ===========================================================================
 // Bounded edit distance, diagonal-word form (qe_bounded.h): one lane per pair, score only, for tasks whose Ukkonen band

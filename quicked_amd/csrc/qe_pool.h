@@ -89,7 +89,7 @@ inline const Chip& chip(int device) {
 enum class Sw : int {
     QuickedFast, QuickedEst, QuickedScorePass, FinishMerge, FinishMergePairs, Finishers, LaneRel, CoopG, CoopFillG, CoopLds,
     CoopTallFill, Wave, ScoreSys, Stage3Device, FormatWave, WindowedCp, WindowedQuad, WindowedSys, SplitBytes, FillSys, FillMulti,
-    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, ScoreLds, ScoreTall, TagsWave, SearchForm, SearchHitsWsKb, PanelSlices, PanelHitsRawKb, PanelAlignWsKb, Count
+    TraceSys, Trace, TracePool, OomWaitMs, BoundedDiag, ScoreNarrow, NarrowFit, NarrowPrune, ScoreMasked, ScoreLds, ScoreTall, ScorePeq, TagsWave, SearchForm, SearchHitsWsKb, PanelSlices, PanelHitsRawKb, PanelAlignWsKb, Count
 };
 struct SwitchDef { Sw sw; const char* name; long long dflt; };
 inline constexpr SwitchDef switch_defs[] = {
@@ -113,6 +113,7 @@ inline constexpr SwitchDef switch_defs[] = {
     {Sw::ScoreMasked, "QE_SCORE_MASKED", 1},           // k_banded<false>'s multi-slot passes: 1 every lane with the slots of the pass inside its band (pass_plan), 0 with all of them or none (the rule before it, pass for pass)
     {Sw::ScoreLds, "QE_SCORE_LDS", -1},                // the first launch of a two-pass BandEd score-only run: -1 band state in LDS where every band of the launch fits a wave's slice and the list has a group per SIMD (score_lds_slots), 0 never (the group workspace, as every other launch), 1 wherever the bands fit, at any list size (tests)
     {Sw::ScoreTall, "QE_SCORE_TALL", -1},              // ... in LDS: -1 one pass of 5 .. 10 slots at the head of every chunk where the plan allows it (tall_height, pass_plan), 0 never (the 4 / 2 / 1 passes, pass for pass), 1 as -1 (tests)
+    {Sw::ScorePeq, "QE_SCORE_PEQ", -1},                // ... its tall passes: -1 Eq read from a per-lane table in LDS, the band state in the group workspace instead (score_peq), wherever the launch would by default take the LDS form with tall passes; 0 never (the launch as it was, instruction for instruction); 1 wherever a tall pass can run, at any list size and band height (tests).  A forced QE_SCORE_LDS = 1 still means the band state in LDS and therefore the form without the table; QE_SCORE_TALL = 0 leaves no pass that would read one
     {Sw::TagsWave, "QE_TAGS_WAVE", -1},                // alignment tags (quicked_batch_configure_tags): -1 the wave form where the CIGAR formatter takes its own (tags_wave_wanted), 0 / 1 the lane / wave form everywhere (tests)
     {Sw::SearchForm, "QE_SEARCH_FORM", -1},            // search runs (quicked_batch_run_search): -1 the library's choice (search_reg_form: the workspace form), 0 the workspace form always, 1 the register form wherever it applies (patterns of up to 256 bases)
     {Sw::SearchHitsWsKb, "QE_SEARCH_HITS_WS_KB", 262144},      // all-occurrences runs (quicked_batch_run_search_all): KiB of workspace the start pass's workspace-form launches share; more groups than fit run in slices (tests force slices with a small value)

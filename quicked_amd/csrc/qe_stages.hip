@@ -467,6 +467,33 @@ static int score_lds_slots(const Context& C, const TaskList& L, int bound) {
     return score_lds_fits(bound) ? bound : 0;
 }
 
+// Eq from a table for the tall passes of the FIRST launch (k_banded<false, false, true>): the LDS then holds a
+// wave's Eq table (peq_bytes(): 80 KB per workgroup) and the band state goes back to the group workspace.  QE_SCORE_PEQ = -1:
+// wherever the launch would by default take the LDS form with tall passes (`tall_lds`); 0: never; 1: wherever a tall pass can
+// run, whatever the list's size and its bands (tests).  A forced QE_SCORE_LDS = 1 asks for the band state in LDS and so for the
+// form without the table, QE_SCORE_TALL = 0 leaves no pass that reads one.  The form needs two workgroups per CU like every
+// launch_groups launch: where the runtime's occupancy query does not place two of 80 KB, it is declined.
+static bool score_peq(const Context& C, const TaskList& L, bool tall_lds) {
+    (void)C; (void)L;
+#ifdef QE_K_BANDED_PEQ
+    if (!QE_K_BANDED_LDS) return false;
+    const int mode = sw(Sw::ScorePeq);
+    if (mode == 0 || sw(Sw::ScoreLds) == 1 || sw(Sw::ScoreTall) == 0) return false;
+    if (mode != 1 && !tall_lds) return false;
+    static thread_local std::vector<std::pair<int, int>> per_cu;          // per host thread and device, as launch_groups' `configured`
+    for (const auto& d : per_cu) if (d.first == tl_device) return d.second >= 2;
+    const void* fn = reinterpret_cast<const void*>(k_banded<false, false, true>);
+    int nb = 0;
+    HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, (size_t)4 * (size_t)peq_bytes()) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
+    if (trace_on()) fprintf(stderr, "[qe] table form: %d workgroups of %d B of LDS per CU\n", nb, 4 * peq_bytes());
+    per_cu.emplace_back(tl_device, nb);
+    return nb >= 2;
+#else
+    return false;
+#endif
+}
+
 static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const TaskList& L, bool reversed, int timed, const BandLayout& lay, int q, int qp, int slots1) {
     ScoreLaunch S;
     S.nt = L.pair.size();
@@ -496,7 +523,13 @@ static ScoreLaunch launch_banded_narrow(quicked_batch& B, Context& C, const Task
     a.lane_rel = sw(Sw::LaneRel);
     a.lds_slots = score_lds_slots(C, L, slots1);
     a.score_tall = (a.lds_slots && sw(Sw::ScoreTall) != 0) ? 1 : 0;      // tall passes: the LDS form only
-    if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots), tall passes %s\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots, a.score_tall ? "on" : "off");
+    const bool peq = score_peq(C, L, a.lds_slots != 0 && a.score_tall != 0);
+    if (peq) { a.lds_slots = 0; a.score_tall = 1; }                       // the table form: the LDS holds Eq, the state goes to the group workspace
+    if (trace_on()) fprintf(stderr, "[qe] two-pass score: first launch of %d groups, band state in %s (%d slots), tall passes %s%s\n", L.ngroups(), a.lds_slots ? "LDS" : "the group workspace", a.lds_slots, a.score_tall ? "on" : "off", peq ? ", Eq from a table in LDS" : "");
+#ifdef QE_K_BANDED_PEQ
+    if (peq) launch_groups(C, k_banded<false, false, true>, a, L.ngroups(), 8, (size_t)peq_bytes());
+    else
+#endif
     if (a.lds_slots) launch_groups(C, k_banded<false, true>, a, L.ngroups(), 8, (size_t)score_lds_bytes(a.lds_slots));
     else launch_groups(C, k_banded<false>, a, L.ngroups(), 8, 0);
     x.phase = 1;

@@ -117,7 +117,7 @@ struct BandedArgs {
                                   // that is not below the task's cutoff: the geometry's (clamped) cutoff, as every other launch
     int32_t lds_slots = 0;        // k_banded<false, true> only: the band slots every wave's slice of the LDS holds (score_lds_bytes(lds_slots)
                                   // per wave); the group workspace is not touched
-    int32_t score_tall = 0;       // k_banded<false, true> only: one pass of tall_height() slots at the head of every chunk (0: the 4 / 2 / 1 plan alone)
+    int32_t score_tall = 0;       // k_banded<false, true> and the table form k_banded<false, false, true> only: one pass of tall_height() slots at the head of every chunk (0: the 4 / 2 / 1 plan alone)
 };
 
 // Bounded edit distance, diagonal-word form (k_bounded_diag, qe_bounded.h): whole pairs (p0 = t0 = 0), T.cutoff = the pair's
@@ -425,6 +425,18 @@ QE_T_HD int score_lds_cap() { return score_lds_ring() - 3; }        // 13 slots:
 QE_T_HD bool score_lds_fits(int slots) { return slots >= 1 && slots <= score_lds_cap(); }
 QE_T_HD int score_lds_row(int r) { return r & (score_lds_ring() - 1); }
 QE_T_HD int score_lds_bytes(int slots) { return 2 * (slots + 1) * 64 * 8 + score_lds_ring() * 64 * 4; }      // per wave: 18 KB at the cap
+
+// Eq from a table (the table form of the fitted first launch; DESIGN.md 4.1, "Eq from a table"): a wave's slice of the LDS
+// holds E[sym][slot][lane], one u64 each -- the 64 Eq bits of that lane's pattern block row at slot `slot` of the pass for the
+// text symbol sym = t0 + 2 t1, (a == t0) & (b == t1) per bit of the two code planes.  2 KB per slot, 20 KB per wave, 80 KB per
+// workgroup of four: two workgroups share a CU's 160 KB.  The sym stride is a multiple of 256 B and lanes are 8 B apart, so
+// lane l reads bank 2 l mod 64 (and the one above it) whatever sym and slot: no ds_read_b64 of a wave meets a bank conflict.
+QE_T_HD int peq_cap() { return QE_TALL_MAX; }                                   // the slots of the tallest pass
+QE_T_HD int peq_slot_stride() { return 64 * 8; }                               // bytes
+QE_T_HD int peq_sym_stride() { return peq_cap() * peq_slot_stride(); }         // bytes
+QE_T_HD int peq_bytes() { return 4 * peq_sym_stride(); }                       // per wave
+QE_T_HD int peq_offset(int sym, int slot, int lane) { return sym * peq_sym_stride() + slot * peq_slot_stride() + lane * 8; }
+QE_T_HD u64 peq_entry(u64 a, u64 b, int sym) { return ((sym & 1) ? a : ~a) & ((sym & 2) ? b : ~b); }
 
 // k_narrow, one thread per task of the list T (whole-text passes: tfin = n).  phase 0: cut1 = narrow_cutoff of every task,
 // the packed list emptied, the statistics zeroed.  phase 1, after the first pass: a task whose cutoff was halved and whose

@@ -223,6 +223,73 @@ __global__ void k_verify(u32* bad) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The tall loop (run64_tall<8>) in its two forms: Eq from the planes, and Eq read from the per-lane LDS table of qe_types.h
+// (peq_*; run64_tall_peq, with and without the reads of the next column pair in flight).  The table is rebuilt before every
+// pass, as slots_pass_tall does, and the planes change from pass to pass in both forms so that nothing is hoisted.
+// FORM 0: planes, 1: table, next pair prefetched, 2: table, read at the top of the iteration
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int TK = 8;
+template <int FORM>
+__device__ __forceinline__ void tall_pass(u64 (&P)[TK], u64 (&M)[TK], const u64 (&a)[TK], const u64 (&b)[TK], u64* E, u64 T0, u64 T1, u64 hinP, u64 hinM,
+                                          u64& houtP, u64& houtM) {
+    if (FORM == 0) qe::run64_tall<TK>(P, M, a, b, T0, T1, hinP, hinM, houtP, houtM);
+    else {
+        qe::peq_build<TK>(E, a, b);
+        if (FORM == 1) qe::run64_tall_peq<TK, 1>(P, M, E, T0, T1, hinP, hinM, houtP, houtM);
+        else qe::run64_tall_peq<TK, 0>(P, M, E, T0, T1, hinP, hinM, houtP, houtM);
+    }
+}
+template <int FORM>
+__global__ __launch_bounds__(256) void k_tall(u32* out, Stamp* stamps, int iters) {
+    using namespace qe;
+    extern __shared__ uint4 pin[];
+    u64* const E = (u64*)((uint8_t*)pin + (size_t)(threadIdx.x >> 6) * (size_t)peq_bytes()) + (threadIdx.x & 63);
+    u64 P[TK], M[TK], a[TK], b[TK];
+    const u64 seed = (u64)(blockIdx.x * 256 + threadIdx.x) * 0x9E3779B97F4A7C15ull + 12345;
+#pragma unroll
+    for (int k = 0; k < TK; ++k) {
+        P[k] = ~(u64)0; M[k] = 0;
+        a[k] = seed * (2 * k + 3) ^ (seed >> 17); b[k] = seed * (2 * k + 5) ^ (seed >> 13);
+    }
+    u64 T0 = seed ^ 0x0123456789abcdefull, T1 = seed * 7 + 1, hinP = ~(u64)0, hinM = 0, houtP = 0, houtM = 0;
+    const uint64_t c0 = __builtin_amdgcn_s_memtime(), t0 = __builtin_amdgcn_s_memrealtime();
+    for (int i = 0; i < iters; ++i) {
+        tall_pass<FORM>(P, M, a, b, E, T0, T1, hinP, hinM, houtP, houtM);
+        T0 = T0 * 6364136223846793005ull + 1442695040888963407ull;
+        T1 ^= T0 >> 7;
+        hinP = houtM | T1; hinM = houtP & ~hinP;
+#pragma unroll
+        for (int k = 0; k < TK; ++k) { a[k] ^= T0; b[k] ^= T1; }
+    }
+    const uint64_t c1 = __builtin_amdgcn_s_memtime(), t1 = __builtin_amdgcn_s_memrealtime();
+    u64 acc = houtP ^ houtM;
+#pragma unroll
+    for (int k = 0; k < TK; ++k) acc ^= P[k] ^ M[k];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (u32)acc ^ (u32)(acc >> 32);
+    if ((threadIdx.x & 63) == 0) stamps[blockIdx.x * 4 + (threadIdx.x >> 6)] = Stamp{c1 - c0, t1 - t0};
+}
+// FORM 1 / 2 against the planes on random passes; 80 KB of dynamic LDS per workgroup of four waves
+template <int FORM>
+__global__ __launch_bounds__(256) void k_verify_tall(u32* bad) {
+    using namespace qe;
+    extern __shared__ uint4 pin[];
+    u64* const E = (u64*)((uint8_t*)pin + (size_t)(threadIdx.x >> 6) * (size_t)peq_bytes()) + (threadIdx.x & 63);
+    u64 s = (u64)(blockIdx.x * blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull + 4242;
+    auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    for (int it = 0; it < 16; ++it) {
+        u64 P1[TK], M1[TK], P2[TK], M2[TK], a[TK], b[TK];
+        for (int k = 0; k < TK; ++k) { const u64 x = rnd(), y = rnd(); P1[k] = P2[k] = x & ~y; M1[k] = M2[k] = y & ~x; a[k] = rnd(); b[k] = rnd(); }
+        const u64 T0 = rnd(), T1 = rnd(), h1 = rnd(), h2 = rnd(), hinP = h1 & ~h2, hinM = h2 & ~h1;
+        u64 o1P, o1M, o2P, o2M;
+        tall_pass<0>(P1, M1, a, b, E, T0, T1, hinP, hinM, o1P, o1M);
+        tall_pass<FORM>(P2, M2, a, b, E, T0, T1, hinP, hinM, o2P, o2M);
+        bool ok = o1P == o2P && o1M == o2M;
+        for (int k = 0; k < TK; ++k) ok = ok && P1[k] == P2[k] && M1[k] == M2[k];
+        if (!ok) atomicAdd(bad, 1u);
+    }
+}
+
 static u32* g_out; static Stamp* g_stamps;
 static const int CUS = 256;
 struct Result { double cyc_wave, clock_ghz, wall_ms; };
@@ -258,9 +325,42 @@ template <int VAR> static void step_row(const char* name, int wps, int iters) {
            per_simd, r.cyc_wave / bc, rate, r.clock_ghz, r.wall_ms);
 }
 
-int main() {
+template <int FORM> static void tall_row(const char* name, int wps, int iters) {
+    auto launch = [&](int blocks, size_t lds, bool warm) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_tall<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL((k_tall<FORM>), dim3(blocks), dim3(256), lds, 0, g_out, g_stamps, warm ? 4 : iters);
+    };
+    const Result r = measure(launch, wps);
+    const double bc = (double)iters * 64 * TK;
+    const double per_simd = r.wall_ms * 1e-3 * r.clock_ghz * 1e9 / (bc * wps);
+    printf("%-44s w=%d  %6.1f cyc / block-column / SIMD (one wave: %6.1f)   clock %.2f GHz  (%.2f ms)\n", name, wps, per_simd, r.cyc_wave / bc, r.clock_ghz,
+           r.wall_ms);
+}
+// the tall loop, planes against table: two workgroups of 80 KB per CU at w = 2, the table form's own footprint
+static void tall_part() {
+    hipMemset(g_out, 0, 64);
+    const size_t lds = (size_t)4 * (size_t)qe::peq_bytes();
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_verify_tall<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_verify_tall<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((k_verify_tall<1>), dim3(256), dim3(256), lds, 0, g_out);
+    hipLaunchKernelGGL((k_verify_tall<2>), dim3(256), dim3(256), lds, 0, g_out + 1);
+    u32 bad[2] = {1, 1};
+    const hipError_t err = hipMemcpy(bad, g_out, 8, hipMemcpyDeviceToHost);
+    printf("tall loop, K = %d: Eq from the LDS table (next pair prefetched / read in place) against the planes on %d random passes each: %u / %u mismatches (%s)\n",
+           TK, 256 * 256 * 16, bad[0], bad[1], hipGetErrorString(err));
+    if (err != hipSuccess) return;
+    const int it = 200;
+    for (int w : {1, 2}) {
+        tall_row<0>("run64_tall<8>, Eq from the planes", w, it);
+        tall_row<1>("run64_tall_peq<8>, table, next pair in flight", w, it);
+        tall_row<2>("run64_tall_peq<8>, table, read in place", w, it);
+    }
+}
+
+int main(int argc, char** argv) {
     hipMalloc(&g_out, (size_t)CUS * 8 * 256 * 4);
     hipMalloc(&g_stamps, (size_t)CUS * 8 * 4 * sizeof(Stamp));
+    if (argc > 1 && strcmp(argv[1], "tall") == 0) { tall_part(); return 0; }      // the tall loop alone
     hipMemset(g_out, 0, 64);
     hipLaunchKernelGGL((k_verify<0>), dim3(256), dim3(256), 0, 0, g_out);
     hipLaunchKernelGGL((k_verify<1>), dim3(256), dim3(256), 0, 0, g_out + 1);
@@ -292,5 +392,6 @@ int main() {
         step_row<9>("asm2 no quarter-rate, all VOP3", w, it);
         step_row<10>("32-row blocks, full-rate only (C++)", w, it);
     }
+    tall_part();
     return 0;
 }
