@@ -481,6 +481,41 @@ quicked_status_t quicked_batch_panel_heads(quicked_batch_t* batch, quicked_panel
  * grows by itself (a run that overflowed is run again with max_total >= wanted). */
 quicked_status_t quicked_batch_configure_panel_queue(quicked_batch_t* batch, int64_t max_total);
 int64_t          quicked_batch_panel_queue_wanted(quicked_batch_t* batch);
+/* Panel search by mismatches only.  QUICKED_PANEL_NO_INDELS is OR-ed into `mode` of quicked_batch_run_panel and
+ * quicked_batch_run_panel_all, beside the two IUPAC flags; on quicked_batch_run_panel it also stands beside
+ * QUICKED_PANEL_MATRIX.  Without the bit nothing about any run changes: no launch, no allocation, no copy.  With it the two
+ * runs answer under the other distance a panel job comes with: index reads and inline barcodes at a fixed position, guide
+ * counting, UMI whitelists, a trimmer's "no indels".  Edit distance is a lower bound of the mismatch count, so the unflagged
+ * runs report members and positions this run must not, and their results cannot be turned into its.
+ *
+ * The definition.  Text i has n bases, member p has m bases and the effective bound k = min(bound[p], m); the bounds are
+ * max_dist / max_dist_all as in the unflagged runs.  For a start s with 0 <= s <= n - m
+ *     H[s] = #{ r in [0, m) : member[r] and text[s + r] are NOT equal under the run's equality },
+ * the equality being the unflagged run's: case folded and any two non-ACGT bytes equal; QUICKED_SEARCH_IUPAC: the base sets
+ * intersect; QUICKED_SEARCH_IUPAC_PATTERN: a text byte outside ACGTU is the empty set and mismatches everything.  R[e] =
+ * H[e - m] for the ends e in E: INFIX E = {m, .., n}, PREFIX E = {m}, n < m: E is empty.  Every column outside E counts as
+ * higher than every value.  From here every sentence of the two runs' contracts above holds with D[m][e] read as R[e]:
+ *   quicked_batch_run_panel: member p's d = min over E of R, text_end the smallest e that has it; d > k or an empty E: p is
+ *     beyond for this text.  Keys, best, runner-up, quicked_batch_scores, empty texts and QUICKED_PANEL_MATRIX as there.
+ *     text_start = text_end - m always (0 with PREFIX); no start pass is launched.
+ *   quicked_batch_run_panel_all: e is an occurrence when R[e] <= k, R[e] < R[e - 1], and the first e' > e in E with R[e'] !=
+ *     R[e], if there is one, has R[e'] > R[e] -- the valley rule, a plateau counted once.  The record is {p, e - m, e, R[e]};
+ *     the order, found / stored, the max_hits cap and quicked_batch_scores as there.  Both consequences listed there hold
+ *     between the two flagged runs.
+ * ASCII and packed batches alike, with the unflagged runs' reading of PLANES3's fifth symbol; QE_PANEL_SLICES as there.
+ *
+ * Every QUICKED_ERROR rule of the two runs comes first, unchanged.  QUICKED_UNIMPLEMENTED, nothing launched, with the bit:
+ * QUICKED_PANEL_CIGARS, QUICKED_PANEL_TAILS or QUICKED_PANEL_HEADS beside it; sync == 0, also on a batch object that
+ * quicked_batch_configure_panel_queue switched on; a member over QUICKED_PANEL_MAX_LEN; check != 0.
+ * QUICKED_ERROR, nothing launched: the bit on quicked_batch_run_panel_scan, _run_search and _run_search_all (an unknown bit
+ * there).
+ * Counters: [0] is the block steps walked -- per (text, member) the start positions (n - m + 1, or 1 with PREFIX, or 0) x
+ * ceil(m / 64) --, [1] .. [7] are 0 ([5] too: the kernels' time is kernel_times slot [0]'s).  kernel_times slot [0] holds the
+ * launches.
+ * Not built: CIGARs, tails and heads under the bit; queued flagged runs; the windowed run under the bit; the bit for
+ * quicked_batch_run_search / _run_search_all; members over 256 bases; reverse-complement members; a per-member choice of
+ * distance within one run. */
+enum { QUICKED_PANEL_NO_INDELS = 32768 };      /* OR-ed into mode of quicked_batch_run_panel / _run_panel_all (4, 8, 128, 256, 1024, 4096 and 16384 stay unknown bits) */
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

@@ -77,6 +77,7 @@ PANEL_MATRIX = 64                                # OR-ed into a panel run's mode
 PANEL_CIGARS = 512                               # OR-ed into run_panel_all's / run_panel_scan's mode: every stored occurrence's alignment
 PANEL_TAILS = 2048                               # OR-ed into run_panel_all's mode: every text's 3' tail besides (panel_tails())
 PANEL_HEADS = 8192                               # OR-ed into run_panel_all's mode: every text's 5' head besides (panel_heads())
+PANEL_NO_INDELS = 32768                          # OR-ed into run_panel's / run_panel_all's mode: mismatches only, text_start = text_end - m
 PANEL_MAX_PATTERNS, PANEL_MAX_LEN = 4096, 256
 PANEL_HIT_DTYPE = np.dtype([("pattern", np.int32), ("score", np.int32), ("text_start", np.int32), ("text_end", np.int32),
                             ("second_pattern", np.int32), ("second_score", np.int32)])      # quicked_panel_hit_t
@@ -489,7 +490,8 @@ class ResidentBatch:
         """quicked_batch_run_panel: every text of the batch against the panel, a list of bytes (the batch's own patterns are
         ignored).  mode: SEARCH_PREFIX / SEARCH_INFIX, optionally | SEARCH_IUPAC or | SEARCH_IUPAC_PATTERN (the members are the
         pattern side).  max_dist: None = no bound, one int for every member, or one bound per member.  matrix=True keeps
-        every member's {score, text_end} for panel_matrix().  Sync runs only."""
+        every member's {score, text_end} for panel_matrix().  | PANEL_NO_INDELS: by mismatches only (no insertions or deletions),
+        text_start = text_end - m; sync only.  Sync runs only."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -539,7 +541,8 @@ class ResidentBatch:
         per text, ordered by (pattern, text_end).  mode, panel and max_dist as in run_panel (no matrix flag); PANEL_CIGARS OR-ed into
         mode aligns every stored occurrence besides (panel_hit_cigars()); PANEL_TAILS (INFIX only) reports every text's 3' tail
         besides (panel_tails()); PANEL_HEADS reports every text's 5' head besides (panel_heads()).  sync=False needs
-        configure_panel_queue() first and no PANEL_CIGARS; fetch() then brings the results."""
+        configure_panel_queue() first and no PANEL_CIGARS; fetch() then brings the results.  PANEL_NO_INDELS: the occurrences by
+        mismatches only (no insertions or deletions), text_start = text_end - m; sync only, and not beside the three bits above."""
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)

@@ -244,7 +244,9 @@ struct PanelRun { int32_t n_patterns; const char* pool; const int64_t* off; cons
 // ... and heads: QUICKED_PANEL_HEADS, every text's best member cut off by the text's start besides (run_panel_heads; the
 // shortest head is the batch's head_min_overlap)
 // ... and queue_total > 0: a panel run queued with sync == 0 (quicked_batch_configure_panel_queue): the room for its records
-struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; bool cigars = false; bool tails = false; bool heads = false; int64_t queue_total = 0; };
+// ... and no_indels: QUICKED_PANEL_NO_INDELS, either panel run by mismatches only (qe_panel_ham.h): never queued, never with
+// cigars, tails or heads
+struct SearchRun { int mode; const int32_t* max_dist; int32_t max_dist_all; int32_t max_hits = 0; int eq = 0; const PanelRun* panel = nullptr; int32_t window = -1; bool cigars = false; bool tails = false; bool heads = false; int64_t queue_total = 0; bool no_indels = false; };
 // the window slots of a batch at `window` columns per lane: every non-empty text in ceil(n / window) of them
 inline int64_t panel_scan_slots(const quicked_batch& B, int64_t window) {
     int64_t slots = 0;

@@ -328,11 +328,13 @@ static bool panel_args_ok(const quicked_batch_t* batch, int eq, int32_t n_patter
 QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
                                                 const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
                                                 int32_t max_dist_all, int sync) {
-    const int eq = search_mode_eq(mode & ~QUICKED_PANEL_MATRIX);
+    const bool no_indels = (mode & QUICKED_PANEL_NO_INDELS) != 0;                   // by mismatches only (qe_panel_ham.h)
+    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_MATRIX | QUICKED_PANEL_NO_INDELS));
     bool too_long = false;
     if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, (mode & QUICKED_PANEL_MATRIX) != 0};
     struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, 0, eq, &pr}, too_long, sync};
+    arg.sr.no_indels = no_indels;
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         // the room for the matrix: a row per text of the batch, the empty ones' included (they read -1)
@@ -340,7 +342,7 @@ QE_API quicked_status_t quicked_batch_run_panel(quicked_batch_t* batch, int mode
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
         // queued only on a batch configured for it (quicked_batch_configure_panel_queue), and never with the matrix
-        if (!x->sync && (B->panel_queue_total == 0 || x->sr.panel->matrix)) return QUICKED_UNIMPLEMENTED;
+        if (!x->sync && (B->panel_queue_total == 0 || x->sr.panel->matrix || x->sr.no_indels)) return QUICKED_UNIMPLEMENTED;
         if (!x->sync) x->sr.queue_total = B->panel_queue_total;
         return run_batch(*B, banded_params(true), x->sync != 0, nullptr, &x->sr);
     }, &arg);
@@ -369,18 +371,22 @@ QE_API quicked_status_t quicked_batch_run_panel_all(quicked_batch_t* batch, int 
     const bool cigars = (mode & QUICKED_PANEL_CIGARS) != 0;                         // every stored occurrence's alignment besides
     const bool tails = (mode & QUICKED_PANEL_TAILS) != 0;                           // every text's 3' tail besides
     const bool heads = (mode & QUICKED_PANEL_HEADS) != 0;                           // every text's 5' head besides
-    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_CIGARS | QUICKED_PANEL_TAILS | QUICKED_PANEL_HEADS));      // (QUICKED_PANEL_MATRIX is "any other bit" here)
+    const bool no_indels = (mode & QUICKED_PANEL_NO_INDELS) != 0;                   // by mismatches only (qe_panel_ham.h)
+    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_CIGARS | QUICKED_PANEL_TAILS | QUICKED_PANEL_HEADS | QUICKED_PANEL_NO_INDELS));      // (QUICKED_PANEL_MATRIX is "any other bit" here)
     bool too_long = false;
     if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
     if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
     if (tails && (mode & 15) == QUICKED_SEARCH_PREFIX) return QUICKED_ERROR;        // D[0][n] = n there: a tail means nothing
     PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
     struct Arg { SearchRun sr; bool too_long; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, -1, cigars, tails, heads}, too_long, sync};
+    arg.sr.no_indels = no_indels;
     return guard(batch, [](quicked_batch* B, void* a) {
         Arg* x = (Arg*)a;
         int64_t texts = 0;
         for (int64_t i = 0; i < B->n; ++i) texts += B->t_len[(size_t)i] > 0;
         if (texts * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;      // the room for the stored occurrences
+        // by mismatches only: the occurrences alone, and sync only
+        if (x->sr.no_indels && (x->sr.cigars || x->sr.tails || x->sr.heads || !x->sync)) return QUICKED_UNIMPLEMENTED;
         if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
         if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
         // queued only on a batch configured for it, which sizes the start pass from its max_total instead of the total the host

@@ -61,6 +61,9 @@
 #if __has_include("qe_kernels_stub_queue.h")
 #include "qe_kernels_stub_queue.h"
 #endif
+#if __has_include("qe_kernels_stub_noindels.h")
+#include "qe_kernels_stub_noindels.h"
+#endif
 #endif
 
 
@@ -1241,6 +1244,7 @@ quicked_status_t run_batch(quicked_batch& B, const quicked_params_t& p, bool fet
         float ms = 0;
         HIP_CHECK(hipEventElapsedTime(&ms, C.ev0, C.ev1));
         B.counters[5] = (int64_t)(ms * 1e6);
+        if (sr && sr->no_indels) B.counters[5] = 0;      // QUICKED_PANEL_NO_INDELS: [1] .. [7] are 0 by contract; kernel_times slot [0] has the time
         B.pending = false;
         memcpy(B.wr->counters, B.counters, sizeof(B.counters));
     }

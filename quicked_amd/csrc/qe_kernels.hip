@@ -32,6 +32,7 @@
 #include "qe_bounded.h"
 #include "qe_search.h"
 #include "qe_panel.h"
+#include "qe_panel_ham.h"
 #include "qe_panel_align.h"
 #include "qe_pack.h"
 #include "qe_tags.h"
@@ -1928,6 +1929,67 @@ template __global__ void k_panel_head_planes<SearchEqIupac>(PanelHeadPlanesArgs)
 __global__ __launch_bounds__(256) void k_panel_heads_finish(int nslots, const int32_t* __restrict__ o_pair, const int32_t* __restrict__ o_start, int32_t* __restrict__ heads) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t < nslots) panel_heads_finish_slot(t, o_pair, o_start, heads);
+}
+
+// Mismatch-only panel runs (qe_panel_ham.h; QUICKED_PANEL_NO_INDELS): kernels of their own beside the unchanged
+// k_search_panel / k_panel_hits, with their launch shape, slot table, slices and `part` / `raw` layouts, so that k_panel_reduce,
+// k_panel_hits_count, k_scan_offsets and k_panel_hits_expand serve them as they are.  The member index comes from blockIdx.y and
+// a loop counter only: planes, length, row masks and bound stay in scalar registers.  A lane holds NB + 1 words of each text
+// plane, the running count and the keeper or the valley scan.  No LDS of its own, no workspace, no task list, no start pass:
+// text_start = text_end - m, written by the two finish steps below.
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_ham(PanelArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    const bool matrix = A.m_score != nullptr && pair >= 0;
+    int32_t* ms = matrix ? A.m_score + (int64_t)pair * A.n_members : nullptr;
+    int32_t* me = matrix ? A.m_end + (int64_t)pair * A.n_members : nullptr;
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelKeeper keep;
+    keep.init();
+    u32 steps = 0;
+    panel_ham_text<Eq>(P, p0, p1, tp, n, A.mode, keep, steps, ms, me);      // (a lane without a text has n = 0: no start position)
+    if (pair >= 0) panel_store_part(A, nslices, slice, slot, keep, steps);
+}
+template __global__ void k_panel_ham<SearchEq3>(PanelArgs);
+template __global__ void k_panel_ham<SearchEqIupac>(PanelArgs);
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_ham_hits(PanelHitsArgs A) {
+    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    if (g * 64 >= A.nslots) return;
+    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
+    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
+    if (!__any(pair >= 0)) return;
+    int n = 0;
+    const u64* tp = A.pl_t;
+    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
+    PanelView P;
+    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    PanelHamScan H;
+    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    u32 steps = 0;
+    panel_ham_text_hits<Eq>(P, p0, p1, tp, n, A.mode, H, steps);
+    if (pair >= 0) panel_hits_store_part(A, nslices, slice, slot, H, steps);
+}
+template __global__ void k_panel_ham_hits<SearchEq3>(PanelHitsArgs);
+template __global__ void k_panel_ham_hits<SearchEqIupac>(PanelHitsArgs);
+// one thread per pair / per stored occurrence: text_start = text_end - m
+__global__ __launch_bounds__(256) void k_panel_ham_finish(int64_t npairs, const int32_t* __restrict__ m_len, int32_t* __restrict__ hits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < npairs) panel_ham_finish_pair(i, m_len, hits);
+}
+__global__ __launch_bounds__(256) void k_panel_ham_hits_finish(int64_t total, const int32_t* __restrict__ m_len, int32_t* __restrict__ hits) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < total) panel_ham_hits_finish_one(j, m_len, hits);
 }
 
 // Every occurrence of every member, long texts split across lanes (qe_panel.h; quicked_batch_run_panel_scan; DESIGN.md

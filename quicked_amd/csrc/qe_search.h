@@ -115,6 +115,10 @@ struct SearchEq3 {
         const uint64_t acgt = ~(p[0] ^ m0) & ~(p[1] ^ m1) & ~p[2];
         return (mn & p[2]) | (~mn & acgt);
     }
+    // position-wise: bit r is row r of p against position r of t (qe_panel_ham.h), where eq() holds one column against every row
+    static QE_S_HD uint64_t eq_pos(const uint64_t (&p)[W], const uint64_t (&t)[W]) {
+        return (p[2] & t[2]) | (~(p[2] | t[2]) & ~((p[0] ^ t[0]) | (p[1] ^ t[1])));
+    }
 };
 // Set intersection over four membership planes {A, C, G, T} (qe_iupac.h): a row matches the column when they share a base
 struct SearchEqIupac {
@@ -129,6 +133,9 @@ struct SearchEqIupac {
         const uint64_t mA = (uint64_t)0 - ((t[0] >> c) & 1), mC = (uint64_t)0 - ((t[1] >> c) & 1);
         const uint64_t mG = (uint64_t)0 - ((t[2] >> c) & 1), mT = (uint64_t)0 - ((t[3] >> c) & 1);
         return (mA & p[0]) | (mC & p[1]) | (mG & p[2]) | (mT & p[3]);
+    }
+    static QE_S_HD uint64_t eq_pos(const uint64_t (&p)[W], const uint64_t (&t)[W]) {      // position-wise, as SearchEq3::eq_pos
+        return (p[0] & t[0]) | (p[1] & t[1]) | (p[2] & t[2]) | (p[3] & t[3]);
     }
 };
 

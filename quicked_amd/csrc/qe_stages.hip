@@ -1448,6 +1448,9 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     PanelOut O;
     const PanelDev D = panel_upload(B, C, sr);
     O.text = D.text;
+    // (QUICKED_PANEL_NO_INDELS: k_panel_ham in k_search_panel's place, the reduction in its PREFIX form -- no start-pass task --
+    // and text_start = text_end - m behind it)
+    const bool start_pass = infix && !sr.no_indels;
     if (O.text.empty()) return O;
     const size_t n = (size_t)B.n, nslots = D.nslots, ngroups = D.ngroups;
     const int64_t* d_pl_off = D.d_pl_off;
@@ -1477,18 +1480,21 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
         // four text groups per workgroup, one per SIMD of its CU, and launch_groups' claim on the CU's LDS: at most two of
         // these workgroups share a CU, whichever slices they belong to
         const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
-        if (eq) hipLaunchKernelGGL(k_search_panel<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+        if (sr.no_indels) {
+            if (eq) hipLaunchKernelGGL(k_panel_ham<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+            else hipLaunchKernelGGL(k_panel_ham<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
+        } else if (eq) hipLaunchKernelGGL(k_search_panel<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
         else hipLaunchKernelGGL(k_search_panel<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
     }
     HIP_CHECK(hipGetLastError());
     tl.end();
     // ---- the reduction, and the start pass's tasks
     PanelReduceArgs r{};
-    r.nslots = (int32_t)nslots; r.nslices = nslices; r.infix = infix ? 1 : 0;
+    r.nslots = (int32_t)nslots; r.nslices = nslices; r.infix = start_pass ? 1 : 0;
     r.text = d_text; r.part = a.part; r.m_len = d_len; r.m_off = d_pl_off; r.t_len = B.d_t_len;
     r.hits = O.d_hits; r.o_adv = O.d_adv;
     int32_t* o_start = nullptr;
-    if (infix) {
+    if (start_pass) {
         int32_t* q = C.scratch_p->take<int32_t>(6 * nslots);
         r.o_pair = q; r.o_m = q + nslots; r.o_n = q + 2 * nslots; r.o_score = q + 3 * nslots; r.o_end = q + 4 * nslots; o_start = q + 5 * nslots;
         HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
@@ -1499,7 +1505,11 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     }
     hipLaunchKernelGGL(k_panel_reduce, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, r);
     HIP_CHECK(hipGetLastError());
-    if (!infix) return O;
+    if (sr.no_indels && infix) {
+        hipLaunchKernelGGL(k_panel_ham_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, (int64_t)n, d_len, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (!start_pass) return O;
     // ---- the start pass: one lane per text over the window that ends at its best member's text_end, reversed
     if (!eq) ensure_reversed(B, C);
     PairView PV = pair_view(B, true);
@@ -1748,7 +1758,9 @@ static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, c
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
     const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
-    const bool infix = sr.mode == SEARCH_INFIX;
+    // (QUICKED_PANEL_NO_INDELS: k_panel_ham_hits in k_panel_hits' place, the expand step in its PREFIX form -- no start-pass task
+    // -- and text_start = text_end - m behind it; never queued, never with strings, tails or heads)
+    const bool infix = sr.mode == SEARCH_INFIX && !sr.no_indels;
     HitsOut O;
     const PanelDev D = panel_upload(B, C, sr);
     O.task_pair = D.text;
@@ -1774,6 +1786,9 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
         if (sr.tails) {
             if (eq) hipLaunchKernelGGL(k_panel_tails<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, ta);
             else hipLaunchKernelGGL(k_panel_tails<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, ta);
+        } else if (sr.no_indels) {
+            if (eq) hipLaunchKernelGGL(k_panel_ham_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
+            else hipLaunchKernelGGL(k_panel_ham_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
         } else if (eq) hipLaunchKernelGGL(k_panel_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
         else hipLaunchKernelGGL(k_panel_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
     }
@@ -1823,6 +1838,10 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     if (queued) hipLaunchKernelGGL(k_panel_queue_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e, (int64_t)O.cap);
     else hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
     HIP_CHECK(hipGetLastError());
+    if (sr.no_indels && sr.mode == SEARCH_INFIX) {
+        hipLaunchKernelGGL(k_panel_ham_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, D.d_len, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
     if (infix) {
         // ---- the start pass: one lane per stored occurrence over its window, reversed
         if (!eq) ensure_reversed(B, C);
