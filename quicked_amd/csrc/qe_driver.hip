@@ -44,8 +44,9 @@
 #define QE_KERNELS_HEADER "qe_kernels.hip"
 #endif
 #include QE_KERNELS_HEADER
-// (the host-only build's stand-ins of kernels that are newer than its stub header, where the tree has them)
-#if !defined(__HIPCC__) && defined(__has_include)
+// (a stub header that does not say it holds every stand-in -- the layout before they were folded into it -- keeps six groups of
+// them in headers beside it; one that does, QE_STUB_HAS_EVERY_STAND_IN, is never followed by one of these)
+#if !defined(__HIPCC__) && defined(__has_include) && !defined(QE_STUB_HAS_EVERY_STAND_IN)
 #if __has_include("qe_kernels_stub_scan.h")
 #include "qe_kernels_stub_scan.h"
 #endif

@@ -1721,9 +1721,9 @@ __global__ __launch_bounds__(256) void k_hits_finish(int64_t total, const int32_
 // ===========================================================================
 // Panel search (qe_panel.h; quicked_batch_run_panel): every text of the batch against one shared set of
 // patterns.  One lane per text, 64 texts per wave in the batch's length order; blockIdx.y is the panel slice, and the wave
-// loops over the members of its slice (panel_text).  The member index comes from blockIdx and kernel arguments only, so
-// everything about a member -- length, bound, block count, row bit, the plane words -- is wave-uniform and read through
-// uniform addresses: it lives in scalar registers, and the dispatch on the block count is a uniform branch.  A lane holds
+// loops over the members of its slice (panel_text).  Every sweep kernel below opens the same way -- the group's exit,
+// panel_slice, panel_lane, the exit of a wave without a text -- and qe_panel.h says there, once, why everything about a member
+// is wave-uniform and lives in scalar registers; each kernel's comment keeps what is its own.  Here a lane holds
 // its text's chunk words, {Pv, Mv, S} of up to four blocks, the SearchLane and the keeper.  A member's chunk loop is each
 // lane's own (search_run): the wave leaves it at its longest text, or when every lane has its answer.  Written: one partial
 // keeper per (slice, text), [field][slice][slot] so that a wave's stores are contiguous rows, and with the matrix wanted every
@@ -1731,25 +1731,19 @@ __global__ __launch_bounds__(256) void k_hits_finish(int64_t total, const int32_
 // ===========================================================================
 template <class Eq>
 __global__ __launch_bounds__(256) void k_search_panel(PanelArgs A) {
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    const bool matrix = A.m_score != nullptr && pair >= 0;
-    int32_t* ms = matrix ? A.m_score + (int64_t)pair * A.n_members : nullptr;
-    int32_t* me = matrix ? A.m_end + (int64_t)pair * A.n_members : nullptr;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
+    const bool matrix = A.m_score != nullptr && T.pair >= 0;
+    int32_t* ms = matrix ? A.m_score + (int64_t)T.pair * A.n_members : nullptr;
+    int32_t* me = matrix ? A.m_end + (int64_t)T.pair * A.n_members : nullptr;
     PanelKeeper keep;
     keep.init();
     u32 steps = 0;
-    panel_text<Eq>(P, p0, p1, tp, n, A.mode, keep, steps, ms, me);
-    if (pair >= 0) panel_store_part(A, nslices, slice, slot, keep, steps);
+    panel_text<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, keep, steps, ms, me);
+    if (T.pair >= 0) panel_store_part(A, S.nslices, S.slice, T.slot, keep, steps);
 }
 template __global__ void k_search_panel<SearchEq3>(PanelArgs);
 template __global__ void k_search_panel<SearchEqIupac>(PanelArgs);
@@ -1777,30 +1771,23 @@ __global__ __launch_bounds__(256) void k_panel_finish(int nslots, const int32_t*
 }
 
 // Every occurrence of every member (qe_panel.h; quicked_batch_run_panel_all): k_search_panel's grid, slots
-// and launch shape, with the all-occurrences scan (SearchHitScanOf over a PanelHitSink) in the place of the keeper.  The member
-// index still comes from blockIdx.y and a loop counter only, so a member's length, bound, block count, row bit and plane words
-// stay wave-uniform and the dispatch on the block count a uniform branch; a lane holds its chunk's text words, {Pv, Mv, S} of
-// up to four blocks, the SearchLane, the scan state and its sink.  The bound stays for the whole text and no lane leaves early.
+// and launch shape, with the all-occurrences scan (SearchHitScanOf over a PanelHitSink) in the place of the keeper.  A lane
+// holds its chunk's text words, {Pv, Mv, S} of up to four blocks, the SearchLane, the scan state and its sink.  The bound
+// stays for the whole text and no lane leaves early.
 // A lane stores only when row m rises out of a valley: one 12-byte record into the stretch of its own (slice, slot), never
 // past max_hits of them; a lane without a text has cap 0 and a null sink.  No workspace, no task list.
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_hits(PanelHitsArgs A) {
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
     PanelHitScan H;
-    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    panel_hit_scan_init(H, panel_lane_raw(A, S, T), T.pair >= 0 ? A.max_hits : 0);
     u32 steps = 0;
-    panel_text_hits<Eq>(P, p0, p1, tp, n, A.mode, H, steps);
-    if (pair >= 0) panel_hits_store_part(A, nslices, slice, slot, H, steps);
+    panel_text_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, H, steps);
+    if (T.pair >= 0) panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps);
 }
 template __global__ void k_panel_hits<SearchEq3>(PanelHitsArgs);
 template __global__ void k_panel_hits<SearchEqIupac>(PanelHitsArgs);
@@ -1836,31 +1823,24 @@ __global__ __launch_bounds__(256) void k_panel_queue_clamp(int64_t n, int64_t ca
 
 // A member cut off by the text's end (qe_panel.h; QUICKED_PANEL_TAILS): k_panel_hits -- its grid, slots,
 // slices, scan and stores, through the argument block it takes -- and, after every member's walk of the text, the walk down
-// the column the lane's registers end in (panel_tail_walk).  The member index still comes from blockIdx.y and a loop counter
-// only, so the member's length, bound, allowance and the walk's loop bounds are wave-uniform; the live-block count and the
-// words are the lane's.  Besides k_panel_hits' stores one tail keeper per (slice, slot).  A kernel of its own: a run without
-// the bit launches k_panel_hits as it is.
+// the column the lane's registers end in (panel_tail_walk).  The walk's allowance and loop bounds are the member's, so
+// wave-uniform too; the live-block count and the words are the lane's.  Besides k_panel_hits' stores one tail keeper per
+// (slice, slot).  A kernel of its own: a run without the bit launches k_panel_hits as it is.
 template <class Eq>
-__global__ __launch_bounds__(256) void k_panel_tails(PanelTailsArgs T) {
-    const PanelHitsArgs& A = T.H;
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+__global__ __launch_bounds__(256) void k_panel_tails(PanelTailsArgs X) {
+    const PanelHitsArgs& A = X.H;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
     PanelHitScan H;
-    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    panel_hit_scan_init(H, panel_lane_raw(A, S, T), T.pair >= 0 ? A.max_hits : 0);
     PanelTailKeeper keep;
     keep.init();
     u32 steps = 0, rows = 0;
-    panel_text_tails<Eq>(P, p0, p1, tp, n, A.mode, T.min_overlap, H, keep, steps, rows);      // (a lane without a text has n = 0: no tail)
-    if (pair >= 0) { panel_hits_store_part(A, nslices, slice, slot, H, steps); panel_tails_store_part(T, nslices, slice, slot, keep, rows); }
+    panel_text_tails<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, X.min_overlap, H, keep, steps, rows);      // (a lane without a text has n = 0: no tail)
+    if (T.pair >= 0) { panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps); panel_tails_store_part(X, S.nslices, S.slice, T.slot, keep, rows); }
 }
 template __global__ void k_panel_tails<SearchEq3>(PanelTailsArgs);
 template __global__ void k_panel_tails<SearchEqIupac>(PanelTailsArgs);
@@ -1888,26 +1868,19 @@ __global__ __launch_bounds__(256) void k_panel_tails_finish(int nslots, const in
 // unchanged k_panel_hits / k_panel_tails, in their launch shape -- one lane per text, four text groups per workgroup, slices of
 // the panel in blockIdx.y.  Per member a fresh INFIX sweep of the member's REVERSED planes over the lane's first min(n, m + k)
 // text columns taken backwards (read from the forward planes, reversed in registers), then the tails' walk down the column the
-// registers end in.  The member index comes from blockIdx.y and a loop counter only: length, bound, allowance and block form
-// are wave-uniform; the column count, the live blocks and the words are the lane's.  One keeper per (slice, slot).
+// registers end in.  The column count, the live blocks and the words are the lane's.  One keeper per (slice, slot).
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_heads(PanelHeadsArgs A) {
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    PanelView P;
-    P.pl = A.pl_m_rev; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
     PanelTailKeeper keep;
     keep.init();
     u32 steps = 0, rows = 0;
-    panel_text_heads<Eq>(P, p0, p1, tp, n, A.min_overlap, keep, steps, rows);      // (a lane without a text has n = 0: no column, no head)
-    if (pair >= 0) panel_heads_store_part(A, nslices, slice, slot, keep, rows, steps);
+    panel_text_heads<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.min_overlap, keep, steps, rows);      // (a lane without a text has n = 0: no column, no head)
+    if (T.pair >= 0) panel_heads_store_part(A, S.nslices, S.slice, T.slot, keep, rows, steps);
 }
 template __global__ void k_panel_heads<SearchEq3>(PanelHeadsArgs);
 template __global__ void k_panel_heads<SearchEqIupac>(PanelHeadsArgs);
@@ -1933,52 +1906,40 @@ __global__ __launch_bounds__(256) void k_panel_heads_finish(int nslots, const in
 
 // Mismatch-only panel runs (qe_panel_ham.h; QUICKED_PANEL_NO_INDELS): kernels of their own beside the unchanged
 // k_search_panel / k_panel_hits, with their launch shape, slot table, slices and `part` / `raw` layouts, so that k_panel_reduce,
-// k_panel_hits_count, k_scan_offsets and k_panel_hits_expand serve them as they are.  The member index comes from blockIdx.y and
-// a loop counter only: planes, length, row masks and bound stay in scalar registers.  A lane holds NB + 1 words of each text
+// k_panel_hits_count, k_scan_offsets and k_panel_hits_expand serve them as they are.  The member's row masks are scalar like
+// its planes, length and bound.  A lane holds NB + 1 words of each text
 // plane, the running count and the keeper or the valley scan.  No LDS of its own, no workspace, no task list, no start pass:
 // text_start = text_end - m, written by the two finish steps below.
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_ham(PanelArgs A) {
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    const bool matrix = A.m_score != nullptr && pair >= 0;
-    int32_t* ms = matrix ? A.m_score + (int64_t)pair * A.n_members : nullptr;
-    int32_t* me = matrix ? A.m_end + (int64_t)pair * A.n_members : nullptr;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
+    const bool matrix = A.m_score != nullptr && T.pair >= 0;
+    int32_t* ms = matrix ? A.m_score + (int64_t)T.pair * A.n_members : nullptr;
+    int32_t* me = matrix ? A.m_end + (int64_t)T.pair * A.n_members : nullptr;
     PanelKeeper keep;
     keep.init();
     u32 steps = 0;
-    panel_ham_text<Eq>(P, p0, p1, tp, n, A.mode, keep, steps, ms, me);      // (a lane without a text has n = 0: no start position)
-    if (pair >= 0) panel_store_part(A, nslices, slice, slot, keep, steps);
+    panel_ham_text<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, keep, steps, ms, me);      // (a lane without a text has n = 0: no start position)
+    if (T.pair >= 0) panel_store_part(A, S.nslices, S.slice, T.slot, keep, steps);
 }
 template __global__ void k_panel_ham<SearchEq3>(PanelArgs);
 template __global__ void k_panel_ham<SearchEqIupac>(PanelArgs);
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_ham_hits(PanelHitsArgs A) {
-    const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
+    const int g = QE_GROUP_INDEX();
     if (g * 64 >= A.nslots) return;
-    const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
-    const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
-    if (!__any(pair >= 0)) return;
-    int n = 0;
-    const u64* tp = A.pl_t;
-    if (pair >= 0) { n = A.t_len[pair]; tp = A.pl_t + Eq::offset(A.pl_t_off[pair]); }
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
     PanelHamScan H;
-    panel_hit_scan_init(H, pair >= 0 ? A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits : nullptr, pair >= 0 ? A.max_hits : 0);
+    panel_hit_scan_init(H, panel_lane_raw(A, S, T), T.pair >= 0 ? A.max_hits : 0);
     u32 steps = 0;
-    panel_ham_text_hits<Eq>(P, p0, p1, tp, n, A.mode, H, steps);
-    if (pair >= 0) panel_hits_store_part(A, nslices, slice, slot, H, steps);
+    panel_ham_text_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, H, steps);
+    if (T.pair >= 0) panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps);
 }
 template __global__ void k_panel_ham_hits<SearchEq3>(PanelHitsArgs);
 template __global__ void k_panel_ham_hits<SearchEqIupac>(PanelHitsArgs);
@@ -1994,18 +1955,19 @@ __global__ __launch_bounds__(256) void k_panel_ham_hits_finish(int64_t total, co
 
 // Every occurrence of every member, long texts split across lanes (qe_panel.h; quicked_batch_run_panel_scan; DESIGN.md
 // 4.14.2): k_panel_hits with a WINDOW SLOT {pair, c0, c1} per lane in the place of a text slot -- the grid is window groups x
-// panel slices, the launch shape k_panel_hits'.  The member index still comes from blockIdx.y and a loop counter only: length,
-// bound, block count, row bit, plane words and the warm-up's length stay wave-uniform, the dispatch on the block count a
-// uniform branch.  A lane walks its warm-up, its owned columns and -- only while a candidate is pending -- the run-out
+// panel slices, the launch shape k_panel_hits'.  The warm-up's length is the member's, so wave-uniform too.
+// A lane walks its warm-up, its owned columns and -- only while a candidate is pending -- the run-out
 // (panel_member_window); the wave leaves a member when its last lane does.  Stores as k_panel_hits: one 12-byte record when
 // row m rises out of an owned valley, never past max_hits per (slice, slot).  No workspace, no task list.
+// This kernel keeps the opener written out: through panel_slice / panel_lane its stream grew by 4 (IUPAC: 9) instructions and
+// the IUPAC form ran 2.9 % slower in every run; as it stands the stream is the one it had (profiles/panel_shells.md).
 template <class Eq>
 __global__ __launch_bounds__(256) void k_panel_scan(PanelScanArgs A) {
     const int g = QE_GROUP_INDEX(), lane = threadIdx.x & 63, slot = g * 64 + lane;
     if (g * 64 >= A.nslots) return;
     const int slice = (int)blockIdx.y, nslices = (A.n_members + A.per_slice - 1) / A.per_slice;      // = gridDim.y
     const int p0 = slice * A.per_slice, p1 = min(A.n_members, p0 + A.per_slice);
-    const int pair = A.w_pair[slot];                           // (nslots is a multiple of 64)
+    const int pair = A.text[slot];                             // (nslots is a multiple of 64)
     if (!__any(pair >= 0)) return;
     int n = 0, c0 = 0, c1 = 0;
     const u64* tp = A.pl_t;

@@ -12,9 +12,8 @@
 // so merging is associative and commutative: a panel may be cut into slices that are searched in any order and merged in any
 // grouping.
 //
-// Why one lane per text.  Everything about a member is the same for every text: its planes, length, block count, row bit
-// and bound are wave-uniform, read through uniform addresses (scalar registers on the device), and the dispatch on the
-// block count is a uniform branch.  A lane keeps the text side only: the chunk's words, {Pv, Mv, S} of up to four blocks,
+// Why one lane per text.  Everything about a member is the same for every text (panel_slice below says why that puts it in
+// scalar registers on the device).  A lane keeps the text side only: the chunk's words, {Pv, Mv, S} of up to four blocks,
 // the SearchLane and the keeper.
 //
 // The second half of the file is the all-occurrences run (quicked_batch_run_panel_all): the same lanes and
@@ -23,6 +22,7 @@
 // reversed member over the text's start, and the same walk; and the windowed run (quicked_batch_run_panel_scan).
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #include "qe_search.h"
 
@@ -55,6 +55,18 @@ struct PanelView {
     const int32_t* len;
     const int32_t* bound;
 };
+// The member loop of every sweep: f(NB, p, pp, m, bound) for the members [p0, p1) in ascending order -- NB a
+// std::integral_constant, the register form that holds the member's blocks (1, 2 or QE_SEARCH_REG_BLOCKS); pp its planes
+template <class Eq, class F>
+QE_S_HD void panel_each_member(const PanelView& P, int p0, int p1, F&& f) {
+    for (int p = p0; p < p1; ++p) {
+        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
+        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+        if (nb <= 1) f(std::integral_constant<int, 1>{}, p, pp, m, bound);
+        else if (nb == 2) f(std::integral_constant<int, 2>{}, p, pp, m, bound);
+        else if (nb <= QE_SEARCH_REG_BLOCKS) f(std::integral_constant<int, QE_SEARCH_REG_BLOCKS>{}, p, pp, m, bound);
+    }
+}
 
 // one member of NB blocks at the most against one text (n columns from the start of its planes tp): the register form
 template <int NB, class Eq>
@@ -62,10 +74,7 @@ QE_S_HD void panel_member(const uint64_t* pp, int m, int bound, const uint64_t* 
     SearchLane L;
     search_lane_init(L, m, n, mode, bound, 0);
     SearchRegStore<NB, Eq> R;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.clear();
     R.load(pp, m);
     search_run<NB>(R, L, tp, 0);
     search_answer(L, score, end);
@@ -77,16 +86,12 @@ QE_S_HD void panel_member(const uint64_t* pp, int m, int bound, const uint64_t* 
 template <class Eq>
 QE_S_HD void panel_text(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelKeeper& keep, uint32_t& steps,
                         int32_t* m_score, int32_t* m_end) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         int32_t score = -1, end = -1;
-        if (nb <= 1) panel_member<1, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
-        else if (nb == 2) panel_member<2, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        panel_member<NB, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        keep.take(score >= 0 ? p : -1, score, end);               // (before the stores: profiles/panel_shells.md)
         if (m_score) { m_score[p] = score; m_end[p] = end; }
-        keep.take(score >= 0 ? p : -1, score, end);
-    }
+    });
 }
 
 // The start-pass task of a text's best member (INFIX): member of m bases found at distance `score` ending at `end` in a text
@@ -104,11 +109,41 @@ QE_S_HD void panel_start_task(int m, int n, int end, int score, int32_t& task_n,
 // word Eq::offset(m_off[p]) of pl_m (three-plane offsets, as a batch's).  Per (slice, slot) one partial keeper and the lane's
 // block steps: field f of {p1, s1, e1, p2, s2, steps} at part[(f nslices + s) nslots + t].  m_score / m_end (null: not kept):
 // every member's {d or -1, text_end or -1} at [pair n_members + p].
-struct PanelArgs {
-    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
+//
+// PanelSweepArgs is what every per-text sweep kernel reads first, and the leading block of each one's arguments.  k_panel_heads
+// has the members' REVERSED planes in pl_m; k_panel_scan has window slots for text slots, so its `text` is the window slots'
+// pairs.  Those two blocks' own names for the two fields, pl_m_rev and w_pair, stay valid beside the shared ones.
+struct PanelSweepArgs {
+    union { const uint64_t* pl_m;  const uint64_t* pl_m_rev; };
+    const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
     int32_t n_members, per_slice;
     const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
-    int32_t nslots;  const int32_t* text;
+    int32_t nslots;
+    union { const int32_t* text;  const int32_t* w_pair; };
+};
+// The opener of every sweep, in two halves.  The slice half is computed from kernel arguments and the slice index
+// (blockIdx.y on the device) alone, and the member loop (panel_each_member) adds a loop counter: so everything about a member
+// -- its index, length, bound, block count, row bit, plane words -- is wave-uniform, read through uniform addresses into
+// scalar registers, and the dispatch on the block count is a uniform branch.  The text half is the lane's own.  They stay two
+// structs returned by value, and a kernel's early exits stay in the kernel: one struct filled through a reference, exits
+// inside, moved the member data out of the scalar registers (profiles/panel_shells.md).
+struct PanelSlice { int slice, nslices, p0, p1; PanelView P; };      // the members [p0, p1); nslices = gridDim.y
+struct PanelLane { int slot, pair, n; const uint64_t* tp; };          // pair < 0: an empty slot, n = 0 and no store
+QE_S_HD PanelSlice panel_slice(const PanelSweepArgs& A, int slice) {
+    PanelSlice S;
+    S.slice = slice; S.nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
+    S.p0 = slice * A.per_slice; S.p1 = A.n_members < S.p0 + A.per_slice ? A.n_members : S.p0 + A.per_slice;
+    S.P.pl = A.pl_m; S.P.off = A.m_off; S.P.len = A.m_len; S.P.bound = A.m_bound;
+    return S;
+}
+template <class Eq>
+QE_S_HD PanelLane panel_lane(const PanelSweepArgs& A, int slot) {
+    PanelLane T;
+    T.slot = slot; T.pair = A.text[slot]; T.n = 0; T.tp = A.pl_t;       // (nslots is a multiple of 64)
+    if (T.pair >= 0) { T.n = A.t_len[T.pair]; T.tp = A.pl_t + Eq::offset(A.pl_t_off[T.pair]); }
+    return T;
+}
+struct PanelArgs : PanelSweepArgs {
     int32_t mode;                            // SEARCH_PREFIX / SEARCH_INFIX
     int32_t* part;
     int32_t* m_score;  int32_t* m_end;
@@ -196,10 +231,7 @@ QE_S_HD void panel_member_hits(const uint64_t* pp, int m, int bound, const uint6
     SearchLane L;
     search_lane_init(L, m, n, mode, bound, 0);
     SearchRegStore<NB, Eq> R;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    R.clear();
     R.load(pp, m);
     H.begin(L);
     search_run_hits<NB>(R, L, H, tp, 0);
@@ -210,29 +242,26 @@ QE_S_HD void panel_member_hits(const uint64_t* pp, int m, int bound, const uint6
 // on over the members; steps: block steps, added to
 template <class Eq>
 QE_S_HD void panel_text_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelHitScan& H, uint32_t& steps) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         H.sink.member = p;
-        if (nb <= 1) panel_member_hits<1, Eq>(pp, m, bound, tp, n, mode, H, steps);
-        else if (nb == 2) panel_member_hits<2, Eq>(pp, m, bound, tp, n, mode, H, steps);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_hits<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, H, steps);
-    }
+        panel_member_hits<NB, Eq>(pp, m, bound, tp, n, mode, H, steps);
+    });
 }
 
 // k_panel_hits<Eq>: k_search_panel's grid and slots (PanelArgs above), the members' occurrences instead of the two best keys.
 // Per (slice s, slot t): field f of {found, stored, best, steps} at part[(f nslices + s) nslots + t], and the stored
 // occurrences -- at most max_hits, the slice's first in (member, text_end) order -- as PanelRawHit number i at
 // raw[(s nslots + t) max_hits + i].  A slot without a text writes nothing.
-struct PanelHitsArgs {
-    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
-    int32_t n_members, per_slice;
-    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
-    int32_t nslots;  const int32_t* text;
+struct PanelHitsArgs : PanelSweepArgs {
     int32_t mode, max_hits;
     int32_t* part;
     PanelRawHit* raw;
 };
+// the stretch of a lane's raw records (here and in PanelScanArgs), null for an empty slot, whose room is 0
+template <class A>
+QE_S_HD PanelRawHit* panel_lane_raw(const A& a, const PanelSlice& S, const PanelLane& T) {
+    return T.pair >= 0 ? a.raw + ((int64_t)S.slice * a.nslots + T.slot) * a.max_hits : nullptr;
+}
 // One thread per text slot (k_panel_hits_count): the slices' counts merged into found[pair], best[pair] (the smallest score
 // among all found occurrences, -1: none) and len[pair] = stored - 1, stored = min(found, max_hits) -- what k_scan_offsets adds
 // 1 to --, and o_adv[t] = the slot's block steps.  Every slice stores its first min(found_s, max_hits), so the first
@@ -368,9 +397,7 @@ template <int NB, class Store>
 QE_S_HD void panel_tail_walk(Store& st, const SearchLane& L, int min_overlap, int32_t p, PanelTailKeeper& keep, uint32_t& rows) {
     if (L.n < 1) return;                                      // an empty text has no tail
     const int m = L.m, k = search_effective(L.k, m);          // (an all-occurrences lane keeps its bound: L.k is the member's)
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+    QE_S_UNROLL
     for (int b = 0; b < NB; ++b) {
         const int left = m - 1 - 64 * b, nrows = left < 64 ? left : 64;      // rows 64 b + 1 .. m - 1 of this block
         if (nrows <= 0 || b >= L.live) continue;
@@ -395,10 +422,8 @@ QE_S_HD void panel_member_tails(const uint64_t* pp, int m, int bound, const uint
     SearchLane L;
     search_lane_init(L, m, n, mode, bound, 0);
     SearchRegStore<NB, Eq> R;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    QE_S_UNROLL
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }      // (not R.clear(): profiles/panel_shells.md)
     R.load(pp, m);
     H.begin(L);
     search_run_hits<NB>(R, L, H, tp, 0);
@@ -409,14 +434,10 @@ QE_S_HD void panel_member_tails(const uint64_t* pp, int m, int bound, const uint
 template <class Eq>
 QE_S_HD void panel_text_tails(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, int min_overlap,
                               PanelHitScan& H, PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         H.sink.member = p;
-        if (nb <= 1) panel_member_tails<1, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
-        else if (nb == 2) panel_member_tails<2, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_tails<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
-    }
+        panel_member_tails<NB, Eq>(pp, m, bound, tp, n, mode, min_overlap, p, H, keep, steps, rows);
+    });
 }
 
 // k_panel_tails<Eq>: k_panel_hits with the walk.  H is k_panel_hits' argument block and everything it names is written as that
@@ -557,10 +578,8 @@ QE_S_HD void panel_member_heads(const uint64_t* pp, int m, int bound, const uint
     SearchLane L;
     search_lane_init(L, m, c0, SEARCH_INFIX, bound, 0);
     SearchRegStore<NB, Eq> R;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    QE_S_UNROLL
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }      // (not R.clear(): profiles/panel_shells.md)
     R.load(pp, m);
     search_store_init<NB>(R, L);
     PanelNoScan none;
@@ -578,23 +597,15 @@ QE_S_HD void panel_member_heads(const uint64_t* pp, int m, int bound, const uint
 template <class Eq>
 QE_S_HD void panel_text_heads(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int min_overlap,
                               PanelTailKeeper& keep, uint32_t& steps, uint32_t& rows) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
-        if (nb <= 1) panel_member_heads<1, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
-        else if (nb == 2) panel_member_heads<2, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_heads<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
-    }
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
+        panel_member_heads<NB, Eq>(pp, m, bound, tp, n, min_overlap, p, keep, steps, rows);
+    });
 }
 
-// k_panel_heads<Eq>: k_panel_hits' grid, slots and slices over the members' reversed planes (pl_m_rev; offsets, lengths and
+// k_panel_heads<Eq>: k_panel_hits' grid, slots and slices over the members' reversed planes (in pl_m; offsets, lengths and
 // bounds the panel's) and the texts' forward planes.  Per (slice s, slot t): field f of {pattern, overlap, score, row steps,
 // block steps} of the slice's best head at hpart[(f nslices + s) nslots + t].  A slot without a text writes nothing.
-struct PanelHeadsArgs {
-    const uint64_t* pl_m_rev;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
-    int32_t n_members, per_slice;
-    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
-    int32_t nslots;  const int32_t* text;
+struct PanelHeadsArgs : PanelSweepArgs {
     int32_t min_overlap;
     int32_t* hpart;
 };
@@ -699,10 +710,8 @@ QE_S_HD void panel_member_window(const uint64_t* pp, int m, int bound, const uin
     SearchLane L;
     search_lane_init(L, m, n, SEARCH_INFIX, bound, 0);
     SearchRegStore<NB, Eq> R;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+    QE_S_UNROLL
+    for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }      // (not R.clear(): profiles/panel_shells.md)
     R.load(pp, m);
     H.begin(L);
     search_store_init<NB>(R, L);
@@ -723,25 +732,18 @@ QE_S_HD void panel_member_window(const uint64_t* pp, int m, int bound, const uin
 // the window owns goes to H's sink, H.found / H.best run on over the members; steps: block steps, added to
 template <class Eq>
 QE_S_HD void panel_window_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int c0, int c1, PanelWindowScan& H, uint32_t& steps) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         H.sink.member = p;
-        if (nb <= 1) panel_member_window<1, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
-        else if (nb == 2) panel_member_window<2, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_member_window<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
-    }
+        panel_member_window<NB, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
+    });
 }
 
 // k_panel_scan<Eq>: k_panel_hits' shape with window slots for text slots.  Window slot w (nslots of them, a multiple of 64)
-// is {w_pair[w] (-1: an empty slot), w_c0[w], w_c1[w]}; a text's slots are contiguous and ascending by window.  Per (slice s,
+// is {text[w] (-1: an empty slot), w_c0[w], w_c1[w]}; a text's slots are contiguous and ascending by window.  Per (slice s,
 // slot w): field f of {found, stored, best, steps} at part[(f nslices + s) nslots + w] and the stored occurrences as PanelRawHit
 // number i at raw[(s nslots + w) max_hits + i].  A slot without a text writes nothing.
-struct PanelScanArgs {
-    const uint64_t* pl_m;  const int64_t* m_off;  const int32_t* m_len;  const int32_t* m_bound;
-    int32_t n_members, per_slice;
-    const uint64_t* pl_t;  const int64_t* pl_t_off;  const int32_t* t_len;
-    int32_t nslots;  const int32_t* w_pair;  const int32_t* w_c0;  const int32_t* w_c1;
+struct PanelScanArgs : PanelSweepArgs {
+    const int32_t* w_c0;  const int32_t* w_c1;
     int32_t max_hits;
     int32_t* part;
     PanelRawHit* raw;

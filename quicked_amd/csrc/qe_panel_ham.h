@@ -37,9 +37,7 @@ QE_S_HD void panel_ham_sweep(const uint64_t* pp, int m, const uint64_t* tp, int 
     const int nstarts = n < m ? 0 : (mode == SEARCH_PREFIX ? 1 : n - m + 1);
     if (nstarts <= 0) return;
     uint64_t p[NB][Eq::W], mask[NB];
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+    QE_S_UNROLL
     for (int b = 0; b < NB; ++b) {
         Eq::pattern_rows(pp, m, b, p[b]);
         const int rows = search_rows(b, m);
@@ -47,24 +45,18 @@ QE_S_HD void panel_ham_sweep(const uint64_t* pp, int m, const uint64_t* tp, int 
     }
     const int last = (n - 1) >> 6;
     uint64_t t[NB + 1][Eq::W];
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+    QE_S_UNROLL
     for (int i = 0; i < NB; ++i) panel_ham_word<Eq>(tp, i, last, t[i]);
     for (int s0 = 0; s0 < nstarts; s0 += 64) {
         panel_ham_word<Eq>(tp, (s0 >> 6) + NB, last, t[NB]);
         const int cnt = nstarts - s0 < 64 ? nstarts - s0 : 64;
         for (int j = 0; j < cnt; ++j) {
             int32_t v = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+            QE_S_UNROLL
             for (int b = 0; b < NB; ++b)
                 if (b < nb) v += search_popc(~Eq::eq_pos(p[b], t[b]) & mask[b]);
             out.put(s0 + j + m, v);
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+            QE_S_UNROLL
             for (int i = 0; i < NB; ++i)
                 for (int k = 0; k < Eq::W; ++k) t[i][k] = (t[i][k] >> 1) | (t[i + 1][k] << 63);
             for (int k = 0; k < Eq::W; ++k) t[NB][k] >>= 1;
@@ -91,16 +83,12 @@ QE_S_HD void panel_ham_member(const uint64_t* pp, int m, int bound, const uint64
 template <class Eq>
 QE_S_HD void panel_ham_text(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelKeeper& keep, uint32_t& steps,
                             int32_t* m_score, int32_t* m_end) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         int32_t score = -1, end = -1;
-        if (nb <= 1) panel_ham_member<1, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
-        else if (nb == 2) panel_ham_member<2, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_ham_member<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
+        panel_ham_member<NB, Eq>(pp, m, bound, tp, n, mode, score, end, steps);
         if (m_score) { m_score[p] = score; m_end[p] = end; }
         keep.take(score >= 0 ? p : -1, score, end);
-    }
+    });
 }
 
 // ---- every occurrence (quicked_batch_run_panel_all): the valley rule over scalar values.  qe_search.h's scan reads row m as
@@ -128,14 +116,10 @@ QE_S_HD void panel_ham_member_hits(const uint64_t* pp, int m, int bound, const u
 // One text against the members [p0, p1): panel_text_hits' arguments and results under this file's definition
 template <class Eq>
 QE_S_HD void panel_ham_text_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int mode, PanelHamScan& H, uint32_t& steps) {
-    for (int p = p0; p < p1; ++p) {
-        const int m = P.len[p], bound = P.bound[p], nb = search_blocks(m);
-        const uint64_t* pp = P.pl + Eq::offset(P.off[p]);
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
         H.sink.member = p;
-        if (nb <= 1) panel_ham_member_hits<1, Eq>(pp, m, bound, tp, n, mode, H, steps);
-        else if (nb == 2) panel_ham_member_hits<2, Eq>(pp, m, bound, tp, n, mode, H, steps);
-        else if (nb <= QE_SEARCH_REG_BLOCKS) panel_ham_member_hits<QE_SEARCH_REG_BLOCKS, Eq>(pp, m, bound, tp, n, mode, H, steps);
-    }
+        panel_ham_member_hits<NB, Eq>(pp, m, bound, tp, n, mode, H, steps);
+    });
 }
 
 // ---- text_start = text_end - m, behind the unchanged k_panel_reduce / k_panel_hits_expand in their PREFIX form (no start

@@ -64,6 +64,11 @@
 #else
 #define QE_S_HD inline
 #endif
+#if defined(__HIPCC__)
+#define QE_S_UNROLL _Pragma("unroll")      // before a loop over a store's blocks: hipcc's pragma, nothing for g++
+#else
+#define QE_S_UNROLL
+#endif
 
 namespace qe {
 
@@ -384,10 +389,12 @@ struct SearchRegStore {
     QE_S_HD uint64_t& M(int b) { return mv[b]; }
     QE_S_HD int32_t& S(int b) { return s[b]; }
     QE_S_HD void planes(int b, uint64_t (&p)[E::W]) { for (int k = 0; k < E::W; ++k) p[k] = pl[b][k]; }
+    QE_S_HD void clear() {
+        QE_S_UNROLL
+        for (int b = 0; b < NB; ++b) { pv[b] = mv[b] = 0; s[b] = 0; }
+    }
     QE_S_HD void load(const uint64_t* pp, int m) {
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
+        QE_S_UNROLL
         for (int b = 0; b < NB; ++b) E::pattern_rows(pp, m, b, pl[b]);
     }
 };

@@ -1205,16 +1205,34 @@ static void hits_total(const quicked_batch& B, Context& C, HitsOut& O, const int
     O.total = tot[0];
 }
 // The start pass of the panel runs: k_search<4, Eq> in its start-pass form (PREFIX, the largest end, bound and window from the
-// forward pass's score / end on the device) over nt tasks laid out as arrays, one launch, timed as kind 0
-static void launch_start_pass(Context& C, int eq, const PairView& PV, size_t nt, const int32_t* pair, const int32_t* m, const int32_t* n,
-                              const int32_t* score, const int32_t* end, int32_t* o_start, u32* o_adv) {
+// forward pass's score / end on the device) over nt tasks laid out as arrays, one launch, timed as kind 0.
+// Its arrays: {pair | m | n | score | end | start} in one take, the kernel before the pass writes the first five (into(): its
+// argument block's o_* fields); start is preset to -1, which a lane that finds nothing leaves, and adv -- the block steps per
+// task, a seventh stretch of the take or (adv_apart, the runs that fetch it: HitsOut / PanelOut::d_adv2) a take of its own -- to 0
+struct StartTasks {
+    size_t nt = 0;                                  // 0: a run without the pass
+    int32_t *pair = nullptr, *m = nullptr, *n = nullptr, *score = nullptr, *end = nullptr, *start = nullptr;
+    u32* adv = nullptr;
+    template <class A> void into(A& a) const { a.o_pair = pair; a.o_m = m; a.o_n = n; a.o_score = score; a.o_end = end; }
+};
+static StartTasks take_start_tasks(Context& C, size_t nt, bool adv_apart) {
+    StartTasks t;
+    t.nt = nt;
+    int32_t* q = C.scratch_p->take<int32_t>((adv_apart ? 6 : 7) * nt);
+    t.pair = q; t.m = q + nt; t.n = q + 2 * nt; t.score = q + 3 * nt; t.end = q + 4 * nt; t.start = q + 5 * nt;
+    t.adv = adv_apart ? C.scratch_p->take<u32>(nt) : (u32*)(q + 6 * nt);
+    HIP_CHECK(hipMemsetAsync(t.start, 0xFF, nt * sizeof(int32_t), C.stream));
+    HIP_CHECK(hipMemsetAsync(t.adv, 0, nt * sizeof(u32), C.stream));
+    return t;
+}
+static void launch_start_pass(Context& C, int eq, const PairView& PV, const StartTasks& t) {
     SearchArgs s{};
     s.P = PV;
-    s.T.ntasks = (int32_t)nt; s.T.pair = pair; s.T.m = m; s.T.n = n; s.T.cutoff = score;
+    s.T.ntasks = (int32_t)t.nt; s.T.pair = t.pair; s.T.m = t.m; s.T.n = t.n; s.T.cutoff = t.score;
     s.mode = SEARCH_PREFIX; s.flags = SEARCH_LARGEST_END;
-    s.in_score = score; s.in_end = end; s.o_start = o_start; s.o_adv = o_adv;
+    s.in_score = t.score; s.in_end = t.end; s.o_start = t.start; s.o_adv = t.adv;
     TimedLaunches tl(C, 0);
-    launch_search(C, eq, 3, s, (nt + 63) / 64);
+    launch_search(C, eq, 3, s, (t.nt + 63) / 64);
     tl.end();
 }
 static HitsOut run_search_hits(quicked_batch& B, Context& C, const SearchLists& S, int mode, int max_hits, int eq = 0) {
@@ -1330,15 +1348,26 @@ static size_t panel_plane_words(const PanelRun& pr) {
     for (int32_t p = 0; p < pr.n_patterns; ++p) w += 3 * ((size_t)(pr.len[p] + 63) / 64 + 2);
     return w;
 }
+// the non-empty texts of the batch: the ones a panel run gives a slot
+static size_t panel_texts(const quicked_batch& B) {
+    size_t texts = 0;
+    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    return texts;
+}
+// a panel of K members cut into `want` slices at the most: the members per slice, and the slices that makes
+struct PanelCut { int per_slice, nslices; };
+static PanelCut panel_cut(int K, int want) {
+    const int per_slice = (K + want - 1) / want;
+    return PanelCut{per_slice, (K + per_slice - 1) / per_slice};
+}
 // What the panel runs take from their pools alike (the planner's fixed needs): the panel's bytes, tables and planes (forward and,
 // INFIX, reversed), a flagged run's four-plane words of the texts, the takes' padding.  -> nslots: the non-empty texts in whole
 // waves, as panel_upload lays them out
 static size_t panel_shared_bytes(const quicked_batch& B, const SearchRun& sr, size_t& nslots) {
     const PanelRun& pr = *sr.panel;
-    size_t texts = 0, pool = 0;
-    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
+    size_t pool = 0;
     for (int32_t p = 0; p < pr.n_patterns; ++p) pool += (size_t)pr.len[p];
-    nslots = (texts + 63) / 64 * 64;
+    nslots = (panel_texts(B) + 63) / 64 * 64;
     const size_t K = (size_t)pr.n_patterns, passes = sr.mode == SEARCH_INFIX ? 2 : 1;
     size_t b = pool + 64 + K * 32 + passes * (size_t)iupac_offset((int64_t)panel_plane_words(pr) + 24) * sizeof(u64);
     if (sr.eq) b += passes * ((size_t)iupac_offset((int64_t)B.pl_t_words) + 16) * sizeof(u64);
@@ -1441,6 +1470,24 @@ static const u64* panel_planes(quicked_batch& B, Context& C, const PanelDev& D, 
     HIP_CHECK(hipGetLastError());
     return (const u64*)pl;
 }
+// what every sweep kernel reads first (PanelSweepArgs): the panel cut into slices of per_slice members over the planes pl_m, the
+// texts' planes pl_t, the text slots (run_search_panel_scan puts its window slots in their place)
+static void panel_sweep_args(PanelSweepArgs& a, const quicked_batch& B, const PanelDev& D, int K, int per_slice, const u64* pl_m, const u64* pl_t) {
+    a.pl_m = pl_m; a.m_off = D.d_pl_off; a.m_len = D.d_len; a.m_bound = D.d_bound;
+    a.n_members = K; a.per_slice = per_slice;
+    a.pl_t = pl_t; a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
+    a.nslots = (int32_t)D.nslots; a.text = D.d_text;
+}
+// A sweep's launch, k3 / k4 the kernel under the library's equality / a flagged run's: slot groups x slices, four groups per
+// workgroup, one per SIMD of its CU, and launch_groups' claim on the CU's LDS: at most two of these workgroups share a CU,
+// whichever slices they belong to
+template <class A>
+static void launch_panel_sweep(Context& C, int eq, void (*k3)(A), void (*k4)(A), const A& a, size_t ngroups, int nslices) {
+    const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
+    if (eq) hipLaunchKernelGGL(k4, grid, dim3(256), 54 * 1024, C.stream, a);
+    else hipLaunchKernelGGL(k3, grid, dim3(256), 54 * 1024, C.stream, a);
+    HIP_CHECK(hipGetLastError());
+}
 static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
     const int K = pr.n_patterns, eq = sr.eq;
@@ -1452,18 +1499,14 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     // and text_start = text_end - m behind it)
     const bool start_pass = infix && !sr.no_indels;
     if (O.text.empty()) return O;
-    const size_t n = (size_t)B.n, nslots = D.nslots, ngroups = D.ngroups;
-    const int64_t* d_pl_off = D.d_pl_off;
-    const int32_t *d_len = D.d_len, *d_bound = D.d_bound;
-    int32_t* d_text = D.d_text;
-    auto panel_planes = [&](bool reversed) { return qe::panel_planes(B, C, D, K, eq, reversed); };
+    const size_t n = (size_t)B.n, nslots = D.nslots;
     // ---- the forward pass
-    const int want = panel_slices(C, ngroups, K), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    const PanelCut cut = panel_cut(K, panel_slices(C, D.ngroups, K));
+    const int nslices = cut.nslices;
     PanelArgs a{};
-    a.pl_m = panel_planes(false); a.m_off = d_pl_off; a.m_len = d_len; a.m_bound = d_bound;
-    a.n_members = K; a.per_slice = per_slice;
-    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
-    a.nslots = (int32_t)nslots; a.text = d_text; a.mode = sr.mode;
+    const u64* pl_m = panel_planes(B, C, D, K, eq, false);
+    panel_sweep_args(a, B, D, K, cut.per_slice, pl_m, panel_text_planes(B, C, eq, false));
+    a.mode = sr.mode;
     a.part = C.scratch_p->take<int32_t>(6 * (size_t)nslices * nslots);
     if (pr.matrix) {
         O.d_mscore = C.scratch_p->take<int32_t>(2 * n * (size_t)K);
@@ -1476,48 +1519,37 @@ static PanelOut run_search_panel(quicked_batch& B, Context& C, const SearchRun& 
     O.d_adv = C.scratch_p->take<u32>(nslots);
     HIP_CHECK(hipMemsetAsync(O.d_adv, 0, nslots * sizeof(u32), C.stream));
     TimedLaunches tl(C, 0);
-    {
-        // four text groups per workgroup, one per SIMD of its CU, and launch_groups' claim on the CU's LDS: at most two of
-        // these workgroups share a CU, whichever slices they belong to
-        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
-        if (sr.no_indels) {
-            if (eq) hipLaunchKernelGGL(k_panel_ham<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
-            else hipLaunchKernelGGL(k_panel_ham<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
-        } else if (eq) hipLaunchKernelGGL(k_search_panel<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
-        else hipLaunchKernelGGL(k_search_panel<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
-    }
-    HIP_CHECK(hipGetLastError());
+    if (sr.no_indels) launch_panel_sweep(C, eq, k_panel_ham<SearchEq3>, k_panel_ham<SearchEqIupac>, a, D.ngroups, nslices);
+    else launch_panel_sweep(C, eq, k_search_panel<SearchEq3>, k_search_panel<SearchEqIupac>, a, D.ngroups, nslices);
     tl.end();
     // ---- the reduction, and the start pass's tasks
     PanelReduceArgs r{};
     r.nslots = (int32_t)nslots; r.nslices = nslices; r.infix = start_pass ? 1 : 0;
-    r.text = d_text; r.part = a.part; r.m_len = d_len; r.m_off = d_pl_off; r.t_len = B.d_t_len;
+    r.text = D.d_text; r.part = a.part; r.m_len = D.d_len; r.m_off = D.d_pl_off; r.t_len = B.d_t_len;
     r.hits = O.d_hits; r.o_adv = O.d_adv;
-    int32_t* o_start = nullptr;
+    StartTasks st;
     if (start_pass) {
-        int32_t* q = C.scratch_p->take<int32_t>(6 * nslots);
-        r.o_pair = q; r.o_m = q + nslots; r.o_n = q + 2 * nslots; r.o_score = q + 3 * nslots; r.o_end = q + 4 * nslots; o_start = q + 5 * nslots;
-        HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
+        st = take_start_tasks(C, nslots, true);
+        st.into(r);
+        O.d_adv2 = st.adv;
         r.o_plp_off = C.scratch_p->take<int64_t>(n);
         HIP_CHECK(hipMemsetAsync(r.o_plp_off, 0, n * sizeof(int64_t), C.stream));
-        O.d_adv2 = C.scratch_p->take<u32>(nslots);
-        HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nslots * sizeof(u32), C.stream));
     }
     hipLaunchKernelGGL(k_panel_reduce, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, r);
     HIP_CHECK(hipGetLastError());
     if (sr.no_indels && infix) {
-        hipLaunchKernelGGL(k_panel_ham_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, (int64_t)n, d_len, O.d_hits);
+        hipLaunchKernelGGL(k_panel_ham_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, (int64_t)n, D.d_len, O.d_hits);
         HIP_CHECK(hipGetLastError());
     }
     if (!start_pass) return O;
     // ---- the start pass: one lane per text over the window that ends at its best member's text_end, reversed
     if (!eq) ensure_reversed(B, C);
     PairView PV = pair_view(B, true);
-    PV.pl_p = panel_planes(true); PV.pl_p_off = r.o_plp_off;
+    PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = r.o_plp_off;
     PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = B.d_plt_off;
-    launch_start_pass(C, eq, PV, nslots, r.o_pair, r.o_m, r.o_n, r.o_score, r.o_end, o_start, O.d_adv2);
-    hipLaunchKernelGGL(k_panel_finish, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, (int)nslots, (const int32_t*)d_text,
-                       (const int32_t*)r.o_pair, (const int32_t*)o_start, O.d_hits);
+    launch_start_pass(C, eq, PV, st);
+    hipLaunchKernelGGL(k_panel_finish, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, (int)nslots, (const int32_t*)D.d_text,
+                       (const int32_t*)st.pair, (const int32_t*)st.start, O.d_hits);
     HIP_CHECK(hipGetLastError());
     return O;
 }
@@ -1550,9 +1582,7 @@ static size_t panel_align_waves(const SearchRun& sr, size_t waves) {
 // what is fixed of it before the total is known: the history at the most occurrences the run can store
 static size_t panel_align_fixed_bytes(const quicked_batch& B, const SearchRun& sr) {
     if (!sr.cigars) return 0;
-    size_t texts = 0;
-    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
-    return panel_align_waves(sr, (texts * (size_t)sr.max_hits + 63) / 64) * panel_align_wave_bytes(sr) + 1024;
+    return panel_align_waves(sr, (panel_texts(B) * (size_t)sr.max_hits + 63) / 64) * panel_align_wave_bytes(sr) + 1024;
 }
 static void run_panel_align(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const u64* pl_m, const u64* pl_t, HitsOut& O) {
     const size_t nh = (size_t)O.total;
@@ -1624,12 +1654,8 @@ static void run_panel_tails(quicked_batch& B, Context& C, const SearchRun& sr, c
     g.nslots = (int32_t)nslots; g.nslices = nslices; g.text = D.d_text; g.tpart = ta.tpart; g.t_len = B.d_t_len;
     g.plane_stride = 3 * (int64_t)panel_tallest_rows(*sr.panel);
     g.tails = O.d_tails; g.o_rows = O.d_tail_rows;
-    int32_t* q = C.scratch_p->take<int32_t>(7 * nslots);
-    g.o_pair = q; g.o_m = q + nslots; g.o_n = q + 2 * nslots; g.o_score = q + 3 * nslots; g.o_end = q + 4 * nslots;
-    int32_t* o_start = q + 5 * nslots;
-    u32* o_adv = (u32*)(q + 6 * nslots);
-    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
-    HIP_CHECK(hipMemsetAsync(o_adv, 0, nslots * sizeof(u32), C.stream));
+    const StartTasks st = take_start_tasks(C, nslots, false);
+    st.into(g);
     g.o_plp_off = C.scratch_p->take<int64_t>(n);
     HIP_CHECK(hipMemsetAsync(g.o_plp_off, 0, n * sizeof(int64_t), C.stream));
     const dim3 grid((unsigned)((nslots + 255) / 256));
@@ -1644,8 +1670,8 @@ static void run_panel_tails(quicked_batch& B, Context& C, const SearchRun& sr, c
     PairView PV = pair_view(B, true);
     PV.pl_p = w.pool; PV.pl_p_off = g.o_plp_off;
     PV.pl_t = pl_t_rev; PV.pl_t_off = B.d_plt_off;
-    launch_start_pass(C, eq, PV, nslots, g.o_pair, g.o_m, g.o_n, g.o_score, g.o_end, o_start, o_adv);
-    hipLaunchKernelGGL(k_panel_tails_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)g.o_pair, (const int32_t*)o_start, O.d_tails);
+    launch_start_pass(C, eq, PV, st);
+    hipLaunchKernelGGL(k_panel_tails_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)st.pair, (const int32_t*)st.start, O.d_tails);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1668,19 +1694,13 @@ static size_t panel_heads_fixed_bytes(const quicked_batch& B, const SearchRun& s
 static void run_panel_heads(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const PanelHitsArgs& a, int nslices, const u64* pl_m_rev, HitsOut& O) {
     const size_t n = (size_t)B.n, nslots = D.nslots;
     const int eq = sr.eq;
-    PanelHeadsArgs h{};
-    h.pl_m_rev = pl_m_rev; h.m_off = a.m_off; h.m_len = a.m_len; h.m_bound = a.m_bound;
-    h.n_members = a.n_members; h.per_slice = a.per_slice;
-    h.pl_t = a.pl_t; h.pl_t_off = a.pl_t_off; h.t_len = a.t_len;
-    h.nslots = a.nslots; h.text = a.text; h.min_overlap = B.head_min_overlap;
+    PanelHeadsArgs h{a};                            // the occurrence kernel's panel, slices and slots ...
+    h.pl_m = pl_m_rev;                              // ... over the members' reversed planes
+    h.min_overlap = B.head_min_overlap;
     h.hpart = C.scratch_p->take<int32_t>(5 * (size_t)nslices * nslots);
     {
         TimedLaunches tl(C, 0);
-        // k_search_panel's launch shape, as k_panel_hits
-        const dim3 grid((unsigned)((D.ngroups + 3) / 4), (unsigned)nslices);
-        if (eq) hipLaunchKernelGGL(k_panel_heads<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, h);
-        else hipLaunchKernelGGL(k_panel_heads<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, h);
-        HIP_CHECK(hipGetLastError());
+        launch_panel_sweep(C, eq, k_panel_heads<SearchEq3>, k_panel_heads<SearchEqIupac>, h, D.ngroups, nslices);
         tl.end();
     }
     O.d_heads = C.scratch_p->take<int32_t>(4 * n);
@@ -1691,12 +1711,8 @@ static void run_panel_heads(quicked_batch& B, Context& C, const SearchRun& sr, c
     g.nslots = (int32_t)nslots; g.nslices = nslices; g.text = D.d_text; g.hpart = h.hpart; g.t_len = B.d_t_len;
     g.plane_stride = 3 * (int64_t)panel_tallest_rows(*sr.panel);
     g.heads = O.d_heads; g.o_steps = O.d_head_steps; g.o_rows = O.d_head_steps + nslots;
-    int32_t* q = C.scratch_p->take<int32_t>(7 * nslots);
-    g.o_pair = q; g.o_m = q + nslots; g.o_n = q + 2 * nslots; g.o_score = q + 3 * nslots; g.o_end = q + 4 * nslots;
-    int32_t* o_start = q + 5 * nslots;
-    u32* o_adv = (u32*)(q + 6 * nslots);
-    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nslots * sizeof(int32_t), C.stream));
-    HIP_CHECK(hipMemsetAsync(o_adv, 0, nslots * sizeof(u32), C.stream));
+    const StartTasks st = take_start_tasks(C, nslots, false);
+    st.into(g);
     g.o_plp_off = C.scratch_p->take<int64_t>(n);
     HIP_CHECK(hipMemsetAsync(g.o_plp_off, 0, n * sizeof(int64_t), C.stream));
     const dim3 grid((unsigned)((nslots + 255) / 256));
@@ -1711,8 +1727,8 @@ static void run_panel_heads(quicked_batch& B, Context& C, const SearchRun& sr, c
     PairView PV = pair_view(B, false);
     PV.pl_p = w.pool; PV.pl_p_off = g.o_plp_off;
     PV.pl_t = a.pl_t; PV.pl_t_off = B.d_plt_off;
-    launch_start_pass(C, eq, PV, nslots, g.o_pair, g.o_m, g.o_n, g.o_score, g.o_end, o_start, o_adv);
-    hipLaunchKernelGGL(k_panel_heads_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)g.o_pair, (const int32_t*)o_start, O.d_heads);
+    launch_start_pass(C, eq, PV, st);
+    hipLaunchKernelGGL(k_panel_heads_finish, grid, dim3(256), 0, C.stream, (int)nslots, (const int32_t*)st.pair, (const int32_t*)st.start, O.d_heads);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1738,9 +1754,7 @@ static int panel_hits_slices(const Context& C, size_t nslots, int K, int max_hit
 }
 // the room a queued run takes for its records: min(max_total, non-empty texts x max_hits) -- no run stores more than the latter
 static int64_t panel_queue_cap(const quicked_batch& B, const SearchRun& sr) {
-    int64_t texts = 0;
-    for (int64_t i = 0; i < B.n; ++i) texts += B.t_len[(size_t)i] > 0;
-    return std::min<int64_t>(sr.queue_total, texts * (int64_t)sr.max_hits);
+    return std::min<int64_t>(sr.queue_total, (int64_t)panel_texts(B) * (int64_t)sr.max_hits);
 }
 // what such a run takes from its pool before the total is known (the planner's fixed needs): panel_shared_bytes, the slice
 // partials and the raw buffer at the slices the host would choose, the per-pair arrays.  The arrays sized by the total (16
@@ -1755,6 +1769,63 @@ static size_t panel_hits_fixed_bytes(const quicked_batch& B, const Context& C, c
     if (sr.queue_total > 0) b += (size_t)panel_queue_cap(B, sr) * (sr.mode == SEARCH_INFIX ? 60 : 16) + 8 * 512;
     return b + panel_align_fixed_bytes(B, sr) + panel_tails_fixed_bytes(B, sr, nslots, nslices) + panel_heads_fixed_bytes(B, sr, nslots, nslices);
 }
+// the reversed planes of a panel run, packed when a pass first asks for them: the panel's for the occurrences' start pass and
+// the heads' sweep, the texts' for the start passes
+struct PanelReversed {
+    quicked_batch& B; Context& C; const PanelDev& D; int K, eq;
+    const u64 *pl_m = nullptr, *pl_t = nullptr;
+    const u64* members() { if (!pl_m) pl_m = panel_planes(B, C, D, K, eq, true); return pl_m; }
+    const u64* texts() {
+        if (!pl_t) { if (!eq) ensure_reversed(B, C); pl_t = panel_text_planes(B, C, eq, true); }
+        return pl_t;
+    }
+};
+// Behind the offsets, for both all-occurrences panel runs: the records' array at O.total (queued: O.cap) places, the run's own
+// expand kernel -- expand(e), over its argument block e, whose fields both blocks have alike are filled here --, INFIX the
+// start pass with one task per place and the finish step, the mismatch-only run's finish step in their stead, a queued run's
+// clamp, the strings.  a: the forward pass's planes
+template <class E, class Expand>
+static void panel_occ_records(quicked_batch& B, Context& C, const SearchRun& sr, const PanelDev& D, const PanelSweepArgs& a, PanelReversed& R,
+                              bool infix, E& e, Expand expand, HitsOut& O) {
+    const bool queued = O.cap > 0;
+    const size_t nh = (size_t)(queued ? O.cap : O.total);
+    const int eq = sr.eq;
+    O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
+    e.off = O.d_off; e.m_len = D.d_len; e.m_off = D.d_pl_off; e.t_len = B.d_t_len; e.t_off = B.d_plt_off; e.hits = O.d_hits;
+    StartTasks st;
+    if (infix) {
+        st = take_start_tasks(C, nh, true);
+        st.into(e);
+        O.d_adv2 = st.adv;
+        if (queued) HIP_CHECK(hipMemsetAsync(st.pair, 0xFF, nh * sizeof(int32_t), C.stream));      // the task slots past the total: no pair, so no lane
+        e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
+        e.o_plt_off = e.o_plp_off + nh;
+    }
+    expand(e);
+    HIP_CHECK(hipGetLastError());
+    const dim3 grid((unsigned)((nh + 255) / 256));
+    if (sr.no_indels && sr.mode == SEARCH_INFIX) {
+        hipLaunchKernelGGL(k_panel_ham_hits_finish, grid, dim3(256), 0, C.stream, (int64_t)nh, D.d_len, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (infix) {
+        // ---- the start pass: one lane per stored occurrence over its window, reversed
+        PairView PV = pair_view(B, true);
+        PV.pl_p = R.members(); PV.pl_p_off = e.o_plp_off;
+        PV.pl_t = R.texts(); PV.pl_t_off = e.o_plt_off;
+        launch_start_pass(C, eq, PV, st);
+        if (queued) hipLaunchKernelGGL(k_panel_queue_finish, grid, dim3(256), 0, C.stream, (const int64_t*)(O.d_off + (size_t)B.n), (int64_t)O.cap, (const int32_t*)st.start, O.d_hits);
+        else hipLaunchKernelGGL(k_panel_hits_finish, grid, dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)st.start, O.d_hits);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (queued) {
+        // ---- the offsets clamped to the cap, W and the real lengths of the records and their step counts beside them
+        O.d_queue = C.scratch_p->take<int64_t>(4);
+        hipLaunchKernelGGL(k_panel_queue_clamp, dim3((unsigned)(((size_t)B.n + 256) / 256)), dim3(256), 0, C.stream, (int64_t)B.n, (int64_t)O.cap, O.d_off, O.d_queue);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
+}
 static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
     const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
@@ -1765,14 +1836,14 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     const PanelDev D = panel_upload(B, C, sr);
     O.task_pair = D.text;
     if (O.task_pair.empty()) return O;
-    const size_t nslots = D.nslots, ngroups = D.ngroups;
+    const size_t nslots = D.nslots;
     // ---- the forward pass
-    const int want = panel_hits_slices(C, nslots, K, max_hits), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    const PanelCut cut = panel_cut(K, panel_hits_slices(C, nslots, K, max_hits));
+    const int nslices = cut.nslices;
     PanelHitsArgs a{};
-    a.pl_m = panel_planes(B, C, D, K, eq, false); a.m_off = D.d_pl_off; a.m_len = D.d_len; a.m_bound = D.d_bound;
-    a.n_members = K; a.per_slice = per_slice;
-    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
-    a.nslots = (int32_t)nslots; a.text = D.d_text; a.mode = sr.mode; a.max_hits = max_hits;
+    const u64* pl_m = panel_planes(B, C, D, K, eq, false);
+    panel_sweep_args(a, B, D, K, cut.per_slice, pl_m, panel_text_planes(B, C, eq, false));
+    a.mode = sr.mode; a.max_hits = max_hits;
     a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
     a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
     int32_t* const d_plen = hits_arrays(C, O, (size_t)B.n, nslots);
@@ -1780,86 +1851,30 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
     PanelTailsArgs ta{};
     if (sr.tails) { ta.H = a; ta.min_overlap = B.tail_min_overlap; ta.tpart = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots); }
     TimedLaunches tl(C, 0);
-    {
-        // k_search_panel's launch shape: four text groups per workgroup and launch_groups' claim on the CU's LDS
-        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
-        if (sr.tails) {
-            if (eq) hipLaunchKernelGGL(k_panel_tails<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, ta);
-            else hipLaunchKernelGGL(k_panel_tails<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, ta);
-        } else if (sr.no_indels) {
-            if (eq) hipLaunchKernelGGL(k_panel_ham_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
-            else hipLaunchKernelGGL(k_panel_ham_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
-        } else if (eq) hipLaunchKernelGGL(k_panel_hits<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
-        else hipLaunchKernelGGL(k_panel_hits<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
-    }
-    HIP_CHECK(hipGetLastError());
+    if (sr.tails) launch_panel_sweep(C, eq, k_panel_tails<SearchEq3>, k_panel_tails<SearchEqIupac>, ta, D.ngroups, nslices);
+    else if (sr.no_indels) launch_panel_sweep(C, eq, k_panel_ham_hits<SearchEq3>, k_panel_ham_hits<SearchEqIupac>, a, D.ngroups, nslices);
+    else launch_panel_sweep(C, eq, k_panel_hits<SearchEq3>, k_panel_hits<SearchEqIupac>, a, D.ngroups, nslices);
     tl.end();
-    // the texts' reversed planes, packed once for the start passes that want them
-    const u64* pl_t_rev = nullptr;
-    auto text_planes_reversed = [&]() {
-        if (!pl_t_rev) { if (!eq) ensure_reversed(B, C); pl_t_rev = panel_text_planes(B, C, eq, true); }
-        return pl_t_rev;
-    };
-    // ... and the panel's, for the occurrences' start pass and the heads' sweep
-    const u64* pl_m_rev = nullptr;
-    auto panel_planes_reversed = [&]() {
-        if (!pl_m_rev) pl_m_rev = panel_planes(B, C, D, K, eq, true);
-        return pl_m_rev;
-    };
+    PanelReversed R{B, C, D, K, eq};
     // ---- counts per pair, offsets in the order of the pairs (a pair without a slot has -1 + 1 = 0 stored), the total
     PanelHitsCountArgs c{};
     c.nslots = (int32_t)nslots; c.nslices = nslices; c.max_hits = max_hits; c.text = D.d_text; c.part = a.part;
     c.found = O.d_found; c.best = O.d_best; c.len = d_plen; c.o_adv = O.d_adv;
     hipLaunchKernelGGL(k_panel_hits_count, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, c);
-    if (sr.tails) run_panel_tails(B, C, sr, D, ta, nslices, text_planes_reversed(), O);      // (before the total: it needs none)
-    if (sr.heads) run_panel_heads(B, C, sr, D, a, nslices, panel_planes_reversed(), O);      // (likewise; no reversed text planes)
+    if (sr.tails) run_panel_tails(B, C, sr, D, ta, nslices, R.texts(), O);        // (before the total: it needs none)
+    if (sr.heads) run_panel_heads(B, C, sr, D, a, nslices, R.members(), O);       // (likewise; no reversed text planes)
     // (a queued run: the total stays on the device and the arrays it sizes are taken at the run's cap instead)
     const bool queued = sr.queue_total > 0;
     if (queued) { hits_offsets(B, C, O, d_plen, B.d_t_len); O.total = -1; O.cap = panel_queue_cap(B, sr); }
     else hits_total(B, C, O, d_plen, B.d_t_len);
     if (!queued && O.total <= 0) return O;
-    const size_t nh = (size_t)(queued ? O.cap : O.total);
-    O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
     PanelHitsExpandArgs e{};
     e.nslots = (int32_t)nslots; e.nslices = nslices; e.max_hits = max_hits; e.infix = infix ? 1 : 0;
-    e.text = D.d_text; e.part = a.part; e.raw = a.raw; e.off = O.d_off;
-    e.m_len = D.d_len; e.m_off = D.d_pl_off; e.t_len = B.d_t_len; e.t_off = B.d_plt_off; e.hits = O.d_hits;
-    int32_t* o_start = nullptr;
-    if (infix) {
-        int32_t* q = C.scratch_p->take<int32_t>(6 * nh);
-        e.o_pair = q; e.o_m = q + nh; e.o_n = q + 2 * nh; e.o_score = q + 3 * nh; e.o_end = q + 4 * nh; o_start = q + 5 * nh;
-        HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
-        if (queued) HIP_CHECK(hipMemsetAsync(e.o_pair, 0xFF, nh * sizeof(int32_t), C.stream));      // the task slots past the total: no pair, so no lane
-        e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
-        e.o_plt_off = e.o_plp_off + nh;
-        O.d_adv2 = C.scratch_p->take<u32>(nh);
-        HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
-    }
-    if (queued) hipLaunchKernelGGL(k_panel_queue_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e, (int64_t)O.cap);
-    else hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, e);
-    HIP_CHECK(hipGetLastError());
-    if (sr.no_indels && sr.mode == SEARCH_INFIX) {
-        hipLaunchKernelGGL(k_panel_ham_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, D.d_len, O.d_hits);
-        HIP_CHECK(hipGetLastError());
-    }
-    if (infix) {
-        // ---- the start pass: one lane per stored occurrence over its window, reversed
-        if (!eq) ensure_reversed(B, C);
-        PairView PV = pair_view(B, true);
-        PV.pl_p = panel_planes_reversed(); PV.pl_p_off = e.o_plp_off;
-        PV.pl_t = text_planes_reversed(); PV.pl_t_off = e.o_plt_off;
-        launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
-        if (queued) hipLaunchKernelGGL(k_panel_queue_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (const int64_t*)(O.d_off + (size_t)B.n), (int64_t)O.cap, (const int32_t*)o_start, O.d_hits);
-        else hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
-        HIP_CHECK(hipGetLastError());
-    }
-    if (queued) {
-        // ---- the offsets clamped to the cap, W and the real lengths of the records and their step counts beside them
-        O.d_queue = C.scratch_p->take<int64_t>(4);
-        hipLaunchKernelGGL(k_panel_queue_clamp, dim3((unsigned)(((size_t)B.n + 256) / 256)), dim3(256), 0, C.stream, (int64_t)B.n, (int64_t)O.cap, O.d_off, O.d_queue);
-        HIP_CHECK(hipGetLastError());
-    }
-    if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
+    e.text = D.d_text; e.part = a.part; e.raw = a.raw;
+    panel_occ_records(B, C, sr, D, a, R, infix, e, [&](const PanelHitsExpandArgs& x) {
+        if (queued) hipLaunchKernelGGL(k_panel_queue_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, x, (int64_t)O.cap);
+        else hipLaunchKernelGGL(k_panel_hits_expand, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, C.stream, x);
+    }, O);
     return O;
 }
 
@@ -1870,7 +1885,7 @@ static HitsOut run_search_panel_hits(quicked_batch& B, Context& C, const SearchR
 // k_panel_scan_sums (one thread per slice and text) and k_panel_scan_count (one per text) merge the counts and leave every
 // slice's rank base; k_scan_offsets and the total
 // as above; k_panel_scan_expand (one thread per lane) ranks the records among their text's and writes them and their
-// start-pass tasks; the start pass and k_panel_hits_finish are the run's above, unchanged.
+// start-pass tasks; the start pass and k_panel_hits_finish are the run's above (panel_occ_records).
 //
 // The library's window (window == 0).  A multiple of 64; enough window groups that groups x slices reach about twice the
 // resident wave slots with the panel cut as finely as it can be (slices cost no warm-up, windows do): groups = ceil(2 slots2
@@ -1933,7 +1948,7 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     // ---- the window slots
     PanelScanTable T;
     panel_scan_table(B, D.text, panel_scan_window(B, C, sr), T);
-    const size_t nslots = T.w_pair.size(), ngroups = nslots / 64;
+    const size_t nslots = T.w_pair.size();
     // one block, one copy: {w_pair | w_text | w_c0 | w_c1 | first_slot | nwin}, every array on a 16-byte boundary (the copy kernel
     // moves whole uint4 and rounds a copy's end up)
     const size_t n4 = (n + 3) & ~(size_t)3;
@@ -1946,24 +1961,18 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     int32_t *d_w_pair = d_tab, *d_w_text = d_tab + nslots, *d_w_c0 = d_tab + 2 * nslots, *d_w_c1 = d_tab + 3 * nslots;
     int32_t *d_first = d_tab + 4 * nslots, *d_nwin = d_first + n4;
     // ---- the forward pass
-    const int want = panel_scan_slices(C, nslots, K, max_hits), per_slice = (K + want - 1) / want, nslices = (K + per_slice - 1) / per_slice;
+    const PanelCut cut = panel_cut(K, panel_scan_slices(C, nslots, K, max_hits));
+    const int nslices = cut.nslices;
     PanelScanArgs a{};
-    a.pl_m = panel_planes(B, C, D, K, eq, false); a.m_off = D.d_pl_off; a.m_len = D.d_len; a.m_bound = D.d_bound;
-    a.n_members = K; a.per_slice = per_slice;
-    a.pl_t = panel_text_planes(B, C, eq, false); a.pl_t_off = B.d_plt_off; a.t_len = B.d_t_len;
-    a.nslots = (int32_t)nslots; a.w_pair = d_w_pair; a.w_c0 = d_w_c0; a.w_c1 = d_w_c1; a.max_hits = max_hits;
+    const u64* pl_m = panel_planes(B, C, D, K, eq, false);
+    panel_sweep_args(a, B, D, K, cut.per_slice, pl_m, panel_text_planes(B, C, eq, false));
+    a.nslots = (int32_t)nslots; a.text = d_w_pair; a.w_c0 = d_w_c0; a.w_c1 = d_w_c1; a.max_hits = max_hits;      // window slots for text slots
     a.part = C.scratch_p->take<int32_t>(4 * (size_t)nslices * nslots);
     a.raw = C.scratch_p->take<PanelRawHit>((size_t)nslices * nslots * (size_t)max_hits);
     int32_t* const d_base = C.scratch_p->take<int32_t>((size_t)nslices * ntext);
     int32_t* const d_plen = hits_arrays(C, O, n, ntext);
     TimedLaunches tl(C, 0);
-    {
-        // k_panel_hits' launch shape: four window groups per workgroup and launch_groups' claim on the CU's LDS
-        const dim3 grid((unsigned)((ngroups + 3) / 4), (unsigned)nslices);
-        if (eq) hipLaunchKernelGGL(k_panel_scan<SearchEqIupac>, grid, dim3(256), 54 * 1024, C.stream, a);
-        else hipLaunchKernelGGL(k_panel_scan<SearchEq3>, grid, dim3(256), 54 * 1024, C.stream, a);
-    }
-    HIP_CHECK(hipGetLastError());
+    launch_panel_sweep(C, eq, k_panel_scan<SearchEq3>, k_panel_scan<SearchEqIupac>, a, nslots / 64, nslices);
     tl.end();
     // ---- counts per pair and rank bases per (slice, text), offsets in the order of the pairs, the total
     PanelScanCountArgs c{};
@@ -1975,32 +1984,14 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     hipLaunchKernelGGL(k_panel_scan_count, dim3((unsigned)((ntext + 255) / 256)), dim3(256), 0, C.stream, c);
     hits_total(B, C, O, d_plen, B.d_t_len);
     if (O.total <= 0) return O;
-    const size_t nh = (size_t)O.total;
-    O.d_hits = C.scratch_p->take<int32_t>(4 * nh);
     PanelScanExpandArgs e{};
     e.ntext = (int32_t)ntext; e.nslots = (int32_t)nslots; e.nslices = nslices; e.max_hits = max_hits;
     e.w_pair = d_w_pair; e.w_text = d_w_text; e.first_slot = d_first; e.nwin = d_nwin;
-    e.part = a.part; e.raw = a.raw; e.base = d_base; e.off = O.d_off;
-    e.m_len = D.d_len; e.m_off = D.d_pl_off; e.t_len = B.d_t_len; e.t_off = B.d_plt_off; e.hits = O.d_hits;
-    int32_t* const q = C.scratch_p->take<int32_t>(6 * nh);
-    e.o_pair = q; e.o_m = q + nh; e.o_n = q + 2 * nh; e.o_score = q + 3 * nh; e.o_end = q + 4 * nh;
-    int32_t* const o_start = q + 5 * nh;
-    HIP_CHECK(hipMemsetAsync(o_start, 0xFF, nh * sizeof(int32_t), C.stream));
-    e.o_plp_off = C.scratch_p->take<int64_t>(2 * nh);
-    e.o_plt_off = e.o_plp_off + nh;
-    O.d_adv2 = C.scratch_p->take<u32>(nh);
-    HIP_CHECK(hipMemsetAsync(O.d_adv2, 0, nh * sizeof(u32), C.stream));
-    hipLaunchKernelGGL(k_panel_scan_expand, dim3((unsigned)((nslots + 255) / 256), (unsigned)nslices), dim3(256), 0, C.stream, e);
-    HIP_CHECK(hipGetLastError());
-    // ---- the start pass: one lane per stored occurrence over its window, reversed
-    if (!eq) ensure_reversed(B, C);
-    PairView PV = pair_view(B, true);
-    PV.pl_p = panel_planes(B, C, D, K, eq, true); PV.pl_p_off = e.o_plp_off;
-    PV.pl_t = panel_text_planes(B, C, eq, true); PV.pl_t_off = e.o_plt_off;
-    launch_start_pass(C, eq, PV, nh, e.o_pair, e.o_m, e.o_n, e.o_score, e.o_end, o_start, O.d_adv2);
-    hipLaunchKernelGGL(k_panel_hits_finish, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, C.stream, (int64_t)nh, (const int32_t*)o_start, O.d_hits);
-    HIP_CHECK(hipGetLastError());
-    if (sr.cigars) run_panel_align(B, C, sr, D, a.pl_m, a.pl_t, O);
+    e.part = a.part; e.raw = a.raw; e.base = d_base;
+    PanelReversed R{B, C, D, K, eq};
+    panel_occ_records(B, C, sr, D, a, R, true, e, [&](const PanelScanExpandArgs& x) {
+        hipLaunchKernelGGL(k_panel_scan_expand, dim3((unsigned)((nslots + 255) / 256), (unsigned)nslices), dim3(256), 0, C.stream, x);
+    }, O);
     return O;
 }
 

@@ -4,8 +4,9 @@
 // its whole library, CMakeLists.txt:43-49).  TEST INFRASTRUCTURE: nothing of the product includes this file.
 //
 // Model: "device memory" is host memory (calloc) under a byte budget that can be made to fail (hipErrorOutOfMemory) --
-// QE_STUB_HBM_BYTES, default 8 GiB; a kernel launch runs the kernel's host stand-in (qe_kernels_stub.h: real code for the
-// copy / scan / decide kernels the host logic depends on, no-ops for the alignment kernels) at once in the launching thread,
+// QE_STUB_HBM_BYTES, default 8 GiB; a kernel launch runs the kernel's host stand-in (qe_kernels_stub.h, the one header that holds
+// them all: real code for the copy / scan / decide kernels the host logic depends on, the kernels' own per-lane source for the
+// search and panel kernels, no-ops for the alignment kernels) at once in the launching thread,
 // so a stream is always drained and an event is complete as soon as it is recorded.  What the sanitizers then see is the
 // host layer itself: contexts on lease, the per-device book, the rotation, queued runs and fetches, the early-finish
 // threads and their hand-over of batch objects, reclaim under a budget -- with real threads.

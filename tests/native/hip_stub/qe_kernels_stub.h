@@ -5,10 +5,12 @@
 // zeros -- a bound of `QE_STUB_BOUND` and, for every `QE_STUB_SKIP_EVERY`-th task, the "goes on to stage 2" flag, so that
 // the fast flow's overflow path, the early-finish threads and the merged flows all get work.  TEST INFRASTRUCTURE.
 #pragma once
+#define QE_STUB_HAS_EVERY_STAND_IN 1      // qe_driver.hip then looks for no satellite header
 #include <algorithm>
 #include "qe_types.h"
 #include "qe_check.h"
-#include "qe_panel.h"      // and through it qe_search.h, qe_bounded.h, qe_iupac.h
+#include "qe_panel_ham.h"      // and through it qe_panel.h, qe_search.h, qe_bounded.h, qe_iupac.h
+#include "qe_panel_align.h"
 #include "qe_tags.h"
 
 namespace qe {
@@ -228,7 +230,7 @@ static void k_search(SearchArgs A) {
         if (valid) {
             if constexpr (NB > 0) {
                 SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
-                for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+                R.clear();
                 R.load(pp, m);
                 search_run<NB>(R, L, tp, tbit);
             } else {
@@ -267,7 +269,7 @@ static void k_search_hits(SearchHitsArgs X) {
         const u64* tp = A.P.pl_t + Eq::offset(A.P.pl_t_off[pair]);
         if constexpr (NB > 0) {
             SearchRegStore<(NB > 0 ? NB : 1), Eq> R;
-            for (int b = 0; b < NB; ++b) { R.pv[b] = R.mv[b] = 0; R.s[b] = 0; }
+            R.clear();
             R.load(pp, m);
             search_run_hits<NB>(R, L, H, tp, 0);
         } else {
@@ -307,52 +309,132 @@ static void k_pack_iupac(IupacPackArgs A) {
 static void k_planes_iupac(IupacPlanesArgs A) {
     for (int i = 0; i < A.nseq; ++i) iupac_from_planes3(A.src + A.pl_off[i], A.len[i], A.n_empty != 0, A.dst + iupac_offset(A.pl_off[i]));
 }
-// Panel runs: the per-slot functions of qe_panel.h that the device kernels call, run slot by slot and slice by slice with the
-// arguments of the device forms
-template <class Eq>
-static void k_search_panel(PanelArgs A) {
-    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
-    for (int slice = 0; slice < nslices; ++slice)
+// Panel runs: the per-slot functions of qe_panel.h, qe_panel_ham.h and qe_panel_align.h that the device kernels call, with the
+// arguments of the device forms.  The seven per-text sweeps run through one loop over the kernels' own opener: f(S, T) for
+// every slice S and every slot T that has a text, slice by slice
+template <class Eq, class F>
+static void stub_panel_sweep(const PanelSweepArgs& A, F f) {
+    const int nslices = panel_slice(A, 0).nslices;
+    for (int slice = 0; slice < nslices; ++slice) {
+        const PanelSlice S = panel_slice(A, slice);
         for (int slot = 0; slot < A.nslots; ++slot) {
-            const int pair = A.text[slot];
-            if (pair < 0) continue;
-            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
-            PanelKeeper keep;
-            keep.init();
-            u32 steps = 0;
-            panel_text<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, keep, steps,
-                           A.m_score ? A.m_score + (int64_t)pair * A.n_members : nullptr, A.m_score ? A.m_end + (int64_t)pair * A.n_members : nullptr);
-            panel_store_part(A, nslices, slice, slot, keep, steps);
+            const PanelLane T = panel_lane<Eq>(A, slot);
+            if (T.pair >= 0) f(S, T);
         }
+    }
 }
+// the best member per text (PanelArgs), by edits (k_search_panel) and by mismatches only (k_panel_ham: TEXT = panel_ham_text)
+template <class Eq, class Text>
+static void stub_panel_best(const PanelArgs& A, Text text) {
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        PanelKeeper keep;
+        keep.init();
+        u32 steps = 0;
+        text(S.P, S.p0, S.p1, T.tp, T.n, A.mode, keep, steps, A.m_score ? A.m_score + (int64_t)T.pair * A.n_members : nullptr,
+             A.m_score ? A.m_end + (int64_t)T.pair * A.n_members : nullptr);
+        panel_store_part(A, S.nslices, S.slice, T.slot, keep, steps);
+    });
+}
+template <class Eq> static void k_search_panel(PanelArgs A) { stub_panel_best<Eq>(A, [](auto&&... a) { panel_text<Eq>(a...); }); }
+template <class Eq> static void k_panel_ham(PanelArgs A) { stub_panel_best<Eq>(A, [](auto&&... a) { panel_ham_text<Eq>(a...); }); }
 static void k_panel_wire_codes(u64* planes, int64_t rows) { for (int64_t r = 0; r < rows; ++r) planes[3 * r] ^= planes[3 * r + 1]; }
 static void k_panel_reduce(PanelReduceArgs A) { for (int t = 0; t < A.nslots; ++t) panel_reduce_slot(A, t); }
 static void k_panel_finish(int nslots, const int32_t* text, const int32_t* o_pair, const int32_t* o_start, int32_t* hits) {
     for (int t = 0; t < nslots; ++t) panel_finish_slot(t, text, o_pair, o_start, hits);
 }
-// ... and of the all-occurrences panel kernels (PanelHitsArgs, PanelHitsCountArgs, PanelHitsExpandArgs)
+static void k_panel_ham_finish(int64_t npairs, const int32_t* m_len, int32_t* hits) { for (int64_t i = 0; i < npairs; ++i) panel_ham_finish_pair(i, m_len, hits); }
+// ... of the all-occurrences panel kernels (PanelHitsArgs, PanelHitsCountArgs, PanelHitsExpandArgs), the mismatch-only one and
+// the 3' tails among them
 template <class Eq>
 static void k_panel_hits(PanelHitsArgs A) {
-    const int nslices = (A.n_members + A.per_slice - 1) / A.per_slice;
-    PanelView P;
-    P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
-    for (int slice = 0; slice < nslices; ++slice)
-        for (int slot = 0; slot < A.nslots; ++slot) {
-            const int pair = A.text[slot];
-            if (pair < 0) continue;
-            const int p0 = slice * A.per_slice, p1 = std::min(A.n_members, p0 + A.per_slice);
-            PanelHitScan H;
-            panel_hit_scan_init(H, A.raw + ((int64_t)slice * A.nslots + slot) * A.max_hits, A.max_hits);
-            u32 steps = 0;
-            panel_text_hits<Eq>(P, p0, p1, A.pl_t + Eq::offset(A.pl_t_off[pair]), A.t_len[pair], A.mode, H, steps);
-            panel_hits_store_part(A, nslices, slice, slot, H, steps);
-        }
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        PanelHitScan H;
+        panel_hit_scan_init(H, panel_lane_raw(A, S, T), A.max_hits);
+        u32 steps = 0;
+        panel_text_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, H, steps);
+        panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps);
+    });
+}
+template <class Eq>
+static void k_panel_ham_hits(PanelHitsArgs A) {
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        PanelHamScan H;
+        panel_hit_scan_init(H, panel_lane_raw(A, S, T), A.max_hits);
+        u32 steps = 0;
+        panel_ham_text_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, H, steps);
+        panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps);
+    });
+}
+template <class Eq>
+static void k_panel_tails(PanelTailsArgs X) {
+    const PanelHitsArgs& A = X.H;
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        PanelHitScan H;
+        panel_hit_scan_init(H, panel_lane_raw(A, S, T), A.max_hits);
+        PanelTailKeeper keep;
+        keep.init();
+        u32 steps = 0, rows = 0;
+        panel_text_tails<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.mode, X.min_overlap, H, keep, steps, rows);
+        panel_hits_store_part(A, S.nslices, S.slice, T.slot, H, steps);
+        panel_tails_store_part(X, S.nslices, S.slice, T.slot, keep, rows);
+    });
 }
 static void k_panel_hits_count(PanelHitsCountArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_count_slot(A, t); }
 static void k_panel_hits_expand(PanelHitsExpandArgs A) { for (int t = 0; t < A.nslots; ++t) panel_hits_expand_slot(A, t); }
 static void k_panel_hits_finish(int64_t total, const int32_t* o_start, int32_t* hits) { for (int64_t j = 0; j < total; ++j) panel_hits_finish_one(j, o_start, hits); }
+static void k_panel_ham_hits_finish(int64_t total, const int32_t* m_len, int32_t* hits) { for (int64_t j = 0; j < total; ++j) panel_ham_hits_finish_one(j, m_len, hits); }
+// ... of the queued run's three steps behind the offset scan (quicked_batch_configure_panel_queue)
+static void k_panel_queue_expand(PanelHitsExpandArgs A, int64_t cap) { for (int t = 0; t < A.nslots; ++t) panel_queue_expand_slot(A, t, cap); }
+static void k_panel_queue_finish(const int64_t* total, int64_t cap, const int32_t* o_start, int32_t* hits) {
+    for (int64_t j = 0; j < cap; ++j) panel_queue_finish_one(j, total, cap, o_start, hits);
+}
+static void k_panel_queue_clamp(int64_t n, int64_t cap, int64_t* off, int64_t* q) {
+    for (int64_t i = 0; i <= n; ++i) panel_queue_clamp_one(i, n, cap, off, q);
+}
+// ... of the steps behind k_panel_tails (QUICKED_PANEL_TAILS), and of the 5' heads (QUICKED_PANEL_HEADS)
+static void k_panel_tails_merge(PanelTailsMergeArgs A) { for (int t = 0; t < A.nslots; ++t) panel_tails_merge_slot(A, t); }
+template <class Eq>
+static void k_panel_tail_planes(PanelTailPlanesArgs A) { for (int t = 0; t < A.nslots; ++t) panel_tail_planes_slot<Eq>(A, t); }
+static void k_panel_tails_finish(int nslots, const int32_t* o_pair, const int32_t* o_start, int32_t* tails) {
+    for (int t = 0; t < nslots; ++t) panel_tails_finish_slot(t, o_pair, o_start, tails);
+}
+template <class Eq>
+static void k_panel_heads(PanelHeadsArgs A) {
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        PanelTailKeeper keep;
+        keep.init();
+        u32 steps = 0, rows = 0;
+        panel_text_heads<Eq>(S.P, S.p0, S.p1, T.tp, T.n, A.min_overlap, keep, steps, rows);
+        panel_heads_store_part(A, S.nslices, S.slice, T.slot, keep, rows, steps);
+    });
+}
+static void k_panel_heads_merge(PanelHeadsMergeArgs A) { for (int t = 0; t < A.nslots; ++t) panel_heads_merge_slot(A, t); }
+template <class Eq>
+static void k_panel_head_planes(PanelHeadPlanesArgs A) { for (int t = 0; t < A.nslots; ++t) panel_head_planes_slot<Eq>(A, t); }
+static void k_panel_heads_finish(int nslots, const int32_t* o_pair, const int32_t* o_start, int32_t* heads) {
+    for (int t = 0; t < nslots; ++t) panel_heads_finish_slot(t, o_pair, o_start, heads);
+}
+// ... of the windowed run (quicked_batch_run_panel_scan): window slots for text slots
+template <class Eq>
+static void k_panel_scan(PanelScanArgs A) {
+    stub_panel_sweep<Eq>(A, [&](const PanelSlice& S, const PanelLane& T) {
+        const int c0 = A.w_c0[T.slot], c1 = A.w_c1[T.slot];
+        PanelWindowScan H;
+        panel_window_scan_init(H, panel_lane_raw(A, S, T), A.max_hits, c0, c1);
+        u32 steps = 0;
+        panel_window_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, c0, c1, H, steps);
+        panel_scan_store_part(A, S.nslices, S.slice, T.slot, H, steps);
+    });
+}
+static void k_panel_scan_sums(PanelScanCountArgs A) { for (int s = 0; s < A.nslices; ++s) for (int t = 0; t < A.ntext; ++t) panel_scan_sums_slice(A, s, t); }
+static void k_panel_scan_count(PanelScanCountArgs A) { for (int t = 0; t < A.ntext; ++t) panel_scan_count_text(A, t); }
+static void k_panel_scan_expand(PanelScanExpandArgs A) {
+    for (int s = 0; s < A.nslices; ++s) for (int w = 0; w < A.nslots; ++w) panel_scan_expand_lane(A, s, w);
+}
+// ... and of the occurrence aligner (QUICKED_PANEL_CIGARS; qe_panel_align.h), occurrence by occurrence
+template <class Eq>
+static void k_panel_occ_align(PanelAlignArgs A) { for (int64_t k = 0; k < A.count; ++k) panel_align_occ<Eq>(A, k); }
+static void k_panel_align_sizes(int64_t total, const int32_t* hits, int32_t* len) { for (int64_t j = 0; j < total; ++j) panel_align_size_one(j, hits, len); }
 // The tag kernels: the walker of qe_tags.h on the host, both forms
 template <bool WRITE> static void k_tags_segs(SegTagArgs T) {
     const SegFormatArgs& A = T.F;

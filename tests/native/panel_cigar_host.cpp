@@ -1,6 +1,6 @@
 // Occurrence alignments (QUICKED_PANEL_CIGARS) on the HOST, under sanitizers: the library's host layer built with g++ against the
 // fake HIP runtime of tests/native/hip_stub.  The stand-ins of k_panel_occ_align / k_panel_align_sizes
-// (hip_stub/qe_kernels_stub_align.h) are the device kernels' own source (qe_panel_align.h) run occurrence by occurrence, the
+// (hip_stub/qe_kernels_stub.h) are the device kernels' own source (qe_panel_align.h) run occurrence by occurrence, the
 // sweeps' stand-ins run the real recurrences and the stand-in of k_pack_iupac is the scalar packer of qe_iupac.h, so a run
 // under an IUPAC flag of an ASCII batch gives true answers here: they are compared with the strings
 // tests/test_host_panel_cigar.py took from the fixture (file `cases` in the directory given; tests/panel_cigar_lib.py's format).
@@ -10,36 +10,12 @@
 // strings for quicked_batch_run_panel_all (PREFIX, INFIX) and quicked_batch_run_panel_scan (windows 64 and 0) in styles 0, 1, 2
 // at caps 1, 2 and 64, with the history's budget unset and 1 KiB (one wave per launch: kernel_times slot [1] counts them); the
 // results of the run without the bit -- records, scores, statuses, counter [0] -- unchanged by the bit; counters [1] and [3].
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "panel_cigar_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "panel_cigar_host"
+#include "panel_host_common.h"
 
 struct Occ { int32_t pattern, start, end, score; std::string want[3]; };
 struct Conf { int mode, flag, uniform; std::vector<std::vector<Occ>> want; };
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
 
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_env(const char* name, const char* v) {
-    if (v) setenv(name, v, 1); else unsetenv(name);
-    CHECK(quicked_debug_reload_env() >= 0);
-}
 struct Results {
     std::vector<int32_t> found, stored, sc, st;
     std::vector<int64_t> off;
@@ -70,23 +46,6 @@ static void strings_refused(quicked_batch_t* b) {
     char p[4];
     CHECK(quicked_batch_panel_hit_cigar_bytes(b) == -1);
     CHECK(quicked_batch_panel_hit_cigars(b, p, o) == QUICKED_ERROR);
-}
-// the strings of the last run, one per stored occurrence; every one NUL-terminated inside the pool
-static std::vector<std::string> strings_of(quicked_batch_t* b) {
-    const int64_t bytes = quicked_batch_panel_hit_cigar_bytes(b), total = quicked_batch_panel_hit_total(b);
-    CHECK(bytes >= 0 && total >= 0);
-    std::vector<char> pool((size_t)bytes + 1, 'Z');
-    std::vector<int64_t> off((size_t)total + 1, -7);
-    CHECK(quicked_batch_panel_hit_cigars(b, pool.data(), off.data()) == QUICKED_OK);
-    CHECK(quicked_batch_panel_hit_cigars(b, nullptr, nullptr) == QUICKED_OK);
-    CHECK(pool[(size_t)bytes] == 'Z' && off[(size_t)total] == -7);
-    std::vector<std::string> out;
-    for (int64_t j = 0; j < total; ++j) {
-        CHECK(off[(size_t)j] >= 0 && off[(size_t)j] < bytes);
-        CHECK(memchr(pool.data() + off[(size_t)j], 0, (size_t)(bytes - off[(size_t)j])) != nullptr);
-        out.emplace_back(pool.data() + off[(size_t)j]);
-    }
-    return out;
 }
 
 int main(int argc, char** argv) {

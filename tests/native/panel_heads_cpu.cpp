@@ -165,12 +165,12 @@ static long run_conf(const Group& G, const Conf& cf) {
         const int per = (K + want_slices - 1) / want_slices, ns = (K + per - 1) / per;
         std::vector<int32_t> hpart((size_t)5 * (size_t)ns * (size_t)nslots, -7);
         qe::PanelHeadsArgs A{};
-        A.pl_m_rev = M.rev.data(); A.m_off = M.off.data(); A.m_len = M.len.data(); A.m_bound = G.bound.data();
+        A.pl_m = M.rev.data(); A.m_off = M.off.data(); A.m_len = M.len.data(); A.m_bound = G.bound.data();
         A.n_members = K; A.per_slice = per;
         A.pl_t = T.fwd.data(); A.pl_t_off = T.off.data(); A.t_len = T.len.data();
         A.nslots = nslots; A.text = text.data(); A.min_overlap = cf.min_overlap; A.hpart = hpart.data();
         qe::PanelView P;
-        P.pl = A.pl_m_rev; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
+        P.pl = A.pl_m; P.off = A.m_off; P.len = A.m_len; P.bound = A.m_bound;
         uint64_t all_steps = 0, all_rows = 0;
         for (int s = 0; s < ns; ++s)
             for (int t = 0; t < nslots; ++t) {

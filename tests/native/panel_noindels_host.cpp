@@ -1,6 +1,6 @@
 // Mismatch-only panel runs (QUICKED_PANEL_NO_INDELS on quicked_batch_run_panel / _run_panel_all) on the HOST, under sanitizers:
 // the library's host layer built with g++ against the fake HIP runtime of tests/native/hip_stub.  The stand-ins of k_panel_ham /
-// k_panel_ham_hits and the two finish steps (hip_stub/qe_kernels_stub_noindels.h) are the device kernels' own source
+// k_panel_ham_hits and the two finish steps (hip_stub/qe_kernels_stub.h) are the device kernels' own source
 // (qe_panel_ham.h) run slot by slot, and the stand-in of k_pack_iupac is the scalar packer of qe_iupac.h, so a run under one of
 // the IUPAC flags gives true answers here: they are compared with what tests/test_host_panel_noindels.py computed with
 // tests/panel_noindels_lib.py (file `cases` in the directory given; the format of tests/native/panel_noindels_cpu.cpp).  A run
@@ -9,37 +9,13 @@
 // huge and caps of 1, 2 and the file's, and every getter the contract names -- results, matrix, counts, total, records, scores,
 // statuses, counters [0] .. [7], kernel_times slot [0] -- with the other families' refusals.
 // A stand-alone program: nothing is loaded into Python.
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "panel_noindels_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "panel_noindels_host"
+#include "panel_host_common.h"
 
 struct Occ { int32_t pattern, start, end, score; };
 struct Conf { int mode, flag; std::vector<std::vector<int32_t>> d, e; std::vector<int32_t> found; std::vector<std::vector<Occ>> occ; };
 struct Group { std::vector<std::string> panel, texts; std::vector<int32_t> bound; std::vector<Conf> confs; };
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
 
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_env(const char* name, const char* v) {
-    if (v) setenv(name, v, 1); else unsetenv(name);
-    CHECK(quicked_debug_reload_env() >= 0);
-}
 static const int NI = QUICKED_PANEL_NO_INDELS, INFIX = QUICKED_SEARCH_INFIX, PREFIX = QUICKED_SEARCH_PREFIX;
 
 static int64_t block_steps(const Group& g, int mode) {

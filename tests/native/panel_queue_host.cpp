@@ -1,5 +1,5 @@
 // Queued panel runs (quicked_batch_configure_panel_queue) on the HOST, under sanitizers: the library's host layer built with g++
-// against the fake HIP runtime of tests/native/hip_stub.  The stand-ins of the new kernels (hip_stub/qe_kernels_stub_queue.h) are
+// against the fake HIP runtime of tests/native/hip_stub.  The stand-ins of the new kernels (hip_stub/qe_kernels_stub.h) are
 // the device kernels' own per-slot source (qe_panel.h); the stand-in of k_pack_iupac is the scalar packer, so the runs under an
 // IUPAC flag give true answers here.  They are compared with the definitions tests/test_host_panel_queue.py wrote (file `cases`
 // in the directory given; tests/panel_queue_lib.py's format): occurrence lists, tails and heads, the best member derived from
@@ -12,22 +12,10 @@
 // 4096, counter [0] against the sync run's; the overflow rule at max_total 1, 2, W - 1, W, W + 1; a second queued run
 // superseding the first; reload and destroy with a run pending; the fetch from another thread; six batch objects with six
 // panels queued before the first fetch and fetched in reverse; `wanted` after each kind of run.
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "panel_queue_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "panel_queue_host"
+#include "panel_host_common.h"
 
 static const int INFIX = QUICKED_SEARCH_INFIX, PREFIX = QUICKED_SEARCH_PREFIX, TL = QUICKED_PANEL_TAILS, HD = QUICKED_PANEL_HEADS;
 static const int FLAGS[3] = {0, QUICKED_SEARCH_IUPAC, QUICKED_SEARCH_IUPAC_PATTERN};
@@ -41,18 +29,6 @@ struct Group {
     std::vector<std::vector<Four>> tails[3], heads[3];     // [flag][min_overlap index]
 };
 static std::vector<int32_t> g_overlaps;
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
-
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_env(const char* name, const char* v) {
-    if (v) setenv(name, v, 1); else unsetenv(name);
-    CHECK(quicked_debug_reload_env() >= 0);
-}
 
 // ---- what every getter answers, status and data: equal snapshots = nothing the caller can see has changed
 struct Snapshot {

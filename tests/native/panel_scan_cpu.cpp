@@ -140,7 +140,7 @@ static long run_conf(const Conf& cf, const std::vector<std::string>& panel, cons
                 A.pl_m = M.fwd.data(); A.m_off = M.off.data(); A.m_len = M.len.data(); A.m_bound = bound.data();
                 A.n_members = K; A.per_slice = per;
                 A.pl_t = T.fwd.data(); A.pl_t_off = T.off.data(); A.t_len = T.len.data();
-                A.nslots = nslots; A.w_pair = w_pair.data(); A.w_c0 = w_c0.data(); A.w_c1 = w_c1.data(); A.max_hits = cap; A.part = part.data(); A.raw = raw.data();
+                A.nslots = nslots; A.text = w_pair.data(); A.w_c0 = w_c0.data(); A.w_c1 = w_c1.data(); A.max_hits = cap; A.part = part.data(); A.raw = raw.data();
                 uint64_t walked = 0, owned = 0;
                 for (int s = 0; s < ns; ++s)
                     for (int w = 0; w < nslots; ++w) {

@@ -1,6 +1,6 @@
 // Windowed panel runs (quicked_batch_run_panel_scan) on the HOST, under sanitizers: the library's host layer built with g++
 // against the fake HIP runtime of tests/native/hip_stub.  The stand-ins of k_panel_scan / k_panel_scan_count /
-// k_panel_scan_expand (hip_stub/qe_kernels_stub_scan.h) are the device kernels' own source (qe_panel.h) run lane by lane, the
+// k_panel_scan_expand (hip_stub/qe_kernels_stub.h) are the device kernels' own source (qe_panel.h) run lane by lane, the
 // stand-in of k_search<4, Eq> runs the real recurrence and the stand-in of k_pack_iupac is the scalar packer of qe_iupac.h, so
 // a FLAGGED run of an ASCII batch gives true answers here: they are compared with the lists tests/test_host_panel_scan.py took
 // from the fixture (file `cases` in the directory given; tests/panel_hits_lib.py's format) and with quicked_batch_run_panel_all
@@ -10,41 +10,12 @@
 // results cleared by a reload, QE_PANEL_SLICES = 1, 2 and a huge value, a 1 KiB QE_PANEL_HITS_RAW_KB, windows of 64, 128 and
 // the library's.
 // A stand-alone program: nothing is loaded into Python.
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "panel_scan_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "panel_scan_host"
+#include "panel_host_common.h"
 
 struct Occ { int32_t pattern, start, end, score; };
 struct Conf { int mode, flag, uniform; std::vector<std::vector<Occ>> want; };
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
 
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_env(const char* name, const char* v) {
-    if (v) setenv(name, v, 1); else unsetenv(name);
-    CHECK(quicked_debug_reload_env() >= 0);
-}
-static int64_t steps_of(quicked_batch_t* b) {
-    int64_t c[8];
-    CHECK(quicked_batch_counters(b, c) >= 0);
-    return c[0];
-}
 // everything the three getters and the scores give after a run of the kind
 struct Results {
     std::vector<int32_t> found, stored, sc, st;

@@ -1,6 +1,6 @@
 // The 3' tails of the panel search (QUICKED_PANEL_TAILS) on the HOST, under sanitizers: the library's host layer built with g++
 // against the fake HIP runtime of tests/native/hip_stub.  The stand-ins of k_panel_tails, k_panel_tails_merge,
-// k_panel_tail_planes and k_panel_tails_finish (hip_stub/qe_kernels_stub_tails.h) are the device kernels' own source (qe_panel.h)
+// k_panel_tail_planes and k_panel_tails_finish (hip_stub/qe_kernels_stub.h) are the device kernels' own source (qe_panel.h)
 // run slot by slot, the start pass's stand-in runs the real recurrence and the stand-in of k_pack_iupac is the scalar packer of
 // qe_iupac.h, so a run under an IUPAC flag of an ASCII batch gives true answers here: they are compared with the tails
 // tests/test_panel_tails_cpu.py took from the fixture (file `cases` in the directory given; tests/panel_tails_lib.py's format).
@@ -11,37 +11,13 @@
 // -- text_start from the start pass -- on every case under both flags with QE_PANEL_SLICES unset, 1 and 4096, with and without
 // QUICKED_PANEL_CIGARS, at min_overlap 1, 3 and 256; the results of the run without the bit -- records, counts, scores, statuses,
 // counter [0], the strings -- unchanged by the bit; counter [2]; a batch without a single full occurrence.
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "panel_tails_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "panel_tails_host"
+#include "panel_host_common.h"
 
 struct Tail { int32_t pattern, overlap, start, score; };
 struct Conf { int flag, min_overlap; std::vector<Tail> want; };
 struct Group { std::vector<std::string> panel, texts; std::vector<int32_t> bound; std::vector<Conf> confs; };
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
 
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_env(const char* name, const char* v) {
-    if (v) setenv(name, v, 1); else unsetenv(name);
-    CHECK(quicked_debug_reload_env() >= 0);
-}
 struct Results {
     std::vector<int32_t> found, stored, sc, st;
     std::vector<int64_t> off;
@@ -66,16 +42,6 @@ static Results results_of(quicked_batch_t* b, int64_t n) {
     CHECK(quicked_batch_counters(b, c) >= 0);
     R.steps = c[0];
     return R;
-}
-static std::vector<std::string> strings_of(quicked_batch_t* b) {
-    const int64_t bytes = quicked_batch_panel_hit_cigar_bytes(b), total = quicked_batch_panel_hit_total(b);
-    CHECK(bytes >= 0 && total >= 0);
-    std::vector<char> pool((size_t)bytes + 1, 'Z');
-    std::vector<int64_t> off((size_t)total + 1, -7);
-    CHECK(quicked_batch_panel_hit_cigars(b, pool.data(), off.data()) == QUICKED_OK);
-    std::vector<std::string> out;
-    for (int64_t j = 0; j < total; ++j) { CHECK(off[(size_t)j] >= 0 && off[(size_t)j] < bytes); out.emplace_back(pool.data() + off[(size_t)j]); }
-    return out;
 }
 static void tails_refused(quicked_batch_t* b) {
     quicked_panel_tail_t t[4];

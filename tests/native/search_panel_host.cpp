@@ -7,40 +7,10 @@
 // k_pack never wrote: only its statuses and the shape of its results are checked.  Checked: every QUICKED_ERROR and
 // QUICKED_UNIMPLEMENTED rule with nothing launched, the getters' rules before and after other kinds of run, results cleared by
 // a reload, QE_PANEL_SLICES = 1, 2 and a huge value.  A stand-alone program: nothing is loaded into Python.
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "quicked.h"
-#include "quicked_batch.h"
-
-extern "C" quicked_status_t quicked_debug_reload_env(void);
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "search_panel_host: %s failed at line %d\n", #cond, __LINE__); exit(1); } } while (0)
+#define PANEL_HOST_NAME "search_panel_host"
+#include "panel_host_common.h"
 
 struct Conf { int mode, flag, uniform; std::vector<std::vector<int32_t>> want; };
-struct Pool { std::string bytes; std::vector<int64_t> off; std::vector<int32_t> len; };
-
-static Pool pool_of(const std::vector<std::string>& seqs) {
-    Pool P;
-    for (const std::string& s : seqs) { P.off.push_back((int64_t)P.bytes.size()); P.len.push_back((int32_t)s.size()); P.bytes += s; }
-    P.bytes.push_back('\0');
-    return P;
-}
-static void set_slices(const char* v) {
-    if (v) setenv("QE_PANEL_SLICES", v, 1); else unsetenv("QE_PANEL_SLICES");
-    CHECK(quicked_debug_reload_env() >= 0);
-}
-static int64_t steps_of(quicked_batch_t* b) {
-    int64_t c[8];
-    CHECK(quicked_batch_counters(b, c) >= 0);
-    return c[0];
-}
 
 int main(int argc, char** argv) {
     CHECK(argc == 2);
@@ -155,7 +125,7 @@ int main(int argc, char** argv) {
     CHECK(!memcmp(hits.data(), hits0.data(), hits.size() * sizeof(quicked_panel_hit_t)));
     // ---- true answers under the two flags, every configuration, with the slices forced and chosen
     for (const char* slices : {(const char*)nullptr, "1", "2", "1000000000000"}) {
-        set_slices(slices);
+        set_env("QE_PANEL_SLICES", slices);
         for (const Conf& cf : confs) {
             if (!cf.flag) continue;
             CHECK(quicked_batch_configure_tags(b, QUICKED_TAG_STATS) == QUICKED_OK);      // ignored: no alignments
@@ -186,7 +156,7 @@ int main(int argc, char** argv) {
             CHECK(quicked_batch_pair_stats(b, &ps) == QUICKED_ERROR);
         }
     }
-    set_slices(nullptr);
+    set_env("QE_PANEL_SLICES", nullptr);
     // ---- an unflagged run: statuses and shapes (the stub's k_pack writes no planes)
     CHECK(run(PREFIX, nullptr, 3) == QUICKED_OK);
     CHECK(quicked_batch_panel_results(b, hits.data()) == QUICKED_OK);
