@@ -516,6 +516,34 @@ int64_t          quicked_batch_panel_queue_wanted(quicked_batch_t* batch);
  * quicked_batch_run_search / _run_search_all; members over 256 bases; reverse-complement members; a per-member choice of
  * distance within one run. */
 enum { QUICKED_PANEL_NO_INDELS = 32768 };      /* OR-ed into mode of quicked_batch_run_panel / _run_panel_all (4, 8, 128, 256, 1024, 4096 and 16384 stay unknown bits) */
+/* Windowed panel search by mismatches only: the flagged quicked_batch_run_panel_all for a few LONG texts -- a panel of guides,
+ * primers or probes against a genome or the contigs of an assembly: every site within k mismatches, no bulges, a PAM written
+ * with IUPAC N.  A function of its own with quicked_batch_run_panel_scan's argument list; QUICKED_PANEL_NO_INDELS on
+ * quicked_batch_run_panel_scan itself stays an unknown bit, as said above.  Here the bit in `mode` is accepted and means
+ * nothing more: a caller may pass the mode it gives quicked_batch_run_panel_all.
+ *
+ * The contract is one sentence: for every input it accepts it leaves exactly what quicked_batch_run_panel_all leaves for the
+ * same batch, panel, mode | QUICKED_PANEL_NO_INDELS, bounds and max_hits, whatever `window` is -- found, stored, the records
+ * in (pattern, text_end) order and which ones the cap keeps; text_start = text_end - m; quicked_batch_scores, the statuses,
+ * empty texts; texts shorter than a member; both IUPAC flags; ASCII and both packed wires.  The three getters of
+ * quicked_batch_run_panel_all serve it; every other getter behaves as after a flagged quicked_batch_run_panel_all.
+ * A lane owns the ends in its window (c0, c1].  R[e] reads text[e - m, e) only, so a lane needs no warm-up: per member it
+ * computes the one start c0 - m, whose value is the previous column of its first owned end (c0 < m: no such column, the first
+ * owned end is m; c1 < m: the window owns nothing), then its owned ends, then the ends past c1 only while a valley that began
+ * in the window is still pending.
+ * Counters: [0] is the block steps really walked -- per (window slot, member) the starts from max(0, c0 - m) to the last one
+ * of the run-out, x ceil(m / 64) --, [1] .. [7] are 0; the kernels' time is in kernel_times slot [0].
+ *
+ * window: quicked_batch_run_panel_scan's rules -- 0 (the library's choice) or a multiple of 64, with the same 2^26 rules.
+ * QUICKED_ERROR, nothing launched: everything quicked_batch_run_panel_scan answers so; QUICKED_PANEL_MATRIX, QUICKED_PANEL_TAILS
+ * and QUICKED_PANEL_HEADS (unknown bits of the scan).
+ * QUICKED_UNIMPLEMENTED, nothing launched: the base mode QUICKED_SEARCH_PREFIX; QUICKED_PANEL_CIGARS; sync == 0, also on a batch
+ * object that quicked_batch_configure_panel_queue switched on; a member over QUICKED_PANEL_MAX_LEN; check != 0.
+ * Not built: CIGARs, tails and heads; queued runs; members over 256 bases; reverse-complement members. */
+quicked_status_t quicked_batch_run_panel_scan_no_indels(quicked_batch_t* batch, int mode,
+                                              int32_t n_patterns, const char* panel_pool, const int64_t* panel_off, const int32_t* panel_len,
+                                              const int32_t* max_dist /* n_patterns values, or NULL */, int32_t max_dist_all,
+                                              int32_t max_hits, int32_t window, int sync);
 quicked_status_t quicked_batch_sync(quicked_batch_t* batch);
 /* Brings the results of the batch's last sync == 0 run to the host: waits for that run (only that one: later runs of
  * this or other batches keep executing) and copies scores / statuses / CIGARs / counters to where the getters read

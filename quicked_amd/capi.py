@@ -67,6 +67,7 @@ EXPORTS = ["quicked_check_error", "quicked_status_msg", "quicked_default_params"
            "quicked_batch_configure_panel_tails", "quicked_batch_panel_tails",
            "quicked_batch_configure_panel_heads", "quicked_batch_panel_heads",
            "quicked_batch_configure_panel_queue", "quicked_batch_panel_queue_wanted",
+           "quicked_batch_run_panel_scan_no_indels",
            "quicked_batch_configure_tags", "quicked_batch_pair_stats", "quicked_batch_md_bytes", "quicked_batch_md"]
 
 TAG_STATS, TAG_MD, TAG_NO_CIGAR = 1, 2, 4
@@ -147,6 +148,9 @@ def lib():
     L.quicked_batch_run_panel_all.restype = C.c_int
     L.quicked_batch_run_panel_scan.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int]
     L.quicked_batch_run_panel_scan.restype = C.c_int
+    if hasattr(L, "quicked_batch_run_panel_scan_no_indels"):      # (an older build loaded for an A/B run lacks the newer symbols)
+        L.quicked_batch_run_panel_scan_no_indels.argtypes = L.quicked_batch_run_panel_scan.argtypes
+        L.quicked_batch_run_panel_scan_no_indels.restype = C.c_int
     L.quicked_batch_panel_hit_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.quicked_batch_panel_hit_counts.restype = C.c_int
     L.quicked_batch_panel_hit_total.argtypes = [C.c_void_p]
@@ -566,6 +570,16 @@ class ResidentBatch:
         (0: the library's choice; else a multiple of 64) and a lane per window: for a few long texts.  INFIX only; mode's flags,
         panel, max_dist and max_hits as in run_panel_all (PANEL_CIGARS included).  Read through panel_hit_counts() / panel_hits() /
         panel_hit_cigars().  Sync runs only."""
+        return self._run_panel_scan(self._lib.quicked_batch_run_panel_scan, mode, panel, max_dist, max_hits, window, sync)
+
+    def run_panel_scan_no_indels(self, mode, panel, max_dist=None, max_hits=16, window=0, sync=True):
+        """quicked_batch_run_panel_scan_no_indels: run_panel_all(mode | PANEL_NO_INDELS)'s results, exactly, with every text cut
+        into windows of `window` columns (0: the library's choice; else a multiple of 64) and a lane per window: a panel by
+        mismatches only against a few long texts.  INFIX only; PANEL_NO_INDELS in mode is accepted and means nothing more.  Read
+        through panel_hit_counts() / panel_hits().  Sync runs only."""
+        return self._run_panel_scan(self._lib.quicked_batch_run_panel_scan_no_indels, mode, panel, max_dist, max_hits, window, sync)
+
+    def _run_panel_scan(self, entry, mode, panel, max_dist, max_hits, window, sync):
         panel = [bytes(p) for p in panel]
         k = len(panel)
         pool = np.frombuffer(b"".join(panel) + b"\0", dtype=np.uint8)
@@ -578,8 +592,8 @@ class ResidentBatch:
             md, md_all = np.ascontiguousarray(max_dist, dtype=np.int32), 0
             if md.shape != (k,):
                 raise ValueError("max_dist: one bound per panel member")
-        return self._lib.quicked_batch_run_panel_scan(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data,
-                                                      None if md is None else md.ctypes.data, int(md_all), int(max_hits), int(window), 1 if sync else 0)
+        return entry(self._h, int(mode), k, pool.ctypes.data, poff.ctypes.data, plen.ctypes.data,
+                     None if md is None else md.ctypes.data, int(md_all), int(max_hits), int(window), 1 if sync else 0)
 
     def panel_hit_counts(self):
         """-> (found, stored) int32 arrays of the last all-occurrences panel run: found[i] occurrences of all members in text i

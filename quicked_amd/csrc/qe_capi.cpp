@@ -436,6 +436,34 @@ QE_API quicked_status_t quicked_batch_run_panel_scan(quicked_batch_t* batch, int
     }, &arg);
 }
 
+// Windowed panel search by mismatches only: the scan's checks in the scan's order; QUICKED_PANEL_NO_INDELS is accepted and means
+// nothing more, the strings are not built
+QE_API quicked_status_t quicked_batch_run_panel_scan_no_indels(quicked_batch_t* batch, int mode, int32_t n_patterns, const char* panel_pool,
+                                                               const int64_t* panel_off, const int32_t* panel_len, const int32_t* max_dist,
+                                                               int32_t max_dist_all, int32_t max_hits, int32_t window, int sync) {
+    const bool cigars = (mode & QUICKED_PANEL_CIGARS) != 0;
+    const int eq = search_mode_eq(mode & ~(QUICKED_PANEL_CIGARS | QUICKED_PANEL_NO_INDELS));
+    bool too_long = false;
+    if (!panel_args_ok(batch, eq, n_patterns, panel_pool, panel_off, panel_len, max_dist, max_dist_all, too_long)) return QUICKED_ERROR;
+    if (max_hits < 1 || max_hits > 4096) return QUICKED_ERROR;
+    if (window < 0 || window % 64 != 0 || window > 0x7FFFFFC0) return QUICKED_ERROR;
+    PanelRun pr{n_patterns, panel_pool, panel_off, panel_len, false};
+    struct Arg { SearchRun sr; bool too_long, cigars; int sync; } arg{{mode & 15, max_dist, max_dist_all, max_hits, eq, &pr, window}, too_long, cigars, sync};
+    arg.sr.no_indels = true;
+    return guard(batch, [](quicked_batch* B, void* a) {
+        Arg* x = (Arg*)a;
+        int64_t texts = 0;
+        for (int64_t i = 0; i < B->n; ++i) texts += B->t_len[(size_t)i] > 0;
+        if (texts * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;
+        if (x->sr.window > 0 && panel_scan_slots(*B, x->sr.window) * x->sr.max_hits > ((int64_t)1 << 26)) return QUICKED_ERROR;
+        if (x->sr.mode == QUICKED_SEARCH_PREFIX) return QUICKED_UNIMPLEMENTED;      // one start per member: the flagged quicked_batch_run_panel_all serves it
+        if (x->cigars || !x->sync) return QUICKED_UNIMPLEMENTED;                    // the occurrences alone, and sync only
+        if (x->too_long) return QUICKED_UNIMPLEMENTED;                              // the register form holds four blocks
+        if (B->check) return QUICKED_UNIMPLEMENTED;                                 // as quicked_batch_run_search
+        return run_batch(*B, banded_params(true), true, nullptr, &x->sr);
+    }, &arg);
+}
+
 QE_API quicked_status_t quicked_batch_panel_hit_counts(quicked_batch_t* batch, int32_t* found, int32_t* stored) {
     return hit_counts(batch, &HostResults::panel_found, &HostResults::panel_occ_off, found, stored);
 }

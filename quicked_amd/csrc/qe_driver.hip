@@ -66,6 +66,12 @@
 #include "qe_kernels_stub_noindels.h"
 #endif
 #endif
+// (the windowed mismatch-only run's stand-ins lie in a header of their own beside either layout)
+#if !defined(__HIPCC__) && defined(__has_include)
+#if __has_include("qe_kernels_stub_noindels_scan.h")
+#include "qe_kernels_stub_noindels_scan.h"
+#endif
+#endif
 
 
 namespace qe {

@@ -1982,6 +1982,27 @@ __global__ __launch_bounds__(256) void k_panel_scan(PanelScanArgs A) {
 }
 template __global__ void k_panel_scan<SearchEq3>(PanelScanArgs);
 template __global__ void k_panel_scan<SearchEqIupac>(PanelScanArgs);
+// The same by mismatches only (qe_panel_ham.h; quicked_batch_run_panel_scan_no_indels): k_panel_scan's shell,
+// grid, argument block and `part` / `raw` layouts around k_panel_ham_hits' body under the window rule
+// (panel_ham_member_window).  The lead-in's shift (c0 - m) & 63 is the same for every lane of the wave that has a lead-in.
+// No LDS of its own, no workspace, no task list, no start pass.
+template <class Eq>
+__global__ __launch_bounds__(256) void k_panel_ham_scan(PanelScanArgs A) {
+    const int g = QE_GROUP_INDEX();
+    if (g * 64 >= A.nslots) return;
+    const PanelSlice S = panel_slice(A, (int)blockIdx.y);
+    const PanelLane T = panel_lane<Eq>(A, g * 64 + (int)(threadIdx.x & 63));
+    if (!__any(T.pair >= 0)) return;
+    int c0 = 0, c1 = 0;
+    if (T.pair >= 0) { c0 = A.w_c0[T.slot]; c1 = A.w_c1[T.slot]; }
+    PanelHamWindowScan H;
+    panel_ham_window_scan_init(H, panel_lane_raw(A, S, T), T.pair >= 0 ? A.max_hits : 0, c0, c1);
+    u32 steps = 0;
+    panel_ham_window_hits<Eq>(S.P, S.p0, S.p1, T.tp, T.n, c0, c1, H, steps);      // (a lane without a text has c1 = 0: no start)
+    if (T.pair >= 0) panel_scan_store_part(A, S.nslices, S.slice, T.slot, H, steps);
+}
+template __global__ void k_panel_ham_scan<SearchEq3>(PanelScanArgs);
+template __global__ void k_panel_ham_scan<SearchEqIupac>(PanelScanArgs);
 
 // one thread per (slice, text) over the text's window slots, then one thread per text over the slices: the counts merged and
 // every slice's rank base (PanelScanCountArgs); then -- behind k_scan_offsets -- one thread per lane (slice, window slot): its stored records ranked among the text's and put in
@@ -1997,6 +2018,11 @@ __global__ __launch_bounds__(256) void k_panel_scan_count(PanelScanCountArgs A) 
 __global__ __launch_bounds__(256) void k_panel_scan_expand(PanelScanExpandArgs A) {
     const int w = blockIdx.x * 256 + threadIdx.x;
     if (w < A.nslots) panel_scan_expand_lane(A, (int)blockIdx.y, w);
+}
+// the same ranking without start-pass tasks, for k_panel_ham_scan's records: k_panel_ham_hits_finish writes text_start behind it
+__global__ __launch_bounds__(256) void k_panel_ham_scan_expand(PanelScanExpandArgs A) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w < A.nslots) panel_scan_expand_lane_of<false>(A, (int)blockIdx.y, w);
 }
 
 // The alignment of every stored occurrence (qe_panel_align.h; QUICKED_PANEL_CIGARS): one lane per occurrence

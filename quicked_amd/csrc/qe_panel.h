@@ -830,7 +830,9 @@ QE_S_HD int32_t panel_scan_members_below(const PanelRawHit* raw, int32_t have, i
     }
     return lo;
 }
-QE_S_HD void panel_scan_expand_lane(const PanelScanExpandArgs& A, int s, int w) {
+// TASKS: with the records' start-pass tasks; without (the mismatch-only scan, qe_panel_ham.h) text_start is left 0 and no o_* is touched
+template <bool TASKS>
+QE_S_HD void panel_scan_expand_lane_of(const PanelScanExpandArgs& A, int s, int w) {
     const int pair = A.w_pair[w];
     if (pair < 0) return;
     const int64_t stride = (int64_t)A.nslices * A.nslots;
@@ -853,14 +855,18 @@ QE_S_HD void panel_scan_expand_lane(const PanelScanExpandArgs& A, int s, int w) 
         const int32_t rank = base + i + others;
         if (rank >= A.max_hits) break;          // (ranks ascend within a lane)
         const int64_t j = j0 + rank;
-        const int m = A.m_len[h.pattern];
-        int32_t task_n, in_end, start;
-        search_hit_task(m, n, h.end, h.score, task_n, in_end, start);
-        A.o_pair[j] = (int32_t)j; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = h.score; A.o_end[j] = in_end;
-        A.o_plp_off[j] = A.m_off[h.pattern]; A.o_plt_off[j] = A.t_off[pair];
+        int32_t start = 0;
+        if (TASKS) {
+            const int m = A.m_len[h.pattern];
+            int32_t task_n, in_end;
+            search_hit_task(m, n, h.end, h.score, task_n, in_end, start);
+            A.o_pair[j] = (int32_t)j; A.o_m[j] = m; A.o_n[j] = task_n; A.o_score[j] = h.score; A.o_end[j] = in_end;
+            A.o_plp_off[j] = A.m_off[h.pattern]; A.o_plt_off[j] = A.t_off[pair];
+        }
         int32_t* o = A.hits + 4 * j;
         o[0] = h.pattern; o[1] = start; o[2] = h.end; o[3] = h.score;
     }
 }
+QE_S_HD void panel_scan_expand_lane(const PanelScanExpandArgs& A, int s, int w) { panel_scan_expand_lane_of<true>(A, s, w); }
 
 }  // namespace qe

@@ -16,6 +16,9 @@
 // position-wise equality (Eq::eq_pos), masked to the block's rows, and a population count of the zeros.  Everything about
 // the member -- planes, length, row masks, bound -- is the same for every lane (scalar registers on the device).
 // Text words past the one that holds column n - 1 are never read; every loop is bounded by n, m and the block count.
+//
+// The end of the file is the same run with long texts split across lanes (quicked_batch_run_panel_scan_no_indels; DESIGN.md
+// 4.14.8): k_panel_ham_scan, a window slot per lane.
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +31,40 @@ template <class Eq>
 QE_S_HD void panel_ham_word(const uint64_t* tp, int idx, int last, uint64_t (&t)[Eq::W]) {
     for (int k = 0; k < Eq::W; ++k) t[k] = idx <= last ? tp[Eq::W * (int64_t)idx + k] : 0;
 }
+
+// What a sweep holds per member and lane: the member's rows and row masks (the same for every lane) and the chain of NB + 1
+// words per text plane.  value(): H of the start the chain stands at; shift(): the chain down by one position.  The windowed
+// sweep at the end of the file is written over it.  panel_ham_sweep below keeps the same steps written out: over this struct
+// k_panel_ham / k_panel_ham_hits came out with another instruction stream, and in the one run that measured it
+// k_panel_ham_hits was 5 % behind (profiles/panel_noindels_scan.md, "The fold that was not kept"); as it stands their
+// assembly is the parent commit's line for line.
+template <int NB, class Eq>
+struct PanelHamChain {
+    uint64_t p[NB][Eq::W], mask[NB], t[NB + 1][Eq::W];
+    int nb;
+    QE_S_HD void member(const uint64_t* pp, int m) {
+        nb = search_blocks(m);
+        QE_S_UNROLL
+        for (int b = 0; b < NB; ++b) {
+            Eq::pattern_rows(pp, m, b, p[b]);
+            const int rows = search_rows(b, m);
+            mask[b] = rows >= 64 ? ~(uint64_t)0 : (rows > 0 ? ((uint64_t)1 << rows) - 1 : 0);
+        }
+    }
+    QE_S_HD int32_t value() const {
+        int32_t v = 0;
+        QE_S_UNROLL
+        for (int b = 0; b < NB; ++b)
+            if (b < nb) v += search_popc(~Eq::eq_pos(p[b], t[b]) & mask[b]);
+        return v;
+    }
+    QE_S_HD void shift() {
+        QE_S_UNROLL
+        for (int i = 0; i < NB; ++i)
+            for (int k = 0; k < Eq::W; ++k) t[i][k] = (t[i][k] >> 1) | (t[i + 1][k] << 63);
+        for (int k = 0; k < Eq::W; ++k) t[NB][k] >>= 1;
+    }
+};
 
 // One member of NB blocks at the most (planes pp, m bases) against one text (planes tp, n columns): out.put(e, R[e]) for every
 // e of E in ascending order.  steps: block steps -- the starts x the member's blocks --, added to
@@ -97,16 +134,18 @@ QE_S_HD void panel_ham_text(const PanelView& P, int p0, int p1, const uint64_t* 
 // beside it.  It walks w = min(R, k + 1) as that scan does: a value above k is no occurrence, ends a plateau as a rise
 // whatever it is, and is a column every value <= k lies below.  A pending plateau is emitted when w rises or E ends
 // (finish) and dropped when w falls.
-struct PanelHamScan : PanelHitScan {
+template <class Range>
+struct PanelHamScanOf : SearchHitScanOf<PanelHitSink, Range> {
     int32_t k;
-    QE_S_HD void member(int bound) { k = bound; prev = k + 1; pend_end = -1; pend_val = 0; }      // column m - 1: higher than every value
+    QE_S_HD void member(int bound) { k = bound; this->prev = k + 1; this->pend_end = -1; this->pend_val = 0; }      // column m - 1: higher than every value
     QE_S_HD void put(int32_t e, int32_t v) {
         const int32_t w = v <= k ? v : k + 1;
-        if (w < prev) { pend_end = e; pend_val = w; }
-        else if (w > prev) emit();
-        prev = w;
+        if (w < this->prev) { this->pend_end = Range::owns(e) ? e : -1; this->pend_val = w; }      // (a window's lane: a descent outside (c0, c1] clears)
+        else if (w > this->prev) this->emit();
+        this->prev = w;
     }
 };
+typedef PanelHamScanOf<SearchAllColumns> PanelHamScan;
 template <int NB, class Eq>
 QE_S_HD void panel_ham_member_hits(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int mode, PanelHamScan& H, uint32_t& steps) {
     H.member(search_effective(bound, m));
@@ -131,6 +170,73 @@ QE_S_HD void panel_ham_finish_pair(int64_t i, const int32_t* m_len, int32_t* hit
 QE_S_HD void panel_ham_hits_finish_one(int64_t j, const int32_t* m_len, int32_t* hits) {
     int32_t* o = hits + 4 * j;
     o[1] = o[2] - m_len[o[0]];
+}
+
+// ---- every occurrence, long texts split across lanes (quicked_batch_run_panel_scan_no_indels)
+// A lane is a window slot {pair, c0, c1} of qe_panel.h's windowed run and owns the ends e in (c0, c1].  R[e] = H[e - m] reads
+// text[e - m, e) only, so there is no warm-up in that run's sense: the lane's row is the text's row wherever it computes it.
+// Per member of m bases it walks the starts s0 = max(0, c0 - m) upwards:
+//   lead-in   c0 >= m: the one start c0 - m, whose value R[c0] is the scan's `prev` for the first owned end.  The scan takes it
+//             as a column it does not own.  c0 < m: no such column exists -- the scan starts at "higher than every value", and
+//             the first owned end is m.  c1 < m (the window lies wholly below m, or n < m): nothing is owned, nothing walked.
+//   owned     the starts up to c1 - m: a descent of min(R, k + 1) makes a candidate.
+//   run-out   the starts after c1 - m, one by one while the candidate is pending: a rise or the text's end emits it, a descent
+//             clears it (PanelHamScanOf<SearchOwnedColumns>: that valley's first end is a later window's).  A plateau that
+//             enters from the left is w == prev at the first owned end: no candidate.
+// The chain starts at s0, which lies on no word boundary: it is loaded at the word that holds s0 and shifted down by s0 & 63
+// once -- the same shift for every lane of a wave with c0 >= m, m being the wave's and c0 a multiple of 64 --, and takes its
+// next word whenever a start crosses into a new word.  A member longer than the window reaches back over several earlier
+// windows' words.  Words past the one that holds column n - 1 are never read; every loop is bounded by n, m and the block count.
+// steps: (the starts walked, s0 to the last one of the run-out) x the member's blocks.
+typedef PanelHamScanOf<SearchOwnedColumns> PanelHamWindowScan;
+QE_S_HD void panel_ham_window_scan_init(PanelHamWindowScan& H, PanelRawHit* out, int32_t cap, int32_t c0, int32_t c1) {
+    panel_window_scan_init(H, out, cap, c0, c1);
+    H.k = 0;
+}
+// the first start a lane walks and the end of its owned stretch (exclusive); first >= own_end: the lane walks nothing
+QE_S_HD void panel_ham_window_starts(int m, int c0, int c1, int& first, int& own_end) {
+    first = c0 > m ? c0 - m : 0;
+    own_end = c1 >= m ? c1 - m + 1 : 0;
+}
+template <int NB, class Eq>
+QE_S_HD void panel_ham_member_window(const uint64_t* pp, int m, int bound, const uint64_t* tp, int n, int c0, int c1, PanelHamWindowScan& H, uint32_t& steps) {
+    H.member(search_effective(bound, m));
+    int s, own_end;
+    panel_ham_window_starts(m, c0, c1, s, own_end);
+    if (s >= own_end) return;                                   // (c1 <= n, so n >= m from here on)
+    const int nstarts = n - m + 1, first = s;
+    PanelHamChain<NB, Eq> C;
+    C.member(pp, m);
+    const int last = (n - 1) >> 6;
+    QE_S_UNROLL
+    for (int i = 0; i <= NB; ++i) panel_ham_word<Eq>(tp, (s >> 6) + i, last, C.t[i]);
+    // (per lane: lanes with c0 < m shift by 0 beside lanes that shift by (c0 - m) & 63, so the amount is no scalar)
+    const int sh = s & 63;
+    if (sh) {
+        QE_S_UNROLL
+        for (int i = 0; i < NB; ++i)
+            for (int k = 0; k < Eq::W; ++k) C.t[i][k] = (C.t[i][k] >> sh) | (C.t[i + 1][k] << (64 - sh));
+        for (int k = 0; k < Eq::W; ++k) C.t[NB][k] >>= sh;
+    }
+    // one start: its value to the scan, the chain down by one position; the next word when the next start opens one
+    auto step = [&]() { H.put(s + m, C.value()); C.shift(); ++s; };
+    auto next_word = [&]() { if (!(s & 63)) panel_ham_word<Eq>(tp, (s >> 6) + NB, last, C.t[NB]); };
+    while (s < own_end) {                                       // the lead-in start and the owned ones, word by word
+        const int left = own_end - s, cnt = left < 64 - (s & 63) ? left : 64 - (s & 63);
+        for (int j = 0; j < cnt; ++j) step();
+        next_word();
+    }
+    while (s < nstarts && H.pend_end >= 0) { step(); next_word(); }      // the run-out
+    H.finish();                                                 // still pending: the walk reached the text's end, where a plateau counts
+    steps += (uint32_t)(s - first) * (uint32_t)C.nb;
+}
+// The window (c0, c1] of one text against the members [p0, p1): panel_window_hits' arguments and results under this file's definition
+template <class Eq>
+QE_S_HD void panel_ham_window_hits(const PanelView& P, int p0, int p1, const uint64_t* tp, int n, int c0, int c1, PanelHamWindowScan& H, uint32_t& steps) {
+    panel_each_member<Eq>(P, p0, p1, [&](auto NB, int p, const uint64_t* pp, int m, int bound) {
+        H.sink.member = p;
+        panel_ham_member_window<NB, Eq>(pp, m, bound, tp, n, c0, c1, H, steps);
+    });
 }
 
 }  // namespace qe

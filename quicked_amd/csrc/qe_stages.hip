@@ -1898,7 +1898,8 @@ static int32_t panel_scan_window(const quicked_batch& B, const Context& C, const
     const PanelRun& pr = *sr.panel;
     int64_t columns = 0, longest = 0, warm = 64;
     for (int64_t i = 0; i < B.n; ++i) { columns += B.t_len[(size_t)i]; longest = std::max<int64_t>(longest, B.t_len[(size_t)i]); }
-    for (int32_t p = 0; p < pr.n_patterns; ++p) warm = std::max<int64_t>(warm, panel_window_warmup(pr.len[p], sr.max_dist ? sr.max_dist[p] : sr.max_dist_all));
+    // (the mismatch-only scan has no warm-up: the term stays at its floor)
+    for (int32_t p = 0; p < pr.n_patterns && !sr.no_indels; ++p) warm = std::max<int64_t>(warm, panel_window_warmup(pr.len[p], sr.max_dist ? sr.max_dist[p] : sr.max_dist_all));
     const int64_t whole = std::min<int64_t>(std::max<int64_t>(64, (longest + 63) / 64 * 64), 0x7FFFFFC0);      // one window per text
     // (whole workgroups of four groups, rounded down, and the window rounded up: one group over two rounds of the chip is a third)
     const int64_t groups = std::max<int64_t>(4, (2 * (int64_t)chip(C.device).slots2() + pr.n_patterns - 1) / pr.n_patterns / 4 * 4);
@@ -1937,9 +1938,12 @@ static size_t panel_scan_fixed_bytes(const quicked_batch& B, const Context& C, c
     b += wslots * 16 + n * 8 + ntext * 8 + n * 12 + (n + 1) * 8 + 16 * 512;
     return b + panel_align_fixed_bytes(B, sr);
 }
+// (quicked_batch_run_panel_scan_no_indels, sr.no_indels; DESIGN.md 4.14.8: k_panel_ham_scan in k_panel_scan's place, the
+// ranking step without start-pass tasks and text_start = text_end - m behind it; never with strings)
 static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchRun& sr) {
     const PanelRun& pr = *sr.panel;
     const int K = pr.n_patterns, eq = sr.eq, max_hits = sr.max_hits;
+    const bool infix = !sr.no_indels;                 // (the run's mode is INFIX always: whether a start pass follows)
     HitsOut O;
     const PanelDev D = panel_upload(B, C, sr);
     O.task_pair = D.text;
@@ -1972,7 +1976,8 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     int32_t* const d_base = C.scratch_p->take<int32_t>((size_t)nslices * ntext);
     int32_t* const d_plen = hits_arrays(C, O, n, ntext);
     TimedLaunches tl(C, 0);
-    launch_panel_sweep(C, eq, k_panel_scan<SearchEq3>, k_panel_scan<SearchEqIupac>, a, nslots / 64, nslices);
+    if (sr.no_indels) launch_panel_sweep(C, eq, k_panel_ham_scan<SearchEq3>, k_panel_ham_scan<SearchEqIupac>, a, nslots / 64, nslices);
+    else launch_panel_sweep(C, eq, k_panel_scan<SearchEq3>, k_panel_scan<SearchEqIupac>, a, nslots / 64, nslices);
     tl.end();
     // ---- counts per pair and rank bases per (slice, text), offsets in the order of the pairs, the total
     PanelScanCountArgs c{};
@@ -1989,8 +1994,10 @@ static HitsOut run_search_panel_scan(quicked_batch& B, Context& C, const SearchR
     e.w_pair = d_w_pair; e.w_text = d_w_text; e.first_slot = d_first; e.nwin = d_nwin;
     e.part = a.part; e.raw = a.raw; e.base = d_base;
     PanelReversed R{B, C, D, K, eq};
-    panel_occ_records(B, C, sr, D, a, R, true, e, [&](const PanelScanExpandArgs& x) {
-        hipLaunchKernelGGL(k_panel_scan_expand, dim3((unsigned)((nslots + 255) / 256), (unsigned)nslices), dim3(256), 0, C.stream, x);
+    panel_occ_records(B, C, sr, D, a, R, infix, e, [&](const PanelScanExpandArgs& x) {
+        const dim3 grid((unsigned)((nslots + 255) / 256), (unsigned)nslices);
+        if (infix) hipLaunchKernelGGL(k_panel_scan_expand, grid, dim3(256), 0, C.stream, x);
+        else hipLaunchKernelGGL(k_panel_ham_scan_expand, grid, dim3(256), 0, C.stream, x);
     }, O);
     return O;
 }
